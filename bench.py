@@ -36,6 +36,8 @@ Timing protocol: the K timed steps carry HIP events around the roofline kernel o
 breakdown (`mfma_kernels`) comes from 3 further untimed steps.  `--history H` times BASELINE.json configs[2]: every
 sample is a queue of H history frames (obtain_history_bev: backbone + BEV encoder per frame, each attending to the rotated
 BEV of the frame before) followed by the current frame's full pass with that history.
+`--dump-outputs DIR` saves what the last timed step returned (rank 0) as DIR/<name>.npy, for output-for-output comparison
+of two builds on the same seeded inputs.
 
 `python bench.py --gpus N` with no torchrun environment re-executes itself under torch.distributed.run with N
 ranks (the reference's tools/dist_train.sh:9-11 role); under torchrun it reads RANK/LOCAL_RANK/WORLD_SIZE.
@@ -102,9 +104,12 @@ def parse():
     ap.add_argument("--mode", choices=["infer", "train"], default="infer",
                     help="infer (default, the BASELINE metric): forward pass; train: forward + loss + "
                          "backward + DDP/RCCL gradient all-reduce + clip + AdamW step per sample")
-    ap.add_argument("--passes", type=int, default=0,
+    ap.add_argument("--passes", type=int, default=1,
                     help="timed passes of --steps steps each (value = the median pass; min / max reported); "
-                         "default 0 = 5 passes when --steps < 50, else 3")
+                         "default 1: exactly --steps timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy "
+                         "(float32; inference: occ class index + flow, train: the losses), at most 64 MB in all")
     ap.add_argument("--history", type=int, default=0,
                     help="BASELINE.json configs[2] (temporal self-attention with a real history): every sample = this many "
                          "history frames through BEVFormerOcc.obtain_history_bev (reference bevformer_occ.py:159-178) + "
@@ -737,6 +742,41 @@ def _bench_parity(head_cfg, ora, feats, metas, out_o, device, n_layers):
             "parity_case": f"{n_layers} encoder layers + lifter + Conv3d decoder + heads, full base geometry, fp32 features"}, prod
 
 
+DUMP_LIMIT = 63 << 20        # array bytes written by --dump-outputs, all arrays together (.npy headers: under 64 MB)
+
+
+def _host_outputs(res):
+    """[(name, host array)] of what one step returned: inference (occ class index, flow), train the loss dict.
+    float64 stays float64, everything else becomes float32 (the class indices are exact in float32)."""
+    import numpy as np
+    items = sorted(res.items()) if isinstance(res, dict) else list(zip(("occ", "flow"), res))
+    out = []
+    for name, v in items:
+        v = v.detach().cpu() if torch.is_tensor(v) else torch.as_tensor(v)
+        v = v.double() if v.dtype == torch.float64 else v.float()
+        out.append((name, np.ascontiguousarray(v.numpy())))
+    return out
+
+
+def dump_outputs(path, arrays):
+    """Write every (name, array) as path/<name>.npy.  Past DUMP_LIMIT in all, each array is replaced by the same share
+    of its flattened elements, picked by a fixed seed (sorted), so that two runs sample the same positions."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = sum(a.nbytes for _, a in arrays)
+    manifest = {}
+    for name, a in arrays:
+        entry = {"shape": list(a.shape), "dtype": str(a.dtype), "sampled": None}
+        if total > DUMP_LIMIT:
+            k = max(1, a.size * DUMP_LIMIT // total)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[idx]
+            entry["sampled"] = {"elements": int(k), "of": int(np.prod(entry["shape"])), "seed": 0}
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        manifest[name] = entry
+    return manifest
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -866,6 +906,7 @@ def main():
     else:
         args.step_graph = False
     enqueue_s = []
+    last_out = [None]
 
     def timed_pass(steps):
         """barrier + synchronize, `steps` steps, synchronize + barrier; MAX over ranks -> seconds"""
@@ -877,7 +918,7 @@ def main():
         for step_i in range(steps):
             if args.per_step:       # GPU-side time of every step (events on the current stream; no host sync)
                 e0 = torch.cuda.Event(enable_timing=True); e0.record()
-            run_step()
+            last_out[0] = run_step()
             if args.per_step:
                 e1 = torch.cuda.Event(enable_timing=True); e1.record()
                 step_events.append((e0, e1))
@@ -901,9 +942,12 @@ def main():
         ext.kernel_timing_only({"sca_fused_forward"})
     # P passes of EXACTLY K steps each, every one bracketed by barrier + synchronize; the line's `value` is the MEDIAN pass
     # and carries min / max (one 0.11-s pass cannot resolve a 3 % delta between boxes that differ by 3-4 %)
-    n_pass = args.passes if args.passes > 0 else (5 if args.steps < 50 else 3)
+    n_pass = max(args.passes, 1)
     pass_s = [timed_pass(args.steps) for _ in range(n_pass)]
     elapsed = sorted(pass_s)[len(pass_s) // 2]
+    # the last timed step's result, copied to the host before any further step can overwrite its buffers
+    dumped = (_host_outputs(graph_out if args.step_graph else last_out[0])
+              if args.dump_outputs and rank == 0 else None)
     for _ in range(5):
         torch.cuda.synchronize()
         t_e = time.perf_counter()
@@ -1141,6 +1185,8 @@ def main():
                         out["fp32_conformant"] = {"error": repr(e)}
         if world == 1 and args.mode == "infer" and not args.no_extras and not args.history and stepper.scope == "e2e":
             out["extra"] = extra_legs(args, cfg, model, geo, device)
+        if dumped is not None:
+            out["dump_outputs"] = dump_outputs(args.dump_outputs, dumped)
         print(json.dumps(out), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -73,6 +73,27 @@ def metric_golden():
           f'mAVE {arrays["mave"]:.4f} OccScore {occ_score:.4f}')
 
 
+def dvr_kernel_golden():
+    """The reference's ray-casting kernel body (dvr.cu:69-319, compiled for the host by oracle/build_ref.py) on the ray sets
+    of DVR_KERNEL_CASES, both phases, and its fused-multiply-add build on 'nuscenes_grid' (test phase)."""
+    from oracle.refshim import _reference_dvr
+    from tests.golden_cases import DVR_FIELDS, DVR_KERNEL_CASES
+    from tests.test_gpu_dvr import _case
+    ref, fma = _reference_dvr(), _reference_dvr('libdvr_reference_fma.so')
+    arrays = {}
+    for name, (seed, N, T, Z, Y, X, M, occ) in DVR_KERNEL_CASES:
+        sigma, origin, points, tindex = _case(seed, N, T, Z, Y, X, M, occ, outside=name == "origin_outside")
+        runs = [(phase, ref, phase) for phase in ("test", "train")]
+        if name == "nuscenes_grid":
+            runs.append(("fma_test", fma, "test"))
+        for tag, lib, phase in runs:
+            for field, a in zip(DVR_FIELDS, lib.render_forward(sigma, origin, points, tindex, [T, Z, Y, X], phase)):
+                arrays[f'{name}_{tag}_{field}'] = a.numpy()
+    path = os.path.join(OUT, 'dvr_reference_kernel.npz')
+    np.savez_compressed(path, **arrays)
+    print(f'dvr_reference_kernel: wrote {path} ({os.path.getsize(path) / 1e6:.2f} MB)')
+
+
 def arrays_lists(arrays, prefix):
     return [arrays[f'{prefix}_{i}'] for i in range(len(METRIC_SEEDS))]
 
@@ -238,8 +259,12 @@ if __name__ == '__main__':
     if '--full-only' in sys.argv:
         fullsize_golden()
         sys.exit(0)
+    if '--dvr-only' in sys.argv:
+        dvr_kernel_golden()
+        sys.exit(0)
     if '--metrics-only' not in sys.argv:
         main()
         fullsize_golden()
         datasets_golden()
+        dvr_kernel_golden()
     metric_golden()

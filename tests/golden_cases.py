@@ -112,6 +112,13 @@ def checksum(tensors):
 # ---- RayIoU / mAVE / OccScore -----------------------------------------------------------
 METRIC_SEEDS = (41, 42)
 
+# ray sets of tests/test_gpu_dvr.py::_case (seed, N, T, Z, Y, X, M, occupancy) on which the reference's ray-casting
+# kernel pins oracle/dvr_ref.c (tests/golden/dvr_reference_kernel.npz); 'nuscenes_grid' also with fused multiply-adds
+DVR_KERNEL_CASES = (("small_dense", (1, 2, 1, 4, 6, 8, 300, 0.3)), ("time_indexed", (2, 2, 3, 8, 20, 24, 2000, 0.05)),
+                    ("nuscenes_grid", (3, 1, 1, 16, 200, 200, 14040, 0.02)), ("empty_grid", (4, 1, 1, 16, 50, 50, 500, 0.0)),
+                    ("origin_outside", (5, 1, 1, 16, 40, 40, 800, 0.1)))
+DVR_FIELDS = ("pred_dist", "gt_dist", "coord_index")
+
 
 def metric_scene(seed):
     """A seeded synthetic occupancy scene at the metric's hard-coded size (ray_metrics.py:209-212 reshapes to

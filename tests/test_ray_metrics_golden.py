@@ -7,8 +7,8 @@ with the reference's ray-casting kernel body (dvr.cu:69-319) compiled for the ho
 Checked against it:
   not gpu   oracle/ray_metrics_ref.py (the restatement) + oracle/dvr_ref.c (plain-C ray caster): bit-exact rays,
             identical scores;  occnet_amd.metrics.calc_metrics (vectorised product mirror): identical scores;
-            oracle/dvr_ref.c vs the reference kernel on random / adversarial rays (container only: needs
-            oracle/_ref built from /root/reference, or prebuilt and shipped);
+            oracle/dvr_ref.c vs the reference kernel on random / adversarial rays (its results stored in
+            tests/golden/dvr_reference_kernel.npz; live as well where oracle/_ref is built);
   gpu       the HIP pipeline (occ_dvr_render_forward_f32 + occnet_amd.metrics) end to end: bit-exact rays, same score.
 """
 import os
@@ -17,10 +17,11 @@ import numpy as np
 import pytest
 import torch
 
-from tests.golden_cases import METRIC_SEEDS, metric_scene
+from tests.golden_cases import DVR_FIELDS, DVR_KERNEL_CASES, METRIC_SEEDS, metric_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = os.path.join(ROOT, 'tests', 'golden', 'ray_metrics.npz')
+DVR_GOLD = os.path.join(ROOT, 'tests', 'golden', 'dvr_reference_kernel.npz')
 REF_SO = os.path.join(ROOT, 'oracle', '_ref', 'libdvr_reference.so')
 
 
@@ -79,43 +80,63 @@ def test_product_calc_metrics_matches_reference_golden(gold):
     assert gold['metric_py_ave'].shape == gold['ave'].shape
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO), reason="oracle/_ref not built (python -m oracle.build_ref)")
+@pytest.fixture(scope='module')
+def dvr_gold():
+    return dict(np.load(DVR_GOLD))
+
+
+def _dvr_case(name, args):
+    from tests.test_gpu_dvr import _case
+    seed, N, T, Z, Y, X, M, occ = args
+    return _case(seed, N, T, Z, Y, X, M, occ, outside=name == "origin_outside"), [T, Z, Y, X]
+
+
 @pytest.mark.parametrize("phase", ["test", "train"])
-def test_c_oracle_matches_reference_kernel(phase):
+def test_c_oracle_matches_reference_kernel(dvr_gold, phase):
     """oracle/dvr_ref.c (the restatement the HIP kernel is held to, bit for bit) vs the reference's own kernel body
     compiled for the host: random occupancy, time-indexed grids, origins outside, padded / axis-aligned /
-    near-zero-length rays (the cases of tests/test_gpu_dvr.py)."""
+    near-zero-length rays (the cases of tests/test_gpu_dvr.py).  The kernel's results are stored in
+    tests/golden/dvr_reference_kernel.npz (oracle/gen_golden.py); where oracle/_ref is built, the kernel runs live too."""
     from oracle import ray_metrics_ref as oref
-    from oracle.refshim import _reference_dvr
-    from tests.test_gpu_dvr import _case
     try:
         oref.dvr_lib()
     except FileNotFoundError:
         pytest.skip("oracle/_build/libdvr_ref.so not built (make -C oracle)")
-    ref = _reference_dvr()
-    for name, args in (("small_dense", (1, 2, 1, 4, 6, 8, 300, 0.3)), ("time_indexed", (2, 2, 3, 8, 20, 24, 2000, 0.05)),
-                       ("nuscenes_grid", (3, 1, 1, 16, 200, 200, 14040, 0.02)), ("empty_grid", (4, 1, 1, 16, 50, 50, 500, 0.0)),
-                       ("origin_outside", (5, 1, 1, 16, 40, 40, 800, 0.1))):
-        seed, N, T, Z, Y, X, M, occ = args
-        sigma, origin, points, tindex = _case(seed, N, T, Z, Y, X, M, occ, outside=name == "origin_outside")
-        want = ref.render_forward(sigma, origin, points, tindex, [T, Z, Y, X], phase)
+    ref = None
+    if os.path.exists(REF_SO):
+        from oracle.refshim import _reference_dvr
+        ref = _reference_dvr()
+    for name, args in DVR_KERNEL_CASES:
+        (sigma, origin, points, tindex), grid = _dvr_case(name, args)
         got = oref.render_forward(sigma, origin, points, tindex, phase)
-        for nm, a, b in zip(("pred_dist", "gt_dist", "coord_index"), got, want):
-            assert torch.equal(a, b), (name, phase, nm, int((a != b).sum()))
+        wants = [[torch.from_numpy(dvr_gold[f'{name}_{phase}_{nm}']) for nm in DVR_FIELDS]]
+        if ref is not None:
+            wants.append(ref.render_forward(sigma, origin, points, tindex, grid, phase))
+        for want in wants:
+            for nm, a, b in zip(DVR_FIELDS, got, want):
+                assert torch.equal(a, b), (name, phase, nm, int((a != b).sum()))
 
 
-@pytest.mark.skipif(not os.path.exists(REF_SO.replace('.so', '_fma.so')), reason="oracle/_ref not built")
-def test_fma_contraction_moves_no_voxel_and_distances_by_ulps():
+def test_fma_contraction_moves_no_voxel_and_distances_by_ulps(dvr_gold):
     """nvcc contracts a*b+c into fused multiply-adds by default; the oracle and the HIP kernel do not.  On the
-    nuScenes-sized case the reference kernel built both ways picks the same voxel for every ray and its distances
-    agree to a few float32 ulps — far below the metric's 1 m threshold."""
-    from oracle.refshim import _reference_dvr
-    from tests.test_gpu_dvr import _case
-    sigma, origin, points, tindex = _case(3, 1, 1, 16, 200, 200, 14040, 0.02)
-    a = _reference_dvr().render_forward(sigma, origin, points, tindex, [1, 16, 200, 200], "test")
-    b = _reference_dvr('libdvr_reference_fma.so').render_forward(sigma, origin, points, tindex, [1, 16, 200, 200], "test")
-    assert torch.equal(a[2], b[2])
-    assert float((a[0] - b[0]).abs().max()) < 1e-4
+    nuScenes-sized case the reference kernel built with contraction (stored in tests/golden/dvr_reference_kernel.npz,
+    live as well where oracle/_ref is built) picks the same voxel for every ray as the oracle (= the reference kernel
+    without contraction, test_c_oracle_matches_reference_kernel) and its distances agree to a few float32 ulps — far
+    below the metric's 1 m threshold."""
+    from oracle import ray_metrics_ref as oref
+    try:
+        oref.dvr_lib()
+    except FileNotFoundError:
+        pytest.skip("oracle/_build/libdvr_ref.so not built (make -C oracle)")
+    (sigma, origin, points, tindex), grid = _dvr_case("nuscenes_grid", dict(DVR_KERNEL_CASES)["nuscenes_grid"])
+    a = oref.render_forward(sigma, origin, points, tindex, "test")
+    fmas = [[torch.from_numpy(dvr_gold[f'nuscenes_grid_fma_test_{nm}']) for nm in DVR_FIELDS]]
+    if os.path.exists(REF_SO.replace('.so', '_fma.so')):
+        from oracle.refshim import _reference_dvr
+        fmas.append(_reference_dvr('libdvr_reference_fma.so').render_forward(sigma, origin, points, tindex, grid, "test"))
+    for b in fmas:
+        assert torch.equal(a[2], b[2])
+        assert float((a[0] - b[0]).abs().max()) < 1e-4
 
 
 @pytest.mark.gpu
