@@ -592,6 +592,14 @@ int occ_conv3x3_nhwc_bf16(const void* x, const void* weight_packed, const float*
  * occ_value_range_scale_from_amax. */
 int occ_conv3x3_nhwc_bf16_amax(const void* x, const void* weight_packed, const float* bias, void* out, int batch,
                                int H, int W, int Cin, int Cout, int stride, int relu, uint32_t* amax8, void* stream);
+/* Either of the two with the tile forced (tests, probes): variant = 10 * NT + RT, a block of 4 waves computes
+ * (2 * RT) x 16 output pixels x (128 * NT) channels; stride 1 has 12, 13, 14, 16, 18, 22, 23, 24, stride 2 has 12, 13,
+ * 22 (NT 2 needs Cout % 256 == 0); 0 lets the launcher choose from the shape as the two entry points above do.  amax8
+ * may be NULL (no max|out|).  A variant the shape lacks returns OCC_E_UNSUPPORTED.  Variants differ from each other only
+ * in f32 summation order. */
+int occ_conv3x3_nhwc_bf16_variant(const void* x, const void* weight_packed, const float* bias, void* out, int batch,
+                                  int H, int W, int Cin, int Cout, int stride, int relu, uint32_t* amax8, int variant,
+                                  void* stream);
 
 /* MFMA B-operand packing: f32 row-major (N, K) matrix -> bf16 in v_mfma_f32_32x32x16_bf16 fragment order
  * packed[((ks * N/32 + nt) * 64 + lane) * 8 + j] = w[nt*32 + (lane & 31)][ks*16 + (lane >> 5)*8 + j], so a wave

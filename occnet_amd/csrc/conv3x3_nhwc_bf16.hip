@@ -7,15 +7,21 @@
 // FPN output / extra-level convolutions, when Cout % 128 == 0 and Cin % 32 == 0; the 7x7 stem stays on MIOpen
 // (the 64-channel layer1 blocks have their own whole-bottleneck kernel).
 //
-// GEMM view: M = output pixels, N = Cout, K = 9 taps x Cin.  Block = 4 waves x (8 x 16 output pixels = four
+// GEMM view: M = output pixels, N = Cout, K = 9 taps x Cin.  Block = 4 waves x (2*RT x 16 output pixels = RT
 // 32-pixel MFMA row tiles of two image rows each) x 128*NT output channels; waves split N.  Per chunk of 32
-// input channels the (8+2) x (16+2) pixel halo is staged ONCE into LDS (zero-filled outside the image =
+// input channels the (2*RT+2) x (16+2) pixel halo (stride 2: (4*RT+1) x 33) is staged ONCE into LDS (zero-filled outside the image =
 // the convolution's padding; double buffered; 80-byte pixel slots, 1536-byte halo rows: conflict-free
 // ds_read_b128) and reused by the 9 taps with compile-time offsets; the weights are pre-packed in MFMA
 // B-fragment order ([chunk][tap][k-step][Cout/32][lane][8]) and every wave streams the operands of its own
 // 32*NT columns global -> registers through a ring of 6 k-steps — they never touch LDS;
 // the chunk order is rotated per block (L2 channel hot-spotting, see conv1x1_nhwc_bf16.hip).
 // v_mfma_f32_32x32x16_bf16, 2 k-steps per (chunk, tap).
+//
+// Variants (id 10 * NT + RT; the launcher picks one per shape, occ_conv3x3_nhwc_bf16_variant forces one): RT = 2..8 row
+// tiles per wave, i.e. 64..256 output pixels per block, and NT = 1 or 2.  Every wave streams 1 KB of weights per k-step
+// and column tile whatever RT is, so a taller tile feeds more MFMAs from the same weight bytes and stages less halo per
+// pixel; a shorter one pads less on small maps and gives a larger grid; NT 2 stages each halo chunk once for 256
+// channels and halves the A-fragment reads per MFMA.
 #include "common.h"
 
 namespace occ {
@@ -28,10 +34,13 @@ constexpr int kC3PX = 80;                             // bytes per halo pixel sl
 // Tile geometry per stride S: output tile TH x 16, input halo HH x HW.  Stride 2 keeps the halo columns
 // DE-INTERLEAVED in LDS (17 even columns, then 17 odd-column slots): for a fixed tap the 16 output pixels of a
 // row then read 16 CONSECUTIVE 80-byte slots, conflict-free like stride 1 (a 160-byte lane stride is not).
-template <int S> struct C3Geom {
-  static constexpr int TH = S == 1 ? 8 : 4, RT = TH / 2;
-  static constexpr int HH = (TH - 1) * S + 3, HW = (kC3TW - 1) * S + 3;     // 10 x 18  /  9 x 33
-  static constexpr int ROW = S == 1 ? 1536 : 34 * kC3PX;                    // bytes per halo row
+template <int S, int RT_> struct C3Geom {
+  static constexpr int RT = RT_, TH = 2 * RT;
+  static constexpr int HH = (TH - 1) * S + 3, HW = (kC3TW - 1) * S + 3;     // RT 4: 10 x 18  /  RT 2: 9 x 33
+  // bytes per halo row: the two image rows of an MFMA row tile lie S rows apart, and S * ROW must be a multiple of the
+  // 256-byte bank cycle for their 16-lane halves to share no bank in a ds_read_b128 lane group (stride 2 with 34
+  // slots = 2720 B had 48 % bank-conflict cycles)
+  static constexpr int ROW = S == 1 ? 1536 : 2816;
   static constexpr int ITEMS = HH * HW * 4, NR = (ITEMS + 255) / 256;       // 16-byte staging items / roles
   __device__ static constexpr int slot(int hx) { return S == 1 ? hx : (hx & 1) * 17 + (hx >> 1); }
 };
@@ -63,15 +72,15 @@ __global__ void conv3x3_pack_weight_kernel(const float* __restrict__ w, unsigned
   packed[idx] = c3_f32_to_bf16(w[((long)co * Cin + ci) * 9 + tap]);
 }
 
-template <int NT, int S, int PF>
-__global__ __launch_bounds__(256, 3) void conv3x3_nhwc_bf16_kernel(
+template <int NT, int S, int PF, int RT_, int MINW>
+__global__ __launch_bounds__(256, MINW) void conv3x3_nhwc_bf16_kernel(
     const uint4* __restrict__ x, const uint4* __restrict__ wp, const float* __restrict__ bias,
     unsigned short* __restrict__ out, int H, int W, int Ho, int Wo, int Cin, int Cout, int tiles_x,
     int tiles_y, int relu, unsigned* __restrict__ amax8) {
-  using G = C3Geom<S>;
+  using G = C3Geom<S, RT_>;
   constexpr int RT = G::RT, BN = 128 * NT, WR = 32 * NT, OLD = BN + 4;
   constexpr int kC3ROW = G::ROW, kC3TH = G::TH;
-  constexpr int HALO_BYTES = G::HH * kC3ROW;                 // 15 360 (stride 1) / 24 480 (stride 2)
+  constexpr int HALO_BYTES = G::HH * kC3ROW;                 // RT 4: 15 360 (stride 1) / RT 2: 25 344 (stride 2)
   constexpr int STAGE_BYTES = 2 * HALO_BYTES, OUT_BYTES = 32 * OLD * 4;   // LDS carries only the halo
   __shared__ __attribute__((aligned(16))) char lds[STAGE_BYTES > OUT_BYTES ? STAGE_BYTES : OUT_BYTES];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -92,14 +101,15 @@ __global__ __launch_bounds__(256, 3) void conv3x3_nhwc_bf16_kernel(
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[rt][t][r] = 0.f;
 
-  // halo staging roles: HH x HW pixels x 4 pieces of 16 B over 256 threads (3 per thread at stride 1, 5 at
-  // stride 2; clamped + zero-masked, unconditional loads)
+  // halo staging roles: HH x HW pixels x 4 pieces of 16 B over 256 threads (RT 4: 3 per thread at stride 1, RT 2: 5 at
+  // stride 2; at most 8; clamped + zero-masked, unconditional loads)
   // (named scalars: small per-thread arrays written in a loop end up in scratch with hipcc / ROCm 7.2)
   constexpr int NR = G::NR;
-  static_assert(NR <= 5, "halo staging register budget");
-  long hofs0, hofs1, hofs2, hofs3 = 0, hofs4 = 0;
-  int hdst0, hdst1, hdst2, hdst3 = 0, hdst4 = 0;
-  bool hin0, hin1, hin2, hin3 = false, hin4 = false, hlive0, hlive1, hlive2, hlive3 = false, hlive4 = false;
+  static_assert(NR >= 2 && NR <= 8, "halo staging register budget");
+  long hofs0, hofs1, hofs2 = 0, hofs3 = 0, hofs4 = 0, hofs5 = 0, hofs6 = 0, hofs7 = 0;
+  int hdst0, hdst1, hdst2 = 0, hdst3 = 0, hdst4 = 0, hdst5 = 0, hdst6 = 0, hdst7 = 0;
+  bool hin0, hin1, hin2 = false, hin3 = false, hin4 = false, hin5 = false, hin6 = false, hin7 = false;
+  bool hlive0, hlive1, hlive2 = false, hlive3 = false, hlive4 = false, hlive5 = false, hlive6 = false, hlive7 = false;
 #define OCC_C3_HALO_ROLE(K, OFS, DST, IN, LIVE)                                                   \
   {                                                                                               \
     const int idx = tid + 256 * (K);                                                              \
@@ -114,9 +124,12 @@ __global__ __launch_bounds__(256, 3) void conv3x3_nhwc_bf16_kernel(
   }
   OCC_C3_HALO_ROLE(0, hofs0, hdst0, hin0, hlive0)
   OCC_C3_HALO_ROLE(1, hofs1, hdst1, hin1, hlive1)
-  OCC_C3_HALO_ROLE(2, hofs2, hdst2, hin2, hlive2)
+  if (NR > 2) OCC_C3_HALO_ROLE(2, hofs2, hdst2, hin2, hlive2)
   if (NR > 3) OCC_C3_HALO_ROLE(3, hofs3, hdst3, hin3, hlive3)
   if (NR > 4) OCC_C3_HALO_ROLE(4, hofs4, hdst4, hin4, hlive4)
+  if (NR > 5) OCC_C3_HALO_ROLE(5, hofs5, hdst5, hin5, hlive5)
+  if (NR > 6) OCC_C3_HALO_ROLE(6, hofs6, hdst6, hin6, hlive6)
+  if (NR > 7) OCC_C3_HALO_ROLE(7, hofs7, hdst7, hin7, hlive7)
 #undef OCC_C3_HALO_ROLE
   // this wave's 32-column tiles in the packed weight: uint4 index of (tile, lane) inside one (chunk, tap, ks)
   const int NT32 = Cout / 32;
@@ -129,15 +142,20 @@ __global__ __launch_bounds__(256, 3) void conv3x3_nhwc_bf16_kernel(
   for (int rt = 0; rt < RT; ++rt)
     abase[rt] = (2 * rt + (vi >> 4)) * S * kC3ROW + (vi & 15) * kC3PX + kb * 16;
 
-  uint4 vh0, vh1, vh2, vh3, vh4;
+  uint4 vh0, vh1, vh2, vh3, vh4, vh5, vh6, vh7;
   const unsigned hm0 = hin0 ? 0xffffffffu : 0u, hm1 = hin1 ? 0xffffffffu : 0u, hm2 = hin2 ? 0xffffffffu : 0u;
-  const unsigned hm3 = hin3 ? 0xffffffffu : 0u, hm4 = hin4 ? 0xffffffffu : 0u;
+  const unsigned hm3 = hin3 ? 0xffffffffu : 0u, hm4 = hin4 ? 0xffffffffu : 0u, hm5 = hin5 ? 0xffffffffu : 0u;
+  const unsigned hm6 = hin6 ? 0xffffffffu : 0u, hm7 = hin7 ? 0xffffffffu : 0u;
 #define OCC_C3_ISSUE_HALO(CH)                                                                     \
   {                                                                                               \
     const long cq = (long)(CH) * 4;                                                               \
-    vh0 = x[hofs0 + cq]; vh1 = x[hofs1 + cq]; vh2 = x[hofs2 + cq];                                \
+    vh0 = x[hofs0 + cq]; vh1 = x[hofs1 + cq];                                                     \
+    if (NR > 2) vh2 = x[hofs2 + cq];                                                              \
     if (NR > 3) vh3 = x[hofs3 + cq];                                                              \
     if (NR > 4) vh4 = x[hofs4 + cq];                                                              \
+    if (NR > 5) vh5 = x[hofs5 + cq];                                                              \
+    if (NR > 6) vh6 = x[hofs6 + cq];                                                              \
+    if (NR > 7) vh7 = x[hofs7 + cq];                                                              \
   }
   // Weights: MFMA-fragment-ordered, global -> registers, a ring of PF k-steps in flight (k-step = (tap, ks),
   // 18 per chunk; the ring runs on across chunk boundaries).  Each wave owns its columns, so there is nothing
@@ -162,9 +180,12 @@ __global__ __launch_bounds__(256, 3) void conv3x3_nhwc_bf16_kernel(
     /* out-of-image pixels are zero (the convolution's padding): AND with an all-ones / all-zeros mask */ \
     if (hlive0) *reinterpret_cast<uint4*>(sH + hdst0) = make_uint4(vh0.x & hm0, vh0.y & hm0, vh0.z & hm0, vh0.w & hm0); \
     if (hlive1) *reinterpret_cast<uint4*>(sH + hdst1) = make_uint4(vh1.x & hm1, vh1.y & hm1, vh1.z & hm1, vh1.w & hm1); \
-    if (hlive2) *reinterpret_cast<uint4*>(sH + hdst2) = make_uint4(vh2.x & hm2, vh2.y & hm2, vh2.z & hm2, vh2.w & hm2); \
+    if (NR > 2 && hlive2) *reinterpret_cast<uint4*>(sH + hdst2) = make_uint4(vh2.x & hm2, vh2.y & hm2, vh2.z & hm2, vh2.w & hm2); \
     if (NR > 3 && hlive3) *reinterpret_cast<uint4*>(sH + hdst3) = make_uint4(vh3.x & hm3, vh3.y & hm3, vh3.z & hm3, vh3.w & hm3); \
     if (NR > 4 && hlive4) *reinterpret_cast<uint4*>(sH + hdst4) = make_uint4(vh4.x & hm4, vh4.y & hm4, vh4.z & hm4, vh4.w & hm4); \
+    if (NR > 5 && hlive5) *reinterpret_cast<uint4*>(sH + hdst5) = make_uint4(vh5.x & hm5, vh5.y & hm5, vh5.z & hm5, vh5.w & hm5); \
+    if (NR > 6 && hlive6) *reinterpret_cast<uint4*>(sH + hdst6) = make_uint4(vh6.x & hm6, vh6.y & hm6, vh6.z & hm6, vh6.w & hm6); \
+    if (NR > 7 && hlive7) *reinterpret_cast<uint4*>(sH + hdst7) = make_uint4(vh7.x & hm7, vh7.y & hm7, vh7.z & hm7, vh7.w & hm7); \
     __syncthreads();   /* halo chunk visible; the other halo buffer is free for the next chunk */ \
     OCC_C3_ISSUE_HALO(OCC_C3_CH((CI) + 1))                                                        \
     const int ch_cur = OCC_C3_CH(CI), ch_nxt = OCC_C3_CH((CI) + 1);                               \
@@ -267,9 +288,45 @@ extern "C" int occ_conv3x3_pack_weight_bf16(const float* weight, void* packed, i
   return OCC_OK;
 }
 
+namespace occ {
+// The tiles: variant = 10 * NT + RT (NT x 128 output channels, 4 waves x 32 * NT, 2 * RT x 16 output pixels per block)
+// and the waves per SIMD each is compiled for (launch_bounds: what its registers, or at stride 2 its LDS, allow).
+struct C3Variant { int stride, id, minw; };
+constexpr C3Variant kC3Variants[] = {{1, 12, 3}, {1, 13, 3}, {1, 14, 3}, {1, 16, 2}, {1, 18, 2}, {1, 22, 2}, {1, 23, 2},
+                                     {1, 24, 2}, {2, 12, 3}, {2, 13, 2}, {2, 22, 2}};
+constexpr int c3_minw(int s, int id) {
+  for (const C3Variant& v : kC3Variants)
+    if (v.stride == s && v.id == id) return v.minw;
+  return 0;
+}
+
+// Default variant for a shape: the candidate with the least
+//   cost = rounds * W * RT * (NT + 1),   rounds = ceil(blocks / (256 CUs * W)),   W = waves per SIMD of the variant.
+// A block keeps its slot for time proportional to what each of its waves issues per k-step, in units of one MFMA:
+// NT * RT MFMAs plus RT A-fragment reads out of the staged halo (the halo is staged once per block, so a 256-channel
+// block pays it once for twice the MFMAs), times the W waves that share the SIMD.  The grid runs in `rounds` passes
+// over the 256 CUs, so row padding (ceil(Ho / 2RT) tiles) and a partly filled last pass both count.  Ties go to the
+// earlier (smaller) tile.  The two constants (weights 1 and 1) fit the per-shape sweep of every variant over the
+// backbone's shapes (tools_dev/conv_probe.py c3v) without making any shape slower than the 8 x 16 tile it replaced.
+int c3_pick(long batch, int Ho, int Wo, int Cout, int stride) {
+  const long tiles_x = (Wo + kC3TW - 1) / kC3TW;
+  int best = 12;
+  long best_cost = -1;
+  for (const C3Variant& v : kC3Variants) {
+    const int nt = v.id / 10, rt = v.id % 10;
+    if (v.stride != stride || Cout % (128 * nt)) continue;
+    const long blocks = batch * tiles_x * ((Ho + 2 * rt - 1) / (2 * rt)) * (Cout / (128 * nt));
+    const long rounds = (blocks + 256L * v.minw - 1) / (256L * v.minw);
+    const long cost = rounds * v.minw * rt * (nt + 1);
+    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = v.id; }
+  }
+  return best;
+}
+}  // namespace occ
+
 static int conv3x3_nhwc_bf16_launch(const void* x, const void* weight_packed, const float* bias, void* out,
                                     int batch, int H, int W, int Cin, int Cout, int stride, int relu,
-                                    uint32_t* amax8, void* stream) {
+                                    uint32_t* amax8, int variant, void* stream) {
   using namespace occ;
   OCC_CHECK_ARG(x && weight_packed && bias && out, "conv3x3_nhwc_bf16: null pointer argument");
   OCC_CHECK_ARG(batch > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0, "conv3x3_nhwc_bf16: bad dimension");
@@ -279,16 +336,32 @@ static int conv3x3_nhwc_bf16_launch(const void* x, const void* weight_packed, co
     return OCC_E_UNSUPPORTED;
   }
   const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;     // floor((H + 2 - 3) / stride) + 1
-  const int TH = stride == 1 ? C3Geom<1>::TH : C3Geom<2>::TH;
-  const int tiles_x = (Wo + kC3TW - 1) / kC3TW, tiles_y = (Ho + TH - 1) / TH;
+  const int id = variant == 0 ? c3_pick(batch, Ho, Wo, Cout, stride) : variant;
+  const int nt = id / 10, rt = id % 10;
+  if (c3_minw(stride, id) == 0 || Cout % (128 * nt)) {
+    set_error("conv3x3_nhwc_bf16: no variant %d at stride %d, Cout %d (stride 1: 12, 13, 14, 16, 18, 22, 23, 24; "
+              "stride 2: 12, 13, 22; 2x: Cout %% 256 == 0)", variant, stride, Cout);
+    return OCC_E_UNSUPPORTED;
+  }
+  const int tiles_x = (Wo + kC3TW - 1) / kC3TW, tiles_y = (Ho + 2 * rt - 1) / (2 * rt);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const unsigned gx = (unsigned)((long)batch * tiles_x * tiles_y);
-#define OCC_C3_LAUNCH(NTT, BNN, SS, PFF)                                                            \
-  hipLaunchKernelGGL((conv3x3_nhwc_bf16_kernel<NTT, SS, PFF>), dim3(gx, (unsigned)(Cout / BNN)), dim3(256), 0, st, \
-                     reinterpret_cast<const uint4*>(x), reinterpret_cast<const uint4*>(weight_packed), \
-                     bias, reinterpret_cast<unsigned short*>(out), H, W, Ho, Wo, Cin, Cout, tiles_x, tiles_y, relu, amax8)
-  // ring of 6 k-steps + 3 waves per SIMD measured faster than 12 k-steps + 2 waves on every ResNet-50 shape
-  if (stride == 2) OCC_C3_LAUNCH(1, 128, 2, 6); else OCC_C3_LAUNCH(1, 128, 1, 6);
+#define OCC_C3_LAUNCH(SS, ID)                                                                       \
+  case ID:                                                                                          \
+    hipLaunchKernelGGL((conv3x3_nhwc_bf16_kernel<ID / 10, SS, 6, ID % 10, c3_minw(SS, ID)>),       \
+                       dim3(gx, (unsigned)(Cout / (128 * (ID / 10)))), dim3(256), 0, st,            \
+                       reinterpret_cast<const uint4*>(x), reinterpret_cast<const uint4*>(weight_packed), bias, \
+                       reinterpret_cast<unsigned short*>(out), H, W, Ho, Wo, Cin, Cout, tiles_x, tiles_y, relu, amax8); \
+    break;
+  // ring of 6 k-steps + 3 waves per SIMD measured faster than 12 k-steps + 2 waves on every ResNet-50 shape (RT 4)
+  if (stride == 2) {
+    switch (id) { OCC_C3_LAUNCH(2, 12) OCC_C3_LAUNCH(2, 13) default: OCC_C3_LAUNCH(2, 22) }
+  } else {
+    switch (id) {
+      OCC_C3_LAUNCH(1, 12) OCC_C3_LAUNCH(1, 13) OCC_C3_LAUNCH(1, 14) OCC_C3_LAUNCH(1, 16) OCC_C3_LAUNCH(1, 18)
+      OCC_C3_LAUNCH(1, 22) OCC_C3_LAUNCH(1, 23) default: OCC_C3_LAUNCH(1, 24)
+    }
+  }
 #undef OCC_C3_LAUNCH
   OCC_CHECK_LAUNCH("conv3x3_nhwc_bf16");
   return OCC_OK;
@@ -297,7 +370,7 @@ static int conv3x3_nhwc_bf16_launch(const void* x, const void* weight_packed, co
 extern "C" int occ_conv3x3_nhwc_bf16(const void* x, const void* weight_packed, const float* bias, void* out,
                                      int batch, int H, int W, int Cin, int Cout, int stride, int relu,
                                      void* stream) {
-  return conv3x3_nhwc_bf16_launch(x, weight_packed, bias, out, batch, H, W, Cin, Cout, stride, relu, nullptr, stream);
+  return conv3x3_nhwc_bf16_launch(x, weight_packed, bias, out, batch, H, W, Cin, Cout, stride, relu, nullptr, 0, stream);
 }
 
 // The same convolution; additionally folds max|out| (sign-stripped bf16 patterns of every element it stores) into amax8[0..8)
@@ -307,5 +380,15 @@ extern "C" int occ_conv3x3_nhwc_bf16_amax(const void* x, const void* weight_pack
                                           int batch, int H, int W, int Cin, int Cout, int stride, int relu,
                                           uint32_t* amax8, void* stream) {
   OCC_CHECK_ARG(amax8, "conv3x3_nhwc_bf16_amax: null amax8");
-  return conv3x3_nhwc_bf16_launch(x, weight_packed, bias, out, batch, H, W, Cin, Cout, stride, relu, amax8, stream);
+  return conv3x3_nhwc_bf16_launch(x, weight_packed, bias, out, batch, H, W, Cin, Cout, stride, relu, amax8, 0, stream);
+}
+
+// Either of the above with the tile forced: variant = row tiles per wave (stride 1: 2, 3, 4, 6, 8; stride 2: 2, 3) or 0
+// for the launcher's own choice; amax8 may be null.  Variants differ only in f32 summation order (the chunk rotation
+// follows the block index); each one is deterministic.
+extern "C" int occ_conv3x3_nhwc_bf16_variant(const void* x, const void* weight_packed, const float* bias, void* out,
+                                             int batch, int H, int W, int Cin, int Cout, int stride, int relu,
+                                             uint32_t* amax8, int variant, void* stream) {
+  return conv3x3_nhwc_bf16_launch(x, weight_packed, bias, out, batch, H, W, Cin, Cout, stride, relu, amax8, variant,
+                                  stream);
 }

@@ -1690,12 +1690,15 @@ def conv3x3_pack_weight(weight):
     return packed
 
 
-def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None):
+def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None, variant=None):
     """3x3 / pad 1 / stride 1 or 2 convolution + bias (+ ReLU) on a channels_last bf16 activation, one launch.
     x (N, Cin, H, W) channels_last bf16; w_packed from conv3x3_pack_weight; bias (Cout) f32
     -> (N, Cout, (H-1)//stride+1, (W-1)//stride+1) channels_last bf16.
     amax: 8 int32 device words (new_absmax_words) the launch folds max|out| into (atomic maxima of the sign-stripped bf16
-    patterns; they accumulate over launches) — the input of value_range_scale_from_amax."""
+    patterns; they accumulate over launches) — the input of value_range_scale_from_amax.
+    variant: None = the launcher's choice; an int forces the tile (occ_conv3x3_nhwc_bf16_variant: 10 * NT + RT for
+    (2 * RT) x 16 pixels x (128 * NT) channels per block; stride 1: 12, 13, 14, 16, 18, 22, 23, 24; stride 2: 12, 13,
+    22; 0 = the launcher's choice through the same entry point)."""
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)):
         raise OccAmdUnsupported("conv3x3_nhwc: x must be a channels_last bfloat16 device tensor")
@@ -1711,7 +1714,12 @@ def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None):
     out = torch.empty((N, cout, (H - 1) // st + 1, (W - 1) // st + 1), dtype=torch.bfloat16, device=x.device,
                       memory_format=torch.channels_last)
     with torch.cuda.device(x.device), _timed('bb_conv3x3'):
-        if amax is None:
+        if variant is not None:
+            rc = _lib.lib().occ_conv3x3_nhwc_bf16_variant(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
+                                                          i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
+                                                          ptr(amax), i32(variant),
+                                                          stream_ptr(x.device))
+        elif amax is None:
             rc = _lib.lib().occ_conv3x3_nhwc_bf16(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
                                                   i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
                                                   stream_ptr(x.device))

@@ -23,15 +23,31 @@ def main(which):
     mk = lambda *s: (torch.randn(*s, generator=g) * 0.05).cuda()
     act = lambda c, h, w: torch.randn(N, c, h, w, generator=g).cuda().to(torch.bfloat16).contiguous(
         memory_format=torch.channels_last)
-    if 'c3' in which:
+    if 'c3' in which or 'c3v' in which:
+        # c3v: every forced tile (occ_conv3x3_nhwc_bf16_variant) next to the launcher's choice, interleaved over 5 rounds
+        # (median): a variant timed first or last on a shape must not win by clock drift
+        def variants(s, cout):
+            if 'c3v' not in which:
+                return (None,)
+            vs = (12, 13, 14, 16, 18, 22, 23, 24) if s == 1 else (12, 13, 22)
+            return (None,) + tuple(v for v in vs if cout % (128 * (v // 10)) == 0)
         for (cin, cout, h, w, s) in [(128, 128, 232, 400, 2), (128, 128, 116, 200, 1), (256, 256, 116, 200, 2),
                                      (256, 256, 58, 100, 1), (512, 512, 58, 100, 2), (512, 512, 29, 50, 1),
-                                     (256, 256, 116, 200, 1), (256, 256, 29, 50, 2)]:
+                                     (256, 256, 116, 200, 1), (256, 256, 29, 50, 1),
+                                     (256, 256, 29, 50, 2)]:
             x, wp, b = act(cin, h, w), ext.conv3x3_pack_weight(mk(cout, cin, 3, 3)), mk(cout)
-            us = timeit(lambda: ext.conv3x3_nhwc(x, wp, b, cout, relu=True, stride=s))
-            ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
-            fl = 2.0 * N * ho * wo * cout * cin * 9
-            print(f"conv3x3 {cin:4d}->{cout:4d} {h:3d}x{w:3d} s{s}: {us:7.1f} us  {fl / us * 1e-6:6.1f} TF/s")
+            vs = variants(s, cout)
+            rounds = 5 if len(vs) > 1 else 1
+            times = {v: [] for v in vs}
+            for _ in range(rounds):
+                for v in vs:
+                    times[v].append(timeit(lambda: ext.conv3x3_nhwc(x, wp, b, cout, relu=True, stride=s, variant=v)))
+            for v in vs:
+                us = sorted(times[v])[rounds // 2]
+                ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+                fl = 2.0 * N * ho * wo * cout * cin * 9
+                tag = 'auto' if v is None else f'v{v}'
+                print(f"conv3x3 {cin:4d}->{cout:4d} {h:3d}x{w:3d} s{s} {tag:4s}: {us:7.1f} us  {fl / us * 1e-6:6.1f} TF/s")
     if 'c1' in which:
         for (cin, cout, h, w, s, res) in [(256, 128, 232, 400, 1, 0), (128, 512, 116, 200, 1, 1),
                                           (512, 128, 116, 200, 1, 0), (256, 512, 232, 400, 2, 0),
