@@ -17,6 +17,8 @@
  *   occ_sca_fused_forward_f32        <- SpatialCrossAttention.forward :136-173 (rebatch, scatter-add,
  *        visible-camera mean) fused with MSDeformableAttention3D.forward :338-396 (softmax,
  *        offset normalisation, z-anchor add, deformable gather), P/bevformer/modules/spatial_cross_attention.py
+ *   occ_sca_fused_backward_f32       <- the autograd backward of that same block (ms_deform_attn_backward on the
+ *        padded rebatch + the softmax / normalisation / rebatch / camera-mean gradients) for fp32 value rows
  *   occ_tsa_fused_forward_f32        <- TemporalSelfAttention.forward :206-262 (softmax, locations,
  *        gather, mean over the 2-deep BEV queue), P/bevformer/modules/temporal_self_attention.py
  *   occ_conv3d_pack_weight_f32, occ_conv3d_bn_relu_f32 <- TransformerOcc.forward lifter view +
@@ -195,6 +197,24 @@ int occ_sca_fused_forward_q16v(const void* value_q16, const int64_t* spatial_sha
                                const uint32_t* vis_bits, const int32_t* order, float* slots, uint64_t* stats,
                                int B, int NC, int S, int M, int D, int L, int P, int Z, int Nq,
                                const float* value_scale, void* stream);
+/* Backward of occ_sca_fused_forward_f32 (fp32 value rows; same geometry and arguments).  grad_slots (B, Nq, M*D) f32 is the
+ * gradient of `slots`.  Outputs:
+ *   grad_value  (B*NC, S, M, D) f32, ACCUMULATED into (the caller zeroes it), like occ_ms_deform_attn_backward_f32's;
+ *   grad_offs   (B, Nq, M*L*P*2) f32, row stride grad_offs_stride floats, every element overwritten;
+ *   grad_logits (B, Nq, M*L*P)   f32, row stride grad_logits_stride floats, every element overwritten.
+ * grad_offs / grad_logits have one writer per element and a fixed summation order: bit-identical run to run.  grad_value runs
+ * through the binned, atomic-free path of the msda backward with the items of the visible (query, camera) rows only; with
+ * OCC_MSDA_BWD_DETERMINISTIC=1 (read per call) it is bit-identical run to run as well.  `workspace`: CALLER-OWNED scratch of at
+ * least occ_sca_fused_backward_workspace_bytes(...) bytes, 256-byte aligned, uninitialised.  Kernels exist for M=8, D=32,
+ * (L,P) in {(4,8),(4,4),(2,8),(1,8)}, Z | P; other shapes (and ..._workspace_bytes() == 0) return OCC_E_UNSUPPORTED. */
+int64_t occ_sca_fused_backward_workspace_bytes(int B, int NC, int S, int M, int D, int L, int P, int Nq);
+int occ_sca_fused_backward_f32(const float* value, const int64_t* spatial_shapes,
+                               const int64_t* level_start_index, const float* offs, int64_t offs_stride,
+                               const float* logits, int64_t logits_stride, const float* ref_cam,
+                               const uint32_t* vis_bits, const float* grad_slots, float* grad_value,
+                               float* grad_offs, int64_t grad_offs_stride, float* grad_logits,
+                               int64_t grad_logits_stride, int B, int NC, int S, int M, int D, int L, int P,
+                               int Z, int Nq, void* workspace, int64_t workspace_bytes, void* stream);
 /* fp32 value rows -> q16 pixel pairs.  v (groups, S, C) f32 contiguous, C % 32 == 0; out (groups, S + (S & 1), C) int16 in
  * the pair order (the pad row of an odd S is not written); scale: NULL or one DEVICE float s, a power of two with
  * max|v| * s <= 2^15. */

@@ -38,6 +38,7 @@
 #include <cstdlib>
 #include <string>
 #include "common.h"
+#include "msda_bwd_bins.h"
 
 namespace occ {
 
@@ -297,11 +298,12 @@ __global__ __launch_bounds__(256) void msda_bwd_bin_kernel(
 // launch instead of ~3 700).
 constexpr int kBinBlockThreads = 1024;
 
-template <bool FILL>
+// SCA: the fused SCA backward's items (msda_bwd_bins.h ScaBinSource; b is then the value batch entry b' * NC + c)
+template <bool FILL, bool SCA = false>
 __global__ __launch_bounds__(kBinBlockThreads) void msda_bwd_bin_block_kernel(
     const int64_t* __restrict__ shapes, const float* __restrict__ loc, const float* __restrict__ attn,
     const unsigned char* __restrict__ nzflag, int* __restrict__ counter, BwdItem* __restrict__ items, int M,
-    int L, int Lq, int P, int bins_per_bm, int blocks_per_bml) {
+    int L, int Lq, int P, int bins_per_bm, int blocks_per_bml, ScaBinSource sca) {
   extern __shared__ int bin_lds[];                    // [nb] block histogram, then (FILL) [nb] global bases
   const int tid = threadIdx.x;
   const int chunk = (int)(blockIdx.x % (unsigned)blocks_per_bml);
@@ -325,12 +327,28 @@ __global__ __launch_bounds__(kBinBlockThreads) void msda_bwd_bin_block_kernel(
   const bool in_grid = qp_raw < qp_n;
   const long qp = in_grid ? qp_raw : qp_n - 1;
   const int q = (int)(qp / P), p = (int)(qp - (long)q * P);
-  const long item = (b * Lq + q) * M + m;             // (b, q, m)
-  const long si = (item * L + l) * P + p;
-  const unsigned char fl = nzflag[item];
-  const float2 xy = *reinterpret_cast<const float2*>(loc + si * 2);
-  const float a = attn[si];
-  const BilinearTerms t = bilinear_terms(xy.x, xy.y, H, W, lane_flag(in_grid) & lane_flag(fl != 0));
+  float2 xy;
+  float a;
+  int live;
+  if constexpr (SCA) {
+    // the location as the fused forward computes it (anchor + normalised offset), the weight softmax / camera count
+    const int c = (int)(b % sca.NC);
+    const long bq = b / sca.NC;
+    const long pi = (((bq * Lq + q) * M + m) * L + l) * P + p;
+    const float2 r = *reinterpret_cast<const float2*>(sca.ref_cam + ((((long)c * sca.B + bq) * Lq + q) * sca.Z + p % sca.Z) * 2);
+    const float2 o = *reinterpret_cast<const float2*>(sca.oxy + pi * 2);
+    xy = make_float2(r.x + o.x, r.y + o.y);
+    a = sca.aw[pi];
+    live = lane_flag(in_grid) & lane_flag(((sca.vis_bits[q] >> c) & 1u) != 0u);
+  } else {
+    const long item = (b * Lq + q) * M + m;           // (b, q, m)
+    const long si = (item * L + l) * P + p;
+    const unsigned char fl = nzflag[item];
+    xy = *reinterpret_cast<const float2*>(loc + si * 2);
+    a = attn[si];
+    live = lane_flag(in_grid) & lane_flag(fl != 0);
+  }
+  const BilinearTerms t = bilinear_terms(xy.x, xy.y, H, W, live);
   const int ok = t.adm;
   const int h_low = t.h_low, w_low = t.w_low;
   const float lh = t.lh, lw = t.lw, hh = t.hh, hw = t.hw;
@@ -466,7 +484,7 @@ __global__ __launch_bounds__(1024) void msda_bwd_scan_kernel(int* __restrict__ c
 __global__ __launch_bounds__(256) void msda_bwd_replay_kernel(
     const int64_t* __restrict__ shapes, const int64_t* __restrict__ lstart, const int4* __restrict__ work,
     const int* __restrict__ work_count, const BwdItem* __restrict__ items, const float* __restrict__ grad_out,
-    float* __restrict__ grad_value, int S, int M, int L, int Lq, int bins_per_bm) {
+    float* __restrict__ grad_value, int S, int M, int L, int Lq, int bins_per_bm, int bdiv) {
   constexpr int D = 32;
   __shared__ float acc_s[8][(kBinPix + 1) * D];        // per half-wave; +1 pixel: the w1 lane of pixel 31
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, ch = lane & 31;
@@ -491,7 +509,7 @@ __global__ __launch_bounds__(256) void msda_bwd_replay_kernel(
     bl -= nb;
   }
   if (l >= L) return;                                  // slack bins of the upper bound (never filled)
-  const float* go = grad_out + (b * Lq * (long)M + m) * D + ch;        // + q * M * D
+  const float* go = grad_out + ((b / bdiv) * Lq * (long)M + m) * D + ch;        // + q * M * D (bdiv: msda_bwd_bins.h)
   // 8 items per half-wave per step, software-pipelined over three steps: the item records of step i+2 and the
   // output-gradient rows of step i+1 are in flight while step i is added into LDS (two dependent global loads per
   // item made every step cost both latencies: ~1.5 us per 64 items and block)
@@ -599,7 +617,7 @@ __global__ __launch_bounds__(256) void msda_bwd_det_zero_kernel(const int* __res
 __global__ __launch_bounds__(256) void msda_bwd_replay_det_kernel(
     const int64_t* __restrict__ shapes, const int64_t* __restrict__ lstart, const int4* __restrict__ work,
     const int* __restrict__ work_count, const BwdItem* __restrict__ items, const float* __restrict__ grad_out,
-    float* __restrict__ grad_value, int S, int M, int L, int Lq, int bins_per_bm, int* __restrict__ split_meta,
+    float* __restrict__ grad_value, int S, int M, int L, int Lq, int bins_per_bm, int bdiv, int* __restrict__ split_meta,
     unsigned long long* __restrict__ tiles) {
   constexpr int D = 32;
   __shared__ unsigned long long acc_d[(kBinPix + 1) * D];
@@ -634,7 +652,7 @@ __global__ __launch_bounds__(256) void msda_bwd_replay_det_kernel(
   if (mx > 0.f) (void)frexpf(mx, &e);                                  // mx < 2^e
   const int sh = 40 - e;                                               // products scaled by 2^sh: |.| < 2^40, exact in fp32
   const double inv = ldexp(1.0, e - 40);
-  const float* go = grad_out + (b * Lq * (long)M + m) * D + ch;        // + q * M * D
+  const float* go = grad_out + ((b / bdiv) * Lq * (long)M + m) * D + ch;        // + q * M * D (bdiv: msda_bwd_bins.h)
   int qA[8], qB[8], qC[8];
   float w0A[8], w1A[8], w0B[8], w1B[8], w0C[8], w1C[8], gA[8], gB[8];
 #pragma unroll
@@ -779,8 +797,7 @@ __global__ __launch_bounds__(256) void msda_bwd_generic_kernel(
 }  // namespace occ
 
 namespace occ {
-struct BwdWsLayout { size_t off_cnt, off_cur, off_work, off_items, off_meta, off_tiles, off_aux, bytes; long n_bins, n_samples, max_items, work_cap, max_split; int bins_per_bm; bool ok; };
-static BwdWsLayout bwd_ws_layout(int B, int S, int M, int L, int Lq, int P) {
+BwdWsLayout bwd_ws_layout(int B, int S, int M, int L, int Lq, int P) {
   BwdWsLayout w;
   const long n_items = (long)B * Lq * M;
   w.bins_per_bm = S / kBinPix + L + 1;                                // >= sum_l ceil(H_l*W_l / 32)
@@ -801,6 +818,92 @@ static BwdWsLayout bwd_ws_layout(int B, int S, int M, int L, int Lq, int P) {
   w.bytes = w.off_aux + 3 * 1024 * sizeof(int);
   w.ok = w.n_bins <= 1024L * 1024 && Lq < (1 << 26) && w.n_bins < (1L << 30) && w.max_items < (1L << 31) && w.work_cap < (1L << 31);
   return w;
+}
+
+bool bwd_block_bins_fit(int B, int S, int M, int L, int Lq, int P) {
+  const long blocks_per_bml = ((long)Lq * P + kBinBlockThreads - 1) / kBinBlockThreads;
+  const size_t lds_b = (size_t)(S / kBinPix + 2) * 2 * sizeof(int);
+  return lds_b <= 48 * 1024 && (long)B * M * L * blocks_per_bml < (1L << 31);
+}
+
+int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const int64_t* spatial_shapes,
+                    const int64_t* level_start_index, const float* sampling_loc, const float* attn_weight,
+                    const ScaBinSource* sca, const float* grad_output, long grad_out_n, float* grad_value, int B, int S,
+                    int M, int L, int Lq, int P, hipStream_t st) {
+  unsigned char* flags = reinterpret_cast<unsigned char*>(ws);
+  int* counts = reinterpret_cast<int*>(ws + w.off_cnt);
+  int* cursor = reinterpret_cast<int*>(ws + w.off_cur);
+  BwdItem* items = reinterpret_cast<BwdItem*>(ws + w.off_items);
+  int* work_count = reinterpret_cast<int*>(ws + w.off_work);
+  int4* work = reinterpret_cast<int4*>(ws + w.off_work + 16);
+  const ScaBinSource src = sca != nullptr ? *sca : ScaBinSource{nullptr, nullptr, nullptr, nullptr, 1, 1, 1};
+  const int bdiv = src.NC;
+  const dim3 grid_s((unsigned)((w.n_samples + 255) / 256));
+  // binning passes: block-aggregated (default) or the wave-aggregated kernels (OCC_MSDA_BWD_BIN=wave, or a
+  // level with more bins than the LDS histogram holds); the SCA items exist in the block-aggregated form only (the
+  // caller checked bwd_block_bins_fit)
+  static const bool wave_bins = getenv("OCC_MSDA_BWD_BIN") != nullptr &&
+                                std::string(getenv("OCC_MSDA_BWD_BIN")) == "wave";
+  const long qp_n = (long)Lq * P;
+  const long blocks_per_bml = (qp_n + kBinBlockThreads - 1) / kBinBlockThreads;
+  const long grid_b = (long)B * M * L * blocks_per_bml;
+  const size_t lds_b = (size_t)(S / kBinPix + 2) * 2 * sizeof(int);        // >= 2 * bins of the largest level
+  const bool block_bins = sca != nullptr || (!wave_bins && lds_b <= 48 * 1024 && grid_b < (1L << 31));
+  if (block_bins) {
+    if (sca != nullptr)
+      hipLaunchKernelGGL((msda_bwd_bin_block_kernel<false, true>), dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
+                         st, spatial_shapes, sampling_loc, attn_weight, flags, counts, items, M, L, Lq, P,
+                         w.bins_per_bm, (int)blocks_per_bml, src);
+    else
+      hipLaunchKernelGGL(msda_bwd_bin_block_kernel<false>, dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
+                         st, spatial_shapes, sampling_loc, attn_weight, flags, counts, items, M, L, Lq, P,
+                         w.bins_per_bm, (int)blocks_per_bml, src);
+  } else {
+    hipLaunchKernelGGL(msda_bwd_bin_kernel<false>, grid_s, dim3(256), 0, st, spatial_shapes, sampling_loc,
+                       attn_weight, flags, counts, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
+  }
+  int* split_meta = reinterpret_cast<int*>(ws + w.off_meta);
+  unsigned long long* tiles = reinterpret_cast<unsigned long long*>(ws + w.off_tiles);
+  const int scan_blocks = (int)((w.n_bins + 1023) / 1024);
+  int* scan_aux = reinterpret_cast<int*>(ws + w.off_aux);
+  hipLaunchKernelGGL(msda_bwd_scan_totals_kernel, dim3((unsigned)scan_blocks), dim3(1024), 0, st, counts, (int)w.n_bins,
+                     kReplayCap, scan_aux);
+  hipLaunchKernelGGL(msda_bwd_scan_offsets_kernel, dim3(1), dim3(1024), 0, st, scan_aux, scan_blocks, counts, (int)w.n_bins,
+                     work_count);
+  hipLaunchKernelGGL(msda_bwd_scan_kernel, dim3((unsigned)scan_blocks), dim3(1024), 0, st, counts, cursor, (int)w.n_bins, work,
+                     scan_aux, kReplayCap, deterministic ? split_meta : nullptr);
+  if (block_bins) {
+    if (sca != nullptr)
+      hipLaunchKernelGGL((msda_bwd_bin_block_kernel<true, true>), dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
+                         st, spatial_shapes, sampling_loc, attn_weight, flags, cursor, items, M, L, Lq, P,
+                         w.bins_per_bm, (int)blocks_per_bml, src);
+    else
+      hipLaunchKernelGGL(msda_bwd_bin_block_kernel<true>, dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
+                         st, spatial_shapes, sampling_loc, attn_weight, flags, cursor, items, M, L, Lq, P,
+                         w.bins_per_bm, (int)blocks_per_bml, src);
+  } else {
+    hipLaunchKernelGGL(msda_bwd_bin_kernel<true>, grid_s, dim3(256), 0, st, spatial_shapes, sampling_loc,
+                       attn_weight, flags, cursor, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
+  }
+  if (deterministic) {
+    const hipError_t ed = hipMemsetAsync(work_count + 1, 0, sizeof(int), st);
+    if (ed != hipSuccess) {
+      set_error("ms_deform_attn_backward: deterministic mode set-up failed: %s", hipGetErrorString(ed));
+      return OCC_E_LAUNCH;
+    }
+    hipLaunchKernelGGL(msda_bwd_maxabs_kernel, dim3(1024), dim3(256), 0, st, grad_output, grad_out_n,
+                       reinterpret_cast<unsigned*>(work_count + 1));
+    hipLaunchKernelGGL(msda_bwd_det_zero_kernel, dim3((unsigned)w.max_split), dim3(256), 0, st, work_count, split_meta,
+                       tiles);
+    hipLaunchKernelGGL(msda_bwd_replay_det_kernel, dim3((unsigned)w.work_cap), dim3(256), 0, st,
+                       spatial_shapes, level_start_index, work, work_count, items, grad_output, grad_value, S, M,
+                       L, Lq, w.bins_per_bm, bdiv, split_meta, tiles);
+  } else {
+    hipLaunchKernelGGL(msda_bwd_replay_kernel, dim3((unsigned)w.work_cap), dim3(256), 0, st,
+                       spatial_shapes, level_start_index, work, work_count, items, grad_output, grad_value, S, M,
+                       L, Lq, w.bins_per_bm, bdiv);
+  }
+  return OCC_OK;
 }
 }  // namespace occ
 
@@ -865,68 +968,14 @@ extern "C" int occ_ms_deform_attn_backward_ws_f32(
     if (e == hipSuccess) e = hipMemsetAsync(ws, 0, w.off_cur, st);      // flags + counts
     if (e == hipSuccess) {
       unsigned char* flags = reinterpret_cast<unsigned char*>(ws);
-      int* counts = reinterpret_cast<int*>(ws + w.off_cnt);
-      int* cursor = reinterpret_cast<int*>(ws + w.off_cur);
-      BwdItem* items = reinterpret_cast<BwdItem*>(ws + w.off_items);
-      int* work_count = reinterpret_cast<int*>(ws + w.off_work);
-      int4* work = reinterpret_cast<int4*>(ws + w.off_work + 16);
-      const dim3 grid_s((unsigned)((w.n_samples + 255) / 256));
       hipLaunchKernelGGL(msda_bwd_d32_kernel<false>, grid1, dim3(256), 0, st, value, spatial_shapes,
                          level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
                          grad_sampling_loc, grad_attn_weight, flags, S, M, L, Lq, P, n_items);
-      // binning passes: block-aggregated (default) or the wave-aggregated kernels (OCC_MSDA_BWD_BIN=wave, or a
-      // level with more bins than the LDS histogram holds)
-      static const bool wave_bins = getenv("OCC_MSDA_BWD_BIN") != nullptr &&
-                                    std::string(getenv("OCC_MSDA_BWD_BIN")) == "wave";
-      const long qp_n = (long)Lq * P;
-      const long blocks_per_bml = (qp_n + kBinBlockThreads - 1) / kBinBlockThreads;
-      const long grid_b = (long)B * M * L * blocks_per_bml;
-      const size_t lds_b = (size_t)(S / kBinPix + 2) * 2 * sizeof(int);        // >= 2 * bins of the largest level
-      const bool block_bins = !wave_bins && lds_b <= 48 * 1024 && grid_b < (1L << 31);
-      if (block_bins) {
-        hipLaunchKernelGGL(msda_bwd_bin_block_kernel<false>, dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
-                           st, spatial_shapes, sampling_loc, attn_weight, flags, counts, items, M, L, Lq, P,
-                           w.bins_per_bm, (int)blocks_per_bml);
-      } else {
-        hipLaunchKernelGGL(msda_bwd_bin_kernel<false>, grid_s, dim3(256), 0, st, spatial_shapes, sampling_loc,
-                           attn_weight, flags, counts, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
-      }
-      int* split_meta = reinterpret_cast<int*>(ws + w.off_meta);
-      unsigned long long* tiles = reinterpret_cast<unsigned long long*>(ws + w.off_tiles);
-const int scan_blocks = (int)((w.n_bins + 1023) / 1024);
-      int* scan_aux = reinterpret_cast<int*>(ws + w.off_aux);
-      hipLaunchKernelGGL(msda_bwd_scan_totals_kernel, dim3((unsigned)scan_blocks), dim3(1024), 0, st, counts, (int)w.n_bins,
-                         kReplayCap, scan_aux);
-      hipLaunchKernelGGL(msda_bwd_scan_offsets_kernel, dim3(1), dim3(1024), 0, st, scan_aux, scan_blocks, counts, (int)w.n_bins,
-                         work_count);
-      hipLaunchKernelGGL(msda_bwd_scan_kernel, dim3((unsigned)scan_blocks), dim3(1024), 0, st, counts, cursor, (int)w.n_bins, work,
-                         scan_aux, kReplayCap, deterministic ? split_meta : nullptr);
-      if (block_bins) {
-        hipLaunchKernelGGL(msda_bwd_bin_block_kernel<true>, dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
-                           st, spatial_shapes, sampling_loc, attn_weight, flags, cursor, items, M, L, Lq, P,
-                           w.bins_per_bm, (int)blocks_per_bml);
-      } else {
-        hipLaunchKernelGGL(msda_bwd_bin_kernel<true>, grid_s, dim3(256), 0, st, spatial_shapes, sampling_loc,
-                           attn_weight, flags, cursor, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
-      }
-      if (deterministic) {
-        const hipError_t ed = hipMemsetAsync(work_count + 1, 0, sizeof(int), st);
-        if (ed != hipSuccess) {
-          if (own) (void)hipFreeAsync(ws, st);
-          set_error("ms_deform_attn_backward: deterministic mode set-up failed: %s", hipGetErrorString(ed));
-          return OCC_E_LAUNCH;
-        }
-        hipLaunchKernelGGL(msda_bwd_maxabs_kernel, dim3(1024), dim3(256), 0, st, grad_output, n_items * 32,
-                           reinterpret_cast<unsigned*>(work_count + 1));
-        hipLaunchKernelGGL(msda_bwd_det_zero_kernel, dim3((unsigned)w.max_split), dim3(256), 0, st, work_count, split_meta,
-                           tiles);
-        hipLaunchKernelGGL(msda_bwd_replay_det_kernel, dim3((unsigned)w.work_cap), dim3(256), 0, st,
-                           spatial_shapes, level_start_index, work, work_count, items, grad_output, grad_value, S, M,
-                           L, Lq, w.bins_per_bm, split_meta, tiles);
-      } else {
-        hipLaunchKernelGGL(msda_bwd_replay_kernel, dim3((unsigned)w.work_cap), dim3(256), 0, st,
-                           spatial_shapes, level_start_index, work, work_count, items, grad_output, grad_value, S, M,
-                           L, Lq, w.bins_per_bm);
+      const int rc = bwd_bins_replay(w, ws, deterministic, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                                     nullptr, grad_output, n_items * 32, grad_value, B, S, M, L, Lq, P, st);
+      if (rc != OCC_OK) {
+        if (own) (void)hipFreeAsync(ws, st);
+        return rc;
       }
       if (own) (void)hipFreeAsync(ws, st);
     } else {

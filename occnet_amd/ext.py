@@ -230,7 +230,8 @@ def sca_unpair_layout(value_pairs, S=None):
 
 
 def sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, ref_cam, vis_bits,
-                      num_heads, num_levels, num_points, order=None, stats=None, value_layout="rows", value_scale=None):
+                      num_heads, num_levels, num_points, order=None, stats=None, value_layout="rows", value_scale=None,
+                      _timing='sca_fused_forward'):
     """Fused SCA gather.  value (B*NC, S, M, D) float32 or float16; offs (B, Nq, M*L*P*2) / logits (B, Nq, M*L*P) may
     be column slices of one wider Linear output (last dim contiguous); ref_cam (NC,B,Nq,Z,2);
     vis_bits (B,Nq) int32.  -> slots (B, Nq, M*D) float32.
@@ -282,12 +283,100 @@ def sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, re
     fn = (_lib.lib().occ_sca_fused_forward_q16v if q16 else _lib.lib().occ_sca_fused_forward_f16v if half
           else _lib.lib().occ_sca_fused_forward_f32)
     tail = (ptr(value_scale), stream_ptr(value.device)) if half else (stream_ptr(value.device),)
-    with torch.cuda.device(value.device), _timed('sca_fused_forward'):
+    with torch.cuda.device(value.device), _timed(_timing):
         rc = fn(ptr(value), ptr(spatial_shapes), ptr(level_start_index), ptr(offs), i64(offs.stride(1)), ptr(logits),
                 i64(logits.stride(1)), ptr(ref_cam), ptr(vis_bits), ptr(order), ptr(slots), ptr(stats), i32(B),
                 i32(NC), i32(S), i32(M), i32(D), i32(L), i32(P), i32(Z), i32(Nq), *tail)
     _lib.check(rc, "sca_fused_forward")
     return slots
+
+
+def sca_fused_backward_workspace_bytes(B, NC, S, M, D, L, P, Nq):
+    """Bytes of scratch sca_fused_backward takes for these shapes (0: no backward kernel for them)."""
+    lib = _lib.lib()
+    lib.occ_sca_fused_backward_workspace_bytes.restype = ctypes.c_int64
+    return int(lib.occ_sca_fused_backward_workspace_bytes(i32(B), i32(NC), i32(S), i32(M), i32(D), i32(L), i32(P),
+                                                          i32(Nq)))
+
+
+def sca_fused_backward(value, spatial_shapes, level_start_index, offs, logits, ref_cam, vis_bits, grad_slots,
+                       num_heads, num_levels, num_points):
+    """Gradient of sca_fused_forward over fp32 value rows (csrc/sca_fused_backward.hip).  Same inputs as the forward
+    (value (B*NC, S, M, D) float32 row order; offs / logits may be column slices of one wider Linear output) plus
+    grad_slots (B, Nq, M*D) -> (grad_value (B*NC, S, M, D), grad_offs (B, Nq, M*L*P*2), grad_logits (B, Nq, M*L*P)).
+    grad_offs / grad_logits are bit-reproducible; grad_value too under OCC_MSDA_BWD_DETERMINISTIC=1.  Raises
+    OccAmdUnsupported for shapes without a backward kernel."""
+    _need_cuda_f32("value", value)
+    _need_cuda_f32("ref_cam", ref_cam)
+    _need_cuda_f32("offs", offs, contiguous=False)
+    _need_cuda_f32("logits", logits, contiguous=False)
+    _need_cuda_f32("grad_slots", grad_slots)
+    _need_cuda_i64("spatial_shapes", spatial_shapes)
+    _need_cuda_i64("level_start_index", level_start_index)
+    if value.dim() != 4 or ref_cam.dim() != 5:
+        raise OccAmdError("sca_fused_backward: expected value (B*NC, S, M, D) and ref_cam (NC, B, Nq, Z, 2)")
+    NC, B, Nq, Z, _ = ref_cam.shape
+    BN, S, M, D = value.shape
+    L, P = int(num_levels), int(num_points)
+    if BN != B * NC or M != num_heads:
+        raise OccAmdError("sca_fused_backward: value batch must equal B*num_cams")
+    for n, t, w in (("offs", offs, M * L * P * 2), ("logits", logits, M * L * P)):
+        if t.dim() != 3 or tuple(t.shape[:2]) != (B, Nq) or t.shape[-1] != w or t.stride(-1) != 1 \
+                or t.stride(0) != Nq * t.stride(1):
+            raise OccAmdError(f"sca_fused_backward: {n} must be (B,Nq,{w}) with unit inner stride")
+    if vis_bits.dtype != torch.int32 or tuple(vis_bits.shape) != (B, Nq) or not vis_bits.is_contiguous():
+        raise OccAmdError("sca_fused_backward: vis_bits must be contiguous int32 (B,Nq)")
+    if tuple(grad_slots.shape) != (B, Nq, M * D):
+        raise OccAmdError(f"sca_fused_backward: grad_slots must be (B,Nq,{M * D})")
+    need = sca_fused_backward_workspace_bytes(B, NC, S, M, D, L, P, Nq)
+    if need <= 0:
+        raise OccAmdUnsupported(f"sca_fused_backward: no backward kernel for M={M} D={D} L={L} P={P} "
+                                f"(or shapes beyond the binned grad_value path)")
+    # scratch from torch's caching allocator, freed back to the pool when this call returns (stream-ordered)
+    ws = torch.empty(need, dtype=torch.uint8, device=value.device)
+    grad_value = torch.zeros_like(value)
+    grad_offs = torch.empty((B, Nq, M * L * P * 2), dtype=torch.float32, device=value.device)
+    grad_logits = torch.empty((B, Nq, M * L * P), dtype=torch.float32, device=value.device)
+    with torch.cuda.device(value.device), _timed('sca_fused_backward'):
+        rc = _lib.lib().occ_sca_fused_backward_f32(
+            ptr(value), ptr(spatial_shapes), ptr(level_start_index), ptr(offs), i64(offs.stride(1)), ptr(logits),
+            i64(logits.stride(1)), ptr(ref_cam), ptr(vis_bits), ptr(grad_slots), ptr(grad_value), ptr(grad_offs),
+            i64(grad_offs.stride(1)), ptr(grad_logits), i64(grad_logits.stride(1)), i32(B), i32(NC), i32(S), i32(M),
+            i32(D), i32(L), i32(P), i32(Z), i32(Nq), ptr(ws), i64(need), stream_ptr(value.device))
+    _lib.check(rc, "sca_fused_backward")
+    return grad_value, grad_offs, grad_logits
+
+
+class SCAFusedFunction(torch.autograd.Function):
+    """The fused SCA gather as an autograd node: forward = occ_sca_fused_forward_f32 on fp32 value rows (training always
+    takes fp32 rows, whatever OCC_SCA_VALUES says), backward = occ_sca_fused_backward_f32.
+    value (B*NC, S, M, D) float32; offs / logits (B, Nq, ...) — column slices of one Linear output are fine, autograd
+    routes both gradients into it; ref_cam (NC, B, Nq, Z, 2) and vis_bits (B, Nq) are constants -> slots (B, Nq, M*D).
+    Raises OccAmdUnsupported (before anything runs) for shapes without a backward kernel."""
+
+    @staticmethod
+    def forward(ctx, value, offs, logits, ref_cam, vis_bits, spatial_shapes, level_start_index, num_heads, num_levels,
+                num_points):
+        value = value.contiguous()
+        NC, B, Nq = ref_cam.shape[:3]
+        BN, S, M, D = value.shape
+        if sca_fused_backward_workspace_bytes(B, NC, S, M, D, int(num_levels), int(num_points), Nq) <= 0:
+            raise OccAmdUnsupported(f"SCAFusedFunction: no backward kernel for M={M} D={D} L={num_levels} "
+                                    f"P={num_points}")
+        # timed under a name of its own: 'sca_fused_forward' is the inference gather's (bench.py's roofline leg)
+        slots = sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, ref_cam, vis_bits,
+                                  num_heads, num_levels, num_points, _timing='sca_fused_forward_train')
+        ctx.save_for_backward(value, offs, logits, ref_cam, vis_bits, spatial_shapes, level_start_index)
+        ctx.dims = (int(num_heads), int(num_levels), int(num_points))
+        return slots
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_slots):
+        value, offs, logits, ref_cam, vis_bits, spatial_shapes, level_start_index = ctx.saved_tensors
+        gv, go, gl = sca_fused_backward(value, spatial_shapes, level_start_index, offs, logits, ref_cam, vis_bits,
+                                        grad_slots.contiguous(), *ctx.dims)
+        return gv, go, gl, None, None, None, None, None, None, None
 
 
 def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points,

@@ -306,6 +306,34 @@ class SpatialCrossAttention(BaseModule):
     # rebatch + softmax + offset normalisation + anchor add as one kernel (OCC_SCA_TRAIN_PREP=torch: ATen ops)
     prep_kernel = os.environ.get("OCC_SCA_TRAIN_PREP", "kernel") != "torch"
 
+    # training through the fused gather and its backward (ext.SCAFusedFunction) instead of the padded decomposition below
+    # (OCC_SCA_TRAIN_FUSED=1; default off)
+    train_fused = os.environ.get("OCC_SCA_TRAIN_FUSED", "0") == "1"
+
+    def _fused_train_slots(self, query, value, reference_points_cam, bev_mask, spatial_shapes, level_start_index,
+                           vis_bits=None):
+        """Autograd form of _fused_slots: the value projection and the two query-side Linears (one GEMM) in the graph,
+        then the fused gather on fp32 value rows with its HIP backward.  Raises OccAmdUnsupported before any work
+        for shapes without a backward kernel."""
+        da = self.deformable_attention
+        if not isinstance(da, MSDeformableAttention3D):
+            raise OccAmdUnsupported("fused SCA training: needs MSDeformableAttention3D")
+        num_cams, l, bs, _ = value.shape
+        Z = reference_points_cam.shape[3]
+        if (ext.sca_fused_backward_workspace_bytes(bs, self.num_cams, l, da.num_heads, self.embed_dims // da.num_heads,
+                                                   da.num_levels, da.num_points, query.shape[1]) <= 0
+                or da.num_points % Z):
+            raise OccAmdUnsupported("fused SCA training: no backward kernel for these shapes")
+        v = value.permute(2, 0, 1, 3).reshape(bs * self.num_cams, l, self.embed_dims)
+        v = da.value_proj(v.float()).view(bs * self.num_cams, l, da.num_heads, -1)
+        proj = da.query_linears_autograd(query.float())                             # (bs, Q, n_off + n_att)
+        n_off = da.sampling_offsets.out_features
+        if vis_bits is None:
+            vis_bits = pack_vis_bits(bev_mask)
+        return ext.SCAFusedFunction.apply(v, proj[..., :n_off], proj[..., n_off:],
+                                          reference_points_cam.float().contiguous(), vis_bits, spatial_shapes,
+                                          level_start_index, da.num_heads, da.num_levels, da.num_points)
+
     def _rebatch_plan(self, bev_mask, reference_points_cam):
         """Visible-query lists of every camera from batch element 0's mask (reference :138-140) as ONE padded index
         tensor, built once per mask TENSOR (the encoder hands the same bev_mask to all layers; nonzero() is a host
@@ -437,6 +465,12 @@ class SpatialCrossAttention(BaseModule):
                                           vis_bits=kwargs.get('vis_bits'),
                                           order=kwargs.get('sca_bev_order', kwargs.get('bev_order')),
                                           stats=kwargs.get('gather_stats'))
+            except OccAmdUnsupported:
+                slots = None
+        elif self.use_fused and self.train_fused and key_padding_mask is None:
+            try:
+                slots = self._fused_train_slots(query, value, reference_points_cam, bev_mask, spatial_shapes,
+                                                level_start_index, vis_bits=kwargs.get('vis_bits'))
             except OccAmdUnsupported:
                 slots = None
         if slots is None:
