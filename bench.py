@@ -10,7 +10,11 @@ to /32 -> ResNet-50 + FPN -> 4 BEVFormer encoder layers -> lifter + Conv3d decod
 voxels x (17 class logits + 2 flow)) per rank, inputs resident in HBM, synthetic data, random-init
 weights.  Ranks process independent samples (data parallel, no data-path collective for inference);
 the only collectives are the barrier and the MAX-reduce of the elapsed time.  Rank 0 prints ONE JSON
-line.  Extra objects on that line:
+line.
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write --dump-outputs, print
+the line.  `--full` adds everything else the bench measures or checks, each after the timed steps, as extra objects
+on that line:
   roofline     the dominant kernel (fused SCA deformable gather): algorithmic bytes per launch
                (N_in*d*e_v + R*S*12 + R*256*e_v, with R and N_in counted on device for
                the very inputs being timed) / mean launch duration from HIP events recorded on the
@@ -31,9 +35,13 @@ line.  Extra objects on that line:
                precision (stock fp32 modules) and its own images -> voxels parity figure against the host.
   extra        short passes of the hot path alone, `--history 3` (configs[2]) and the 400x400x32 grid (configs[4]).
 
-Timing protocol: the K timed steps carry HIP events around the roofline kernel only (8 event records per step);
-`value_no_instrumentation` is a second barrier-bracketed pass of K steps with no events at all, and the per-kernel
-breakdown (`mfma_kernels`) comes from 3 further untimed steps.  `--history H` times BASELINE.json configs[2]: every
+  value_no_instrumentation, mfma_kernels, host_enqueue_ms_per_step   see the timing protocol.
+
+Timing protocol: the K timed steps carry HIP events around the roofline kernel only (8 event records per step), with
+or without --full; with --full, one untimed step before them counts the roofline's R and N_in, and after them
+`value_no_instrumentation` is a second barrier-bracketed pass of K steps with no events at all, the per-kernel
+breakdown (`mfma_kernels`) comes from 3 further untimed steps and `host_enqueue_ms_per_step` from 5 isolated ones.
+`--history H` times BASELINE.json configs[2]: every
 sample is a queue of H history frames (obtain_history_bev: backbone + BEV encoder per frame, each attending to the rotated
 BEV of the frame before) followed by the current frame's full pass with that history.
 `--dump-outputs DIR` saves what the last timed step returned (rank 0) as DIR/<name>.npy, for output-for-output comparison
@@ -114,9 +122,13 @@ def parse():
                     help="BASELINE.json configs[2] (temporal self-attention with a real history): every sample = this many "
                          "history frames through BEVFormerOcc.obtain_history_bev (reference bevformer_occ.py:159-178) + "
                          "the current frame with prev_bev; 3 = the reference's 4-frame queue.  Default 0 = configs[1]")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything beyond the headline figure: roofline, "
+                         "per-kernel and host-enqueue figures, the un-instrumented second pass, the CPU oracle baseline "
+                         "and its parity checks, the fp32-backbone legs and the `extra` configurations (default: off)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle and fp32 legs")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the short hot-path / --history 3 / hi-res passes reported under `extra`")
+                    help="with --full: skip the short hot-path / --history 3 / hi-res passes reported under `extra`")
     ap.add_argument("--cpu-baseline-only", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--no-step-graph", dest="step_graph", action="store_false", default=None,
@@ -870,7 +882,7 @@ def main():
     torch.cuda.synchronize()
     if args.mode == "train" and world > 1 and hasattr(stepper.model, "_set_ddp_runtime_logging_sample_rate"):
         stepper.model._set_ddp_runtime_logging_sample_rate(1)      # every timed step feeds DDP's comm / compute timers
-    stats, da = gather_stats(model, stepper) if args.mode == "infer" else ([], None)
+    stats, da = gather_stats(model, stepper) if args.mode == "infer" and args.full else ([], None)
     if args.history:    # every SCA module ran once per frame of the queue: counters per launch
         stats = [(r // (1 + args.history), n // (1 + args.history)) for r, n in stats]
 
@@ -948,46 +960,49 @@ def main():
     # the last timed step's result, copied to the host before any further step can overwrite its buffers
     dumped = (_host_outputs(graph_out if args.step_graph else last_out[0])
               if args.dump_outputs and rank == 0 else None)
-    for _ in range(5):
-        torch.cuda.synchronize()
-        t_e = time.perf_counter()
-        run_step()
-        enqueue_s.append(time.perf_counter() - t_e)
-    torch.cuda.synchronize()
-    times = ext.kernel_times_ms(record) if record is not None else {}
-    ext.kernel_timing(False)
-    if record is None and args.step_graph and args.mode == "infer":
-        # graph replays carry no events: the roofline kernel's launch time comes from a few EAGER steps after the timed pass
-        rec_g = ext.kernel_timing(True)
-        ext.kernel_timing_only({"sca_fused_forward"})
-        for _ in range(3):
-            stepper()
-        torch.cuda.synchronize()
-        times = {k: v for k, v in ext.kernel_times_ms(rec_g).items() if k == "sca_fused_forward"}
-        ext.kernel_timing(False)
-    # per-kernel breakdown: `detail` further, untimed steps with every instrumented launch timed
-    detail = 3
-    if record is not None:
-        rec2 = ext.kernel_timing(True)
-        for _ in range(detail):
-            stepper()
-        torch.cuda.synchronize()
-        for k, v in ext.kernel_times_ms(rec2).items():
-            if k != "sca_fused_forward":
-                times[k] = v
-        ext.kernel_timing(False)
-        # the same K steps once more with no events at all: what the instrumentation costs
-        elapsed_clean = timed_pass(args.steps)
+    # with --full: the figures that take steps of their own, all after the timed passes
+    times, elapsed_clean, sca_rank_ms, detail = {}, None, None, 3
+    if not args.full:
+        ext.kernel_timing(False)        # the timed region's events are left unread: nothing reports them
     else:
-        elapsed_clean = elapsed
-    # every rank's mean roofline-kernel launch time (a future multi-GPU run shows per-rank skew)
-    sca_rank_ms = None
-    if world > 1 and times.get("sca_fused_forward"):
-        mine = torch.tensor([sum(times["sca_fused_forward"]) / len(times["sca_fused_forward"])], dtype=torch.float64,
-                            device="cpu" if share else device)
-        allm = [torch.zeros_like(mine) for _ in range(world)]
-        dist.all_gather(allm, mine)
-        sca_rank_ms = [float(t.item()) for t in allm]
+        for _ in range(5):
+            torch.cuda.synchronize()
+            t_e = time.perf_counter()
+            run_step()
+            enqueue_s.append(time.perf_counter() - t_e)
+        torch.cuda.synchronize()
+        times = ext.kernel_times_ms(record) if record is not None else {}
+        ext.kernel_timing(False)
+        if record is None and args.step_graph and args.mode == "infer":
+            # graph replays carry no events: the roofline kernel's launch time comes from a few EAGER steps after the timed pass
+            rec_g = ext.kernel_timing(True)
+            ext.kernel_timing_only({"sca_fused_forward"})
+            for _ in range(3):
+                stepper()
+            torch.cuda.synchronize()
+            times = {k: v for k, v in ext.kernel_times_ms(rec_g).items() if k == "sca_fused_forward"}
+            ext.kernel_timing(False)
+        # per-kernel breakdown: `detail` further, untimed steps with every instrumented launch timed
+        if record is not None:
+            rec2 = ext.kernel_timing(True)
+            for _ in range(detail):
+                stepper()
+            torch.cuda.synchronize()
+            for k, v in ext.kernel_times_ms(rec2).items():
+                if k != "sca_fused_forward":
+                    times[k] = v
+            ext.kernel_timing(False)
+            # the same K steps once more with no events at all: what the instrumentation costs
+            elapsed_clean = timed_pass(args.steps)
+        else:
+            elapsed_clean = elapsed
+        # every rank's mean roofline-kernel launch time (a future multi-GPU run shows per-rank skew)
+        if world > 1 and times.get("sca_fused_forward"):
+            mine = torch.tensor([sum(times["sca_fused_forward"]) / len(times["sca_fused_forward"])], dtype=torch.float64,
+                                device="cpu" if share else device)
+            allm = [torch.zeros_like(mine) for _ in range(world)]
+            dist.all_gather(allm, mine)
+            sca_rank_ms = [float(t.item()) for t in allm]
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
@@ -999,8 +1014,6 @@ def main():
             "value": value, "unit": "samples/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": ms_per_step, "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None,
-            # second pass of the same K steps without any HIP events (the timed region carries 2 per SCA launch)
-            "value_no_instrumentation": world * args.steps / elapsed_clean,
             "passes": {"n": n_pass, "steps_each": args.steps, "statistic": "median",
                        "ms_per_step": [e / args.steps * 1e3 for e in pass_s],
                        "value_min": world * args.steps / max(pass_s), "value_max": world * args.steps / min(pass_s)},
@@ -1036,11 +1049,14 @@ def main():
             },
         }
         out["host_cores_bound"] = None if bound is None else len(bound)
-        # launch-side time of ONE step on rank 0: the host time of run_step() with an EMPTY device queue (a synchronise
-        # before each of 5 isolated steps, median) — inside the timed loop the host is throttled by the queue depth and its
-        # loop time says nothing.  Far below ms_per_step = the GPU is the bottleneck; close to it = the rank is host-bound
-        # (the first thing to look at when N ranks share a host: VERDICT r4 item 8)
-        out["host_enqueue_ms_per_step"] = _median(enqueue_s) * 1e3 if enqueue_s else None
+        if args.full:
+            # second pass of the same K steps without any HIP events (the timed region carries 2 per SCA launch)
+            out["value_no_instrumentation"] = world * args.steps / elapsed_clean
+            # launch-side time of ONE step on rank 0: the host time of run_step() with an EMPTY device queue (a synchronise
+            # before each of 5 isolated steps, median) — inside the timed loop the host is throttled by the queue depth and
+            # its loop time says nothing.  Far below ms_per_step = the GPU is the bottleneck; close to it = the rank is
+            # host-bound (the first thing to look at when N ranks share a host: VERDICT r4 item 8)
+            out["host_enqueue_ms_per_step"] = _median(enqueue_s) * 1e3
         if args.mode == "train" and world > 1:
             from occnet_amd.dist import ddp_comm_stats
             # the path's ONLY collective: DDP's bucketed gradient all-reduce (RCCL over xGMI), as DDP's logger timed it
@@ -1159,7 +1175,7 @@ def main():
                                "note": "event-timed launches of the bf16 NHWC inference plan (ResNet-50 + FPN, eval BN folded); "
                                        "dtype bf16 in / f32 accumulate; peak = 2.5 PF dense bf16 MFMA; outside SURVEY.md section 8"}
                 out.setdefault("mfma_kernels", {"peak_tflops_f32": 157.3, "peak_tflops_bf16": 2500.0})["backbone"] = bb
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 hf = stepper.features() if args.mode == "infer" and not args.history else None
                 out["cpu_baseline"] = cpu_baseline(cfg, geo, device=device, headline_feats=hf)
@@ -1183,7 +1199,8 @@ def main():
                     except Exception as e:
                         out["value_fp32_conformant"] = None
                         out["fp32_conformant"] = {"error": repr(e)}
-        if world == 1 and args.mode == "infer" and not args.no_extras and not args.history and stepper.scope == "e2e":
+        if (args.full and world == 1 and args.mode == "infer" and not args.no_extras and not args.history
+                and stepper.scope == "e2e"):
             out["extra"] = extra_legs(args, cfg, model, geo, device)
         if dumped is not None:
             out["dump_outputs"] = dump_outputs(args.dump_outputs, dumped)

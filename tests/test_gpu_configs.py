@@ -109,7 +109,7 @@ def test_bench_multi_rank_plumbing(tmp_path):
     env = dict(os.environ, OCC_BENCH_SHARE_GPU="1", MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--steps", "3", "--warmup", "1", "--scope", "hotpath", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--scope", "hotpath", "--no-cpu-baseline", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]
@@ -139,3 +139,5 @@ def test_bench_self_launch_two_ranks():
     assert len(lines) == 1, res.stdout[-2000:]
     out = json.loads(lines[0])
     assert out["n_gpus"] == 2 and out["steps"] == 2 and out["config"]["parallelism"] == "dp2"
+    # a plain run (no --full) reports the headline only: no roofline, per-kernel or second-pass figures
+    assert not {"roofline", "mfma_kernels", "value_no_instrumentation", "host_enqueue_ms_per_step"} & set(out)

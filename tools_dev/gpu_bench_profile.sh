@@ -6,9 +6,10 @@ export TMPDIR=/tmp
 KR="sca_fused|tsa_fused|conv3d_mfma|conv3d_bf16x3|occ_heads|linear_bf16x3|linear_mfma|value_proj"
 for what in "${@:-bench trace}"; do
 case $what in
-bench)
-  timeout 900 python bench.py --steps 30 --warmup 5 > gpurun_out/bench_e2e.log 2>&1; tail -1 gpurun_out/bench_e2e.log | cut -c1-240
-  timeout 300 python bench.py --scope hotpath --steps 30 --warmup 5 --no-cpu-baseline > gpurun_out/bench_hot.log 2>&1; tail -1 gpurun_out/bench_hot.log | cut -c1-200 ;;
+bench)   # the --full lines; logs go to $OUT (default bench_logs/)
+  OUT=${OUT:-bench_logs}; mkdir -p "$OUT"
+  timeout 900 python bench.py --steps 30 --warmup 5 --full > "$OUT/bench_e2e.log" 2>&1; tail -1 "$OUT/bench_e2e.log" | cut -c1-240
+  timeout 300 python bench.py --scope hotpath --steps 30 --warmup 5 --no-cpu-baseline --full > "$OUT/bench_hot.log" 2>&1; tail -1 "$OUT/bench_hot.log" | cut -c1-200 ;;
 train)
   timeout 900 python bench.py --mode train --steps 5 --warmup 3 --no-cpu-baseline > gpurun_out/bench_train.log 2>&1; tail -1 gpurun_out/bench_train.log | cut -c1-240 ;;
 trace)
