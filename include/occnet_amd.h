@@ -597,6 +597,17 @@ int occ_conv1x1_nhwc_bf16(const void* x, const void* weight, const float* bias, 
                           void* out, int batch, int Hin, int Win, int Cin, int Cout, int stride, int relu,
                           int residual_upsample2, void* stream);
 
+/* The same convolution with the kernel forced (tests, probes).  variant: 0 = the launcher's choice from the arguments, as
+ * the entry point above; 1 = the tiled kernel (64 pixels x 256 channels per block, K staged in 32-channel chunks);
+ * 2 = the activation-resident kernel (the block's pixel tile x Cin stays in LDS for all its output channels: Cin 128, 256
+ * or 512, Cout % 128 == 0, Cout <= 4096) with its default tile; 22 / 24 = resident with the 64- / 128-row
+ * tile (22: Cin 512 only); 100 * ncb + 22 / 24 also fixes the column blocks per row tile (ncb must
+ * divide the number of column passes).  A variant the arguments have no kernel for returns OCC_E_UNSUPPORTED ("no
+ * variant") before any launch.  The kernels differ only in f32 summation order; each is deterministic. */
+int occ_conv1x1_nhwc_bf16_variant(const void* x, const void* weight, const float* bias, const void* residual,
+                                  void* out, int batch, int Hin, int Win, int Cin, int Cout, int stride, int relu,
+                                  int residual_upsample2, int variant, void* stream);
+
 /* Backbone 3x3 pad-1 convolution, stride 1 or 2, on NHWC bf16 with bias (+ ReLU) fused (outside the
  * hand-written hot path).  x (batch, H, W, Cin) bf16 ; weight packed by occ_conv3x3_pack_weight_bf16 from
  * torch's (Cout, Cin, 3, 3) f32 layout to [Cin/32][tap][co][32] bf16 ; bias (Cout) f32 ;

@@ -15,6 +15,7 @@
 // (occ_mfma_pack_b_frag_bf16: [K/16][Cout/32][lane][8 bf16]) and goes global -> registers directly, three chunks
 // deep; v_mfma_f32_32x32x16_bf16, 2 k-steps per chunk.
 // Strided 1x1 convolutions (the downsample branch) only change which input pixel a row reads.
+#include <cstdlib>
 #include "common.h"
 
 namespace occ {
@@ -201,10 +202,20 @@ __global__ __launch_bounds__(256) void conv1x1_nhwc_bf16_kernel(
 
 }  // namespace occ
 
-extern "C" int occ_conv1x1_nhwc_bf16(const void* x, const void* weight, const float* bias,
-                                     const void* residual, void* out, int batch, int Hin, int Win,
-                                     int Cin, int Cout, int stride, int relu, int residual_upsample2,
-                                     void* stream) {
+namespace occ {
+// the activation-resident kernels (conv1x1_resident_bf16.hip)
+int conv1x1_resident_tile(int Cin, int Cout, long M, long in_pixels, int rt);
+int conv1x1_resident_launch(const void* x, const void* weight, const float* bias, const void* residual, void* out,
+                            long M, int Hin, int Win, int Hout, int Wout, int Cin, int Cout, int stride, int relu,
+                            int residual_upsample2, int rt, int ncb_force, hipStream_t st);
+}  // namespace occ
+
+// variant: 0 = chosen here from the arguments, 1 = the tiled kernel above, 2 = the activation-resident kernel with its
+// default tile, 22 / 24 = resident with the 64- / 128-row tile; 100 * ncb + 22 / 24 also fixes the number of column
+// blocks per row tile (probes).
+static int conv1x1_nhwc_bf16_launch(const void* x, const void* weight, const float* bias, const void* residual,
+                                    void* out, int batch, int Hin, int Win, int Cin, int Cout, int stride, int relu,
+                                    int residual_upsample2, int variant, void* stream) {
   using namespace occ;
   OCC_CHECK_ARG(x && weight && bias && out, "conv1x1_nhwc_bf16: null pointer argument");
   OCC_CHECK_ARG(batch > 0 && Hin > 0 && Win > 0 && Cin > 0 && Cout > 0 && stride > 0,
@@ -218,7 +229,29 @@ extern "C" int occ_conv1x1_nhwc_bf16(const void* x, const void* weight, const fl
   OCC_CHECK_ARG(!residual_upsample2 || (residual && Hout % 2 == 0 && Wout % 2 == 0),
                 "conv1x1_nhwc_bf16: an upsampled residual needs even output sizes (exact x2 nearest upsampling)");
   const long M = (long)batch * Hout * Wout;
+  const long in_pixels = (long)batch * Hin * Win;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  // OCC_CONV1X1_RESIDENT=0 (development switch, read once) keeps every default launch on the tiled kernel
+  static const bool resident_on = [] { const char* e = getenv("OCC_CONV1X1_RESIDENT"); return !(e && e[0] == '0'); }();
+  int rt = 0, ncb_force = 0;
+  if (variant == 0) {
+    // the resident kernel wherever it exists: every shape of the ResNet-50 / FPN table it covers measured faster than
+    // on the tiled kernel (EXPERIMENTS.md section 8g); maps of a few row tiles stay where they were
+    if (resident_on && M >= 512) rt = conv1x1_resident_tile(Cin, Cout, M, in_pixels, 0);
+  } else if (variant != 1) {
+    const int v = variant % 100;
+    ncb_force = variant / 100;
+    const int want = v == 2 && ncb_force == 0 ? 0 : v == 22 ? 2 : v == 24 ? 4 : -1;
+    rt = variant < 0 || want < 0 ? 0 : conv1x1_resident_tile(Cin, Cout, M, in_pixels, want);
+    if (rt == 0) {
+      set_error("conv1x1_nhwc_bf16: no variant %d for Cin=%d Cout=%d (1 = tiled; 2, 22, 24 = activation-resident: Cin 128 / "
+                "256 / 512, Cout %% 128 == 0, Cout <= 4096; 22 only Cin 512)", variant, Cin, Cout);
+      return OCC_E_UNSUPPORTED;
+    }
+  }
+  if (rt != 0)
+    return conv1x1_resident_launch(x, weight, bias, residual, out, M, Hin, Win, Hout, Wout, Cin, Cout, stride, relu,
+                                   residual_upsample2, rt, ncb_force, st);
 #define OCC_C1_LAUNCH(NTT, RTT, BNN)                                                                \
   hipLaunchKernelGGL((conv1x1_nhwc_bf16_kernel<NTT, RTT>),                                          \
                      dim3((unsigned)((M + 32 * RTT - 1) / (32 * RTT)), (unsigned)((Cout + BNN - 1) / BNN)), \
@@ -232,4 +265,23 @@ extern "C" int occ_conv1x1_nhwc_bf16(const void* x, const void* weight, const fl
 #undef OCC_C1_LAUNCH
   OCC_CHECK_LAUNCH("conv1x1_nhwc_bf16");
   return OCC_OK;
+}
+
+extern "C" int occ_conv1x1_nhwc_bf16(const void* x, const void* weight, const float* bias,
+                                     const void* residual, void* out, int batch, int Hin, int Win,
+                                     int Cin, int Cout, int stride, int relu, int residual_upsample2,
+                                     void* stream) {
+  return conv1x1_nhwc_bf16_launch(x, weight, bias, residual, out, batch, Hin, Win, Cin, Cout, stride, relu,
+                                  residual_upsample2, 0, stream);
+}
+
+// The same convolution with the kernel forced (tests, probes): see conv1x1_nhwc_bf16_launch.  A variant the arguments
+// have no kernel for returns OCC_E_UNSUPPORTED before any launch.  The kernels differ only in f32 summation order; each
+// one is deterministic.
+extern "C" int occ_conv1x1_nhwc_bf16_variant(const void* x, const void* weight, const float* bias,
+                                             const void* residual, void* out, int batch, int Hin, int Win,
+                                             int Cin, int Cout, int stride, int relu, int residual_upsample2,
+                                             int variant, void* stream) {
+  return conv1x1_nhwc_bf16_launch(x, weight, bias, residual, out, batch, Hin, Win, Cin, Cout, stride, relu,
+                                  residual_upsample2, variant, stream);
 }

@@ -1674,11 +1674,13 @@ def conv1x1_pack_weight(weight2d):
     return mfma_pack_b_frag(weight2d.float().contiguous())
 
 
-def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, residual_upsample2=False):
+def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, residual_upsample2=False, variant=None):
     """1x1 convolution + bias (+ residual) (+ ReLU) on a channels_last bf16 activation, one launch.
     x (N, Cin, H, W) channels_last bf16; weight_frag = conv1x1_pack_weight((Cout, Cin) matrix); bias (Cout) f32;
     residual (N, Cout, Ho, Wo) channels_last bf16 or None -> (N, Cout, Ho, Wo) channels_last bf16.
-    residual_upsample2: residual is (N, Cout, Ho/2, Wo/2) and is added nearest-upsampled x2 (FPN top-down)."""
+    residual_upsample2: residual is (N, Cout, Ho/2, Wo/2) and is added nearest-upsampled x2 (FPN top-down).
+    variant: None = the launcher's choice; an int forces the kernel (occ_conv1x1_nhwc_bf16_variant: 1 = tiled, 2 =
+    activation-resident, 22 / 24 = resident with the 64- / 128-row tile); OccAmdUnsupported where the shape has none."""
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)):
         raise OccAmdUnsupported("conv1x1_nhwc: x must be a channels_last bfloat16 device tensor")
@@ -1699,10 +1701,16 @@ def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, resi
                                      residual.is_contiguous(memory_format=torch.channels_last)):
         raise OccAmdUnsupported("conv1x1_nhwc: residual must match the output (channels_last bfloat16)")
     with torch.cuda.device(x.device), _timed('bb_conv1x1'):
-        rc = _lib.lib().occ_conv1x1_nhwc_bf16(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
-                                              i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
-                                              i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
-                                              stream_ptr(x.device))
+        if variant is None:
+            rc = _lib.lib().occ_conv1x1_nhwc_bf16(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
+                                                  i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
+                                                  i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
+                                                  stream_ptr(x.device))
+        else:
+            rc = _lib.lib().occ_conv1x1_nhwc_bf16_variant(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
+                                                          i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
+                                                          i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
+                                                          i32(int(variant)), stream_ptr(x.device))
     _note_flops('bb_conv1x1', 2.0 * N * Ho * Wo * Cin * Cout)
     _lib.check(rc, "conv1x1_nhwc")
     return out

@@ -48,23 +48,47 @@ def main(which):
                 fl = 2.0 * N * ho * wo * cout * cin * 9
                 tag = 'auto' if v is None else f'v{v}'
                 print(f"conv3x3 {cin:4d}->{cout:4d} {h:3d}x{w:3d} s{s} {tag:4s}: {us:7.1f} us  {fl / us * 1e-6:6.1f} TF/s")
-    if 'c1' in which:
-        for (cin, cout, h, w, s, res) in [(256, 128, 232, 400, 1, 0), (128, 512, 116, 200, 1, 1),
-                                          (512, 128, 116, 200, 1, 0), (256, 512, 232, 400, 2, 0),
-                                          (512, 256, 116, 200, 1, 0), (256, 1024, 58, 100, 1, 1),
-                                          (1024, 256, 58, 100, 1, 0), (512, 1024, 116, 200, 2, 0),
-                                          (1024, 512, 58, 100, 1, 0), (512, 2048, 29, 50, 1, 1),
-                                          (2048, 512, 29, 50, 1, 0), (1024, 2048, 58, 100, 2, 0),
-                                          (512, 256, 116, 200, 1, 0), (1024, 256, 58, 100, 1, 0),
-                                          (2048, 256, 29, 50, 1, 0)]:
+    if 'c1' in which or 'c1v' in which or 'c1x' in which:
+        # res: 0 none, 1 plain, 2 = the coarser lateral, added nearest-upsampled x2 (residual_upsample2, as the plan
+        # launches FPN laterals 0 and 1).  c1v: tiled (1) against activation-resident (2) next to the launcher's
+        # choice, 5 interleaved rounds, median and min-max; c1x adds the resident tiles and column splits.
+        def variants(cin, cout, res):
+            if 'c1v' not in which and 'c1x' not in which:
+                return (None,)
+            if cin > 512:
+                return (None, 1)
+            vs = [None, 1, 2]
+            if 'c1x' in which:
+                np_ = cout // (256 if cout % 256 == 0 else 128)
+                tiles = (24, 22) if cin == 512 else (24,)
+                vs += [100 * d + t for t in tiles for d in range(1, np_ + 1) if np_ % d == 0]
+            return tuple(vs)
+        for (cin, cout, h, w, s, res, relu) in [(256, 128, 232, 400, 1, 0, 1), (128, 512, 116, 200, 1, 1, 1),
+                                                (512, 128, 116, 200, 1, 0, 1), (256, 512, 232, 400, 2, 0, 0),
+                                                (512, 256, 116, 200, 1, 0, 1), (256, 1024, 58, 100, 1, 1, 1),
+                                                (1024, 256, 58, 100, 1, 0, 1), (512, 1024, 116, 200, 2, 0, 0),
+                                                (1024, 512, 58, 100, 1, 0, 1), (512, 2048, 29, 50, 1, 1, 1),
+                                                (2048, 512, 29, 50, 1, 0, 1), (1024, 2048, 58, 100, 2, 0, 0),
+                                                (512, 256, 116, 200, 1, 2, 0), (1024, 256, 58, 100, 1, 2, 0),
+                                                (2048, 256, 29, 50, 1, 0, 0)]:
             x, wp, b = act(cin, h, w), ext.conv1x1_pack_weight(mk(cout, cin)), mk(cout)
             ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
-            r = act(cout, ho, wo) if res else None
-            us = timeit(lambda: ext.conv1x1_nhwc(x, wp, b, residual=r, relu=True, stride=s))
+            r = act(cout, ho, wo) if res == 1 else act(cout, ho // 2, wo // 2) if res == 2 else None
+            vs = variants(cin, cout, res)
+            rounds = 5 if len(vs) > 1 else 1
+            times = {v: [] for v in vs}
+            for _ in range(rounds):
+                for v in vs:
+                    times[v].append(timeit(lambda: ext.conv1x1_nhwc(x, wp, b, residual=r, relu=bool(relu), stride=s,
+                                                                    residual_upsample2=res == 2, variant=v)))
             fl = 2.0 * N * ho * wo * cout * cin
-            mb = N * (ho * wo * (cin + cout * (2 if res else 1))) * 2 / 1e6
-            print(f"conv1x1 {cin:4d}->{cout:4d} {h:3d}x{w:3d} s{s} res{res}: {us:7.1f} us  {fl / us * 1e-6:6.1f} TF/s  "
-                  f"{mb / us:5.2f} TB/s")
+            mb = N * (ho * wo * (cin + cout * (2 if res == 1 else 1.25 if res == 2 else 1))) * 2 / 1e6
+            for v in vs:
+                t = sorted(times[v])
+                us = t[rounds // 2]
+                tag = 'auto' if v is None else f'v{v}'
+                print(f"conv1x1 {cin:4d}->{cout:4d} {h:3d}x{w:3d} s{s} res{res} {tag:5s}: {us:7.1f} us "
+                      f"[{t[0]:6.1f} - {t[-1]:6.1f}]  {fl / us * 1e-6:6.1f} TF/s  {mb / us:5.2f} TB/s", flush=True)
 
 
 def vp():
