@@ -1443,12 +1443,26 @@ class DropoutAddLayerNormFunction(torch.autograd.Function):
         return gx.view(shape), gres.view(rshape), ggb[:C], ggb[C:], None, None
 
 
+def _float4_rows_ok(t):
+    """The LayerNorm kernels read their operands as float4: dense rows starting on a 16-byte boundary.  (x and residual are
+    made contiguous by the node, and a copy is aligned; a tensor that already is contiguous is passed as it stands.)"""
+    return t.is_contiguous() and t.data_ptr() % 16 == 0
+
+
 def dropout_add_layernorm_ok(x, residual, norm):
-    """True when DropoutAddLayerNormFunction covers this site (fp32 device rows of 256 columns, an affine LayerNorm over them)."""
-    return (isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine and norm.bias is not None
+    """True when DropoutAddLayerNormFunction covers this site: fp32 rows of 256 columns and an affine LayerNorm over them, all
+    on ONE device, gamma / beta dense and 16-byte aligned (an offset view of a flat parameter buffer is not), x / residual
+    aligned where the node passes them on without a copy.  False: the site keeps its ATen tail."""
+    if not (isinstance(norm, torch.nn.LayerNorm) and norm.elementwise_affine and norm.bias is not None
             and tuple(norm.normalized_shape) == (256,) and x.is_cuda and x.dtype == torch.float32
             and residual.dtype == torch.float32 and x.shape == residual.shape and x.shape[-1] == 256
-            and x.numel() < (1 << 32) and norm.weight.dtype == torch.float32)
+            and x.numel() < (1 << 32) and norm.weight.dtype == torch.float32 and norm.bias.dtype == torch.float32):
+        return False
+    if not all(t.device == x.device for t in (residual, norm.weight, norm.bias)):
+        return False
+    if not (_float4_rows_ok(norm.weight) and _float4_rows_ok(norm.bias)):
+        return False
+    return all(not t.is_contiguous() or t.data_ptr() % 16 == 0 for t in (x, residual))
 
 
 def dropout_add_layernorm(x, residual, norm, p, training):

@@ -109,17 +109,24 @@ class ConvBNActFunction(torch.autograd.Function):
         from .. import ext
         x16, w16, y, weight, gamma, rstd, mean_rstd, conv_bias = ctx.saved_tensors
         stride, padding, relu, res_dtype, one_launch = ctx.conv
+        need = ctx.needs_input_grad
         s = None if (gamma is None or one_launch) else gamma * rstd
         cl = torch.channels_last
         if not (gy.dtype == torch.bfloat16 and gy.is_contiguous(memory_format=cl)):
             gy = gy.to(torch.bfloat16).contiguous(memory_format=cl)
         g, gb = ext.bias_act_bwd_nhwc(gy, y, relu=relu)
-        need = ctx.needs_input_grad
         gx, gw, _ = torch.ops.aten.convolution_backward(g, x16, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
                                                         (bool(need[0]), bool(need[1] or need[2]), False))
         dW = dgamma = dbeta = dcb = None
-        if gw is not None and one_launch and need[1] and need[2]:
-            dW, dgamma = ext.conv_bn_fold_bwd(gw, weight, gamma, rstd, mean_rstd, gb)    # the fold's chain rule: one launch
+        if gw is not None and one_launch:
+            # the fold's chain rule, one launch, makes dW and dgamma together; a mask that wants one of them (frozen BatchNorm
+            # affine parameters, frozen convolution weights) takes the same launch and drops the other: the same bits as under
+            # the full mask
+            dW, dgamma = ext.conv_bn_fold_bwd(gw, weight, gamma, rstd, mean_rstd, gb)
+            if not need[1]:
+                dW = None
+            if not need[2]:
+                dgamma = None
         elif gw is not None:
             gwf = gw.float()
             if s is not None:
@@ -222,6 +229,7 @@ class ResNet(BaseModule):
         assert style == 'pytorch'
         self.depth, self.num_stages = depth, num_stages
         self.out_indices, self.frozen_stages, self.norm_eval = out_indices, frozen_stages, norm_eval
+        self.norm_requires_grad = bool(dict(norm_cfg or {}).get('requires_grad', True))
         self.conv1 = nn.Conv2d(in_channels, base_channels, 7, stride=2, padding=3, bias=False)
         self.bn1 = nn.BatchNorm2d(base_channels)
         self.relu = nn.ReLU(inplace=True)
@@ -242,6 +250,11 @@ class ResNet(BaseModule):
             name = f'layer{i + 1}'
             self.add_module(name, nn.Sequential(*blocks))
             self.res_layers.append(name)
+        if not self.norm_requires_grad:     # norm_cfg=dict(type='BN', requires_grad=False): frozen affine parameters
+            for m in self.modules():
+                if isinstance(m, nn.BatchNorm2d):
+                    for p_ in m.parameters():
+                        p_.requires_grad = False
         self._freeze_stages()
 
     def _freeze_stages(self):

@@ -267,8 +267,9 @@ def test_rows_gather_sum_matches_torch_index_ops_and_gradient():
     y = ext.RowsGatherSumFunction.apply(xd, r2q.cuda(), q2r.cuda())
     y.backward(go.cuda())
     torch.cuda.synchronize()
-    assert float((y.detach().cpu().double() - yr.detach()).abs().max()) == 0.0          # a copy
-    assert float((xd.grad.cpu().double() - xr.grad).abs().max()) < 1e-5
+    from tests.grad_bounds import ROWS_GATHER_GRAD_ABS, ROWS_GATHER_OUT_ABS
+    assert float((y.detach().cpu().double() - yr.detach()).abs().max()) == ROWS_GATHER_OUT_ABS          # a copy
+    assert float((xd.grad.cpu().double() - xr.grad).abs().max()) < ROWS_GATHER_GRAD_ABS
     # the other direction: scatter-back = gather-sum over the inverse map
     o = torch.randn(2, nc * max_len, F, generator=g)
     s_ref = torch.zeros(2, Q, F, dtype=torch.double).index_add_(1, r2q[:, 0].clamp(min=0), o.double() * valid)
@@ -320,7 +321,8 @@ def test_sca_prep_function_matches_torch_ops_and_gradient():
     e_att = float((att_d.detach().cpu().double() - att.detach()).abs().max())
     e_g = float((pd.grad.cpu().double() - pr.grad).abs().max() / pr.grad.abs().max())
     print(f"sca_prep: loc {e_loc:.2e} attn {e_att:.2e} grad rel {e_g:.2e}")
-    assert e_loc < 1e-5 and e_att < 1e-6 and e_g < 1e-5
+    from tests.grad_bounds import SCA_PREP_ATTN_ABS, SCA_PREP_GRAD_REL, SCA_PREP_LOC_ABS
+    assert e_loc < SCA_PREP_LOC_ABS and e_att < SCA_PREP_ATTN_ABS and e_g < SCA_PREP_GRAD_REL
 
 
 def test_data_copy_before_eval_is_caught_by_the_content_fingerprint():
@@ -411,6 +413,7 @@ def test_dropout_add_layernorm_node_matches_torch(rows, p, monkeypatch):
     import ctypes
     import numpy as np
     from occnet_amd import _lib, ext
+    from tests.grad_bounds import DROPOUT_LN_REL
     g = torch.Generator().manual_seed(rows)
     C = 256
     x0 = torch.randn(2, rows, C, generator=g).cuda()
@@ -451,7 +454,7 @@ def test_dropout_add_layernorm_node_matches_torch(rows, p, monkeypatch):
     want = [yr.detach(), x.grad, r.grad, ln.weight.grad, ln.bias.grad]
     for a, b, name in zip(got, want, ("y", "gx", "gres", "dgamma", "dbeta")):
         err = float((a - b).abs().max() / (b.abs().max() + 1e-12))
-        assert err < 2e-5, (name, err)
+        assert err < DROPOUT_LN_REL, (name, err)
 
 
 def test_layer_with_the_fused_tail_matches_the_aten_tail(monkeypatch):
