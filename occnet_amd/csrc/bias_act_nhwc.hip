@@ -10,7 +10,6 @@
 
 namespace occ {
 
-__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 __global__ __launch_bounds__(256) void bias_act_nhwc_bf16_kernel(
     uint4* __restrict__ x, const float* __restrict__ bias, const uint4* __restrict__ residual, long n_vec,
     int C, int relu) {

@@ -27,9 +27,6 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kBnTH = 8, kBnTW = 16, kBnHH = 10, kBnHW = 18, kBnNP = kBnHH * kBnHW;   // 180 halo pixels
 constexpr int kBnXS = 80;                    // bytes per x-chunk pixel slot (32 bf16 + 16 pad)
 constexpr int kBnXA = 192 * kBnXS;           // one x chunk buffer (6 row tiles of 32 halo pixels)
@@ -38,9 +35,6 @@ constexpr int kBnH1ROW = kBnHW * kBnMS;      // 2592
 constexpr int kBnH1 = kBnHH * kBnH1ROW;      // 25 920
 constexpr int kBnC2 = 128 * kBnMS;           // 18 432
 constexpr int kBnOLD = 256 + 4;              // epilogue transpose row stride (floats)
-
-__device__ __forceinline__ float bn_bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-__device__ __forceinline__ unsigned short bn_f32_to_bf16(float f) { return bf16_rne(f); }
 
 // f32 row-major weight (N, K) -> bf16 MFMA B-fragment order: packed[((ks * N/32 + nt) * 64 + lane) * 8 + j]
 // = w[nt*32 + (lane & 31)][ks*16 + (lane >> 5)*8 + j]   (v_mfma_f32_32x32x16_bf16 operand of lane `lane`)
@@ -54,7 +48,7 @@ __global__ void mfma_pack_b_frag_kernel(const float* __restrict__ w, unsigned sh
   const int nts = N / 32;
   const int nt = (int)(rest % nts), ks = (int)(rest / nts);
   const int n = nt * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8 + j;
-  packed[idx] = bn_f32_to_bf16(w[(long)n * K + k]);
+  packed[idx] = bf16_rne(w[(long)n * K + k]);
 }
 
 template <int CIN, bool DS>
@@ -318,10 +312,10 @@ __global__ __launch_bounds__(256, 2) void bottleneck64_nhwc_bf16_kernel(
       const int oy = y0 + 2 * rt + (row >> 4), ox = x0 + (row & 15);
       if (oy < H && ox < W) {
         float4 v = *reinterpret_cast<const float4*>(sO + row * kBnOLD + c);
-        v.x += bv.x + bn_bf16_to_f32((unsigned short)(rv[rr].x & 0xffffu));
-        v.y += bv.y + bn_bf16_to_f32((unsigned short)(rv[rr].x >> 16));
-        v.z += bv.z + bn_bf16_to_f32((unsigned short)(rv[rr].y & 0xffffu));
-        v.w += bv.w + bn_bf16_to_f32((unsigned short)(rv[rr].y >> 16));
+        v.x += bv.x + bf16_to_f32((unsigned short)(rv[rr].x & 0xffffu));
+        v.y += bv.y + bf16_to_f32((unsigned short)(rv[rr].x >> 16));
+        v.z += bv.z + bf16_to_f32((unsigned short)(rv[rr].y & 0xffffu));
+        v.w += bv.w + bf16_to_f32((unsigned short)(rv[rr].y >> 16));
         v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         const uint2 o = make_uint2(pack_bf16x2_rne(v.x, v.y), pack_bf16x2_rne(v.z, v.w));
         *reinterpret_cast<uint2*>(out + (((long)img * H + oy) * W + ox) * 256 + c) = o;

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include "../../include/occnet_amd.h"
 
 namespace occ {
@@ -100,6 +101,61 @@ __device__ __forceinline__ unsigned pack_bf16x2_rne(float lo, float hi) {
 }
 __device__ __forceinline__ unsigned short bf16_rne(float f) {
   return (unsigned short)(pack_bf16x2_rne(f, 0.f) & 0xffffu);
+}
+
+// bf16 -> f32 is a shift: of one value, and of the low / high half of a packed word
+__device__ __forceinline__ float bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
+__device__ __forceinline__ float bf16_lo_to_f32(unsigned v) { return __uint_as_float(v << 16); }
+__device__ __forceinline__ float bf16_hi_to_f32(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
+
+// The bf16x3 operand split: x = hi + lo to 16 mantissa bits (hi = rne(x), lo = rne(x - hi)), so that
+// a.b ~= al.bh + ah.bl + ah.bh on the bf16 matrix cores with f32 accumulation (product error <= 2^-16).
+__device__ __forceinline__ void bf16_split(float x, unsigned short& hi, unsigned short& lo) {
+  hi = bf16_rne(x);
+  lo = bf16_rne(x - bf16_to_f32(hi));
+}
+// two values at once: hi pair = cvt_pk(x0, x1), lo pair = cvt_pk(x0 - hi0, x1 - hi1)   (6 VALU ops per pair)
+__device__ __forceinline__ void bf16_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
+  hi = pack_bf16x2_rne(x0, x1);
+  lo = pack_bf16x2_rne(x0 - bf16_lo_to_f32(hi), x1 - bf16_hi_to_f32(hi));
+}
+
+// Vector types of the matrix-core kernels: MFMA accumulator tile, bf16 operand fragment, packed 16-bit pair, and the LDS
+// pointer that the direct-to-LDS loads take.
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+typedef unsigned occ_u32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+
+// Sum over the 64 lanes of a wave (xor butterfly: every lane ends with the total).
+__device__ __forceinline__ float wave_sum(float v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+  return v;
+}
+
+// Running max of |x| over two packed bf16 / fp16 values, as bit patterns (sign cleared, unsigned compare): v_and + v_pk_max_u16
+__device__ __forceinline__ unsigned absmax_pk2(unsigned m, unsigned x) {
+  const u16x2 a = __builtin_bit_cast(u16x2, m), b = __builtin_bit_cast(u16x2, x & 0x7fff7fffu);
+  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(a, b));
+}
+
+// torch.nn.Softplus(beta=1, threshold=20) = max(x, 0) + log(1 + exp(-|x|)), branch-free on the two transcendental
+// instructions (v_exp_f32 / v_log_f32 on an argument in (1, 2]: ~1e-7 absolute).  Above the threshold exp(-x) < 2.1e-9 is below
+// half an ulp of x, 1 + e rounds to 1 and the expression returns x itself — what torch's cut-off returns.  (As
+// `x > 20 ? x : ... __logf(...)` hipcc emitted an exec-mask branch and a 12-instruction refined logarithm per element: the heads
+// phase of the fused decoder kernel is VALU-bound.)
+__device__ __forceinline__ float softplus(float x) {
+  const float e = __builtin_amdgcn_exp2f(fabsf(x) * -1.44269504088896341f);
+  return fmaxf(x, 0.f) + __builtin_amdgcn_logf(1.f + e) * 0.693147180559945309f;
+}
+
+// Host side: an environment switch that is ON unless the variable starts with '0'.  Callers keep the result in a
+// function-local `static const bool`, so a switch is read once, at the first launch that consults it.
+inline bool env_default_on(const char* name) {
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
 }
 
 // fp32 quotient WITHOUT the IEEE division expansion.  hipcc turns `a / d` into v_div_scale_f32 (x2, one writes VCC) /
@@ -200,8 +256,6 @@ __device__ __forceinline__ int bilinear_setup_b(float loc_x, float loc_y, float 
   sp.w[3] = t.c[3] ? t.lh * t.lw * attn : 0.f; sp.o[3] = t.c[3] ? (unsigned)(base + W + 1) * pix_bytes : dead;
   return t.c[0] + t.c[1] + t.c[2] + t.c[3];
 }
-
-typedef unsigned occ_u32x4 __attribute__((ext_vector_type(4)));
 
 // Buffer descriptor over `bytes` bytes at `base`, built from PROVABLY wave-uniform words: anything derived from
 // threadIdx — even the wave id — is divergent to hipcc, which then wraps every buffer load in a waterfall loop

@@ -20,12 +20,6 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-
-__device__ __forceinline__ float c1_bf16_to_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
-
 template <int NT, int RT>
 __global__ __launch_bounds__(256) void conv1x1_nhwc_bf16_kernel(
     const uint4* __restrict__ x, const uint4* __restrict__ w, const float* __restrict__ bias,
@@ -186,10 +180,10 @@ __global__ __launch_bounds__(256) void conv1x1_nhwc_bf16_kernel(
       if (m < M && col_live) {
         float4 v = *reinterpret_cast<const float4*>(sO + row * OLD + c);
         v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-        v.x += c1_bf16_to_f32((unsigned short)(rv[rr].x & 0xffffu));
-        v.y += c1_bf16_to_f32((unsigned short)(rv[rr].x >> 16));
-        v.z += c1_bf16_to_f32((unsigned short)(rv[rr].y & 0xffffu));
-        v.w += c1_bf16_to_f32((unsigned short)(rv[rr].y >> 16));
+        v.x += bf16_to_f32((unsigned short)(rv[rr].x & 0xffffu));
+        v.y += bf16_to_f32((unsigned short)(rv[rr].x >> 16));
+        v.z += bf16_to_f32((unsigned short)(rv[rr].y & 0xffffu));
+        v.w += bf16_to_f32((unsigned short)(rv[rr].y >> 16));
         if (relu) {
           v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
         }
@@ -232,7 +226,7 @@ static int conv1x1_nhwc_bf16_launch(const void* x, const void* weight, const flo
   const long in_pixels = (long)batch * Hin * Win;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   // OCC_CONV1X1_RESIDENT=0 (development switch, read once) keeps every default launch on the tiled kernel
-  static const bool resident_on = [] { const char* e = getenv("OCC_CONV1X1_RESIDENT"); return !(e && e[0] == '0'); }();
+  static const bool resident_on = env_default_on("OCC_CONV1X1_RESIDENT");
   int rt = 0, ncb_force = 0;
   if (variant == 0) {
     // the resident kernel wherever it exists: every shape of the ResNet-50 / FPN table it covers measured faster than

@@ -28,14 +28,7 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void* c1r_lds_ptr_t;
-
 constexpr int kC1rPitch = 80, kC1rScratch = 32 * kC1rPitch;     // per-wave epilogue scratch: 32 rows x 64 B, padded
-
-__device__ __forceinline__ float c1r_lo(unsigned v) { return __uint_as_float(v << 16); }
-__device__ __forceinline__ float c1r_hi(unsigned v) { return __uint_as_float(v & 0xffff0000u); }
 
 // LDS: activation tile + the four waves' scratch + the bias of the block's columns
 // output pixel m = (n, yo, xo) of a (Hout, Wout) map -> pixel (n, yo / 2, xo / 2) of the map of half the resolution
@@ -88,7 +81,7 @@ __global__ __launch_bounds__(256, MINB) void conv1x1_resident_kernel(
       const unsigned yo = rem / (unsigned)Wout, xo = rem - yo * (unsigned)Wout;
       pix = (int)((n * (unsigned)Hin + yo * (unsigned)stride) * (unsigned)Win + xo * (unsigned)stride);
     }
-    __builtin_amdgcn_global_load_lds(x + (long)pix * PCS + (slot ^ (r & MASK)), (c1r_lds_ptr_t)(clds + inst * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(x + (long)pix * PCS + (slot ^ (r & MASK)), (lds_ptr_t)(clds + inst * 1024), 16, 0, 0);
   }
 
   // weight ring: slot (step & 3) = the wave's NTW column tiles of flat step = pass * KS + k-step (buffer loads: one
@@ -225,7 +218,7 @@ __global__ __launch_bounds__(256, MINB) void conv1x1_resident_kernel(
                 v3 = acc[rt][t][4 * q + 3];
           if (RES) {
             const uint2 r = *reinterpret_cast<const uint2*>(sp);
-            v0 += c1r_lo(r.x); v1 += c1r_hi(r.x); v2 += c1r_lo(r.y); v3 += c1r_hi(r.y);
+            v0 += bf16_lo_to_f32(r.x); v1 += bf16_hi_to_f32(r.x); v2 += bf16_lo_to_f32(r.y); v3 += bf16_hi_to_f32(r.y);
           }
           if (relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
           *reinterpret_cast<uint2*>(sp) = make_uint2(pack_bf16x2_rne(v0, v1), pack_bf16x2_rne(v2, v3));

@@ -18,11 +18,9 @@
 // CH/2 contiguous floats of ONE voxel and its B fragment CH/2 contiguous floats of the packed weight.
 // Zero padding of the convolution = zero-filled halo slots.  Epilogue: y = relu(acc*scale + shift)
 // with the eval-mode BatchNorm folded into (scale, shift) per output channel, 128-byte rows per voxel.
-#include "common.h"
+#include "heads_x3.h"
 
 namespace occ {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <int Z, int CH, int TY, int TX>
 struct ConvGeom {
@@ -40,6 +38,25 @@ struct ConvGeom {
   static constexpr int TXG = TX / PX;                        // row tiles per pillar row
 };
 
+// XCD-aware tile order: hardware block b runs on XCD b % 8, each with a private L2.  Dealt linearly, the eight tiles
+// of a row segment land on eight different L2s and every XCD fetches its own copy of the shared halos (PMC, round 2:
+// 306 MB read for an 82 MB input).  Here XCD x walks the contiguous tile range [x*q + min(x, r), ...) — neighbours in
+// space are neighbours in time on ONE L2 (bijective for any grid size: q = n / 8, r = n % 8).  The block's tile is batch
+// entry b, pillars (y0.., x0..).
+struct ConvTile { int b, y0, x0; };
+template <int TY, int TX>
+__device__ __forceinline__ ConvTile conv_tile_of_block(int tiles_x, int tiles_y) {
+  int bid;
+  {
+    const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
+    bid = x * q + (x < r ? x : r) + j;
+  }
+  const int tx_i = bid % tiles_x;
+  bid /= tiles_x;
+  const int ty_i = bid % tiles_y;
+  return {bid / tiles_y, ty_i * TY, tx_i * TX};
+}
+
 // LAYOUT 0: in[b][y][x][z][Cin]          (channels innermost: output layout of this kernel)
 // LAYOUT 1: in[b][y][x][Cin][Z]          (lifter view of the BEV embedding: c = ci*Z + z)
 template <int Z, int CH, int TY, int TX, int LAYOUT>
@@ -51,20 +68,8 @@ __global__ __launch_bounds__(256) void conv3d_mfma_kernel(
   constexpr int VS = G::VS, PS = G::PS, HX = G::HX, HY = G::HY, NACC = G::NACC, H2 = CH / 2;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware tile order: hardware block b runs on XCD b % 8, each with a private L2.  Dealt linearly, the eight tiles
-  // of a row segment land on eight different L2s and every XCD fetches its own copy of the shared halos (PMC, round 2:
-  // 306 MB read for an 82 MB input).  Here XCD x walks the contiguous tile range [x*q + min(x, r), ...) — neighbours in
-  // space are neighbours in time on ONE L2 (bijective for any grid size: q = n / 8, r = n % 8).
-  int bid;
-  {
-    const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
-    bid = x * q + (x < r ? x : r) + j;
-  }
-  const int tx_i = bid % tiles_x;
-  bid /= tiles_x;
-  const int ty_i = bid % tiles_y;
-  const int b = bid / tiles_y;
-  const int y0 = ty_i * TY, x0 = tx_i * TX;
+  const ConvTile tile = conv_tile_of_block<TY, TX>(tiles_x, tiles_y);
+  const int b = tile.b, y0 = tile.y0, x0 = tile.x0;
   const float* inb = in + (long)b * Y * X * Z * Cin;
 
   // z-halo slots (z = -1 and z = Z) of every halo pillar stay zero for all phases
@@ -213,8 +218,6 @@ __global__ void conv3d_pack_weight_kernel(const float* __restrict__ w, float* __
 // [16 hi | 16 lo] bf16 + 16 B pad = the same 80 bytes as the f32 kernel's 16 + 4 floats, so the LDS geometry and
 // its conflict-free ds_read_b128 pattern carry over; lanes 0-31 / 32-63 supply channels 0-7 / 8-15 of a voxel.
 // Weights: packed[phase][tap][hi, lo][k half][co][8] bf16 — one 16-byte load per lane, plane and tap.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __global__ void conv3d_pack_weight_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ packed,
                                                  int Cin) {
   const int n = 32 * Cin * 27;                                 // one (hi, lo) pair per thread
@@ -228,8 +231,8 @@ __global__ void conv3d_pack_weight_bf16x3_kernel(const float* __restrict__ w, un
   const int p = r / 27;
   const int ci = p * 16 + kh * 8 + j;
   const float x = w[((long)co * Cin + ci) * 27 + t];
-  const unsigned short hi = bf16_rne(x);
-  const unsigned short lo = bf16_rne(x - __uint_as_float((unsigned)hi << 16));
+  unsigned short hi, lo;
+  bf16_split(x, hi, lo);
   const long base = (((long)(p * 27 + t) * 2) * 2 + kh) * 32 * 8 + co * 8 + j;     // plane 0 (hi)
   packed[base] = hi;
   packed[base + 2 * 32 * 8] = lo;                                                    // plane 1 (lo)
@@ -310,20 +313,8 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(
   constexpr int VSB = G::VS * 4, PSB = G::PS * 4, HX = G::HX, HY = G::HY, NACC = G::NACC;   // bytes
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // XCD-aware tile order: hardware block b runs on XCD b % 8, each with a private L2.  Dealt linearly, the eight tiles
-  // of a row segment land on eight different L2s and every XCD fetches its own copy of the shared halos (PMC, round 2:
-  // 306 MB read for an 82 MB input).  Here XCD x walks the contiguous tile range [x*q + min(x, r), ...) — neighbours in
-  // space are neighbours in time on ONE L2 (bijective for any grid size: q = n / 8, r = n % 8).
-  int bid;
-  {
-    const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
-    bid = x * q + (x < r ? x : r) + j;
-  }
-  const int tx_i = bid % tiles_x;
-  bid /= tiles_x;
-  const int ty_i = bid % tiles_y;
-  const int b = bid / tiles_y;
-  const int y0 = ty_i * TY, x0 = tx_i * TX;
+  const ConvTile tile = conv_tile_of_block<TY, TX>(tiles_x, tiles_y);
+  const int b = tile.b, y0 = tile.y0, x0 = tile.x0;
   const float* inb = in + (long)b * Y * X * Z * Cin;
 
   // z-halo slots (z = -1 and z = Z) of every halo pillar stay zero for all phases
@@ -382,11 +373,9 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(
         const int idx = tid + it * 256;
         const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
         if (idx < ITEMS) {
-          const unsigned h01 = pack_bf16x2_rne(v[it].x, v[it].y), h23 = pack_bf16x2_rne(v[it].z, v[it].w);
-          const unsigned l01 = pack_bf16x2_rne(v[it].x - __uint_as_float(h01 << 16),
-                                               v[it].y - __uint_as_float(h01 & 0xffff0000u));
-          const unsigned l23 = pack_bf16x2_rne(v[it].z - __uint_as_float(h23 << 16),
-                                               v[it].w - __uint_as_float(h23 & 0xffff0000u));
+          unsigned h01, h23, l01, l23;
+          bf16_split2(v[it].x, v[it].y, h01, l01);
+          bf16_split2(v[it].z, v[it].w, h23, l23);
           char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;
           *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
           *reinterpret_cast<uint2*>(d + 32) = make_uint2(l01, l23);
@@ -414,8 +403,8 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(
           char* d = ldsb + pil * PSB + (z4 * 4 + 1) * VSB + ci * 2;
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            const unsigned short hi = bf16_rne(f[q]);
-            const unsigned short lo = bf16_rne(f[q] - __uint_as_float((unsigned)hi << 16));
+            unsigned short hi, lo;
+            bf16_split(f[q], hi, lo);
             *reinterpret_cast<unsigned short*>(d + q * VSB) = hi;
             *reinterpret_cast<unsigned short*>(d + q * VSB + 32) = lo;
           }
@@ -466,8 +455,8 @@ __global__ void conv3d_pack_weight_bf16x3_c8_kernel(const float* __restrict__ w,
   const int s = r / 2;
   const int t = 2 * s + kh;
   const float x = t < 27 ? w[((long)co * 8 + j) * 27 + t] : 0.f;
-  const unsigned short hi = bf16_rne(x);
-  const unsigned short lo = bf16_rne(x - __uint_as_float((unsigned)hi << 16));
+  unsigned short hi, lo;
+  bf16_split(x, hi, lo);
   const long base = (((long)s * 2) * 2 + kh) * 32 * 8 + co * 8 + j;                 // plane 0 (hi)
   packed[base] = hi;
   packed[base + 2 * 32 * 8] = lo;                                                    // plane 1 (lo)
@@ -483,16 +472,8 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_c8_kernel(
   constexpr int VSB = G::VS * 4, PSB = G::PS * 4, HX = G::HX, HY = G::HY, NACC = G::NACC;   // bytes
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int bid;                                    // XCD-aware tile order (see conv3d_bf16x3_kernel)
-  {
-    const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
-    bid = x * q + (x < r ? x : r) + j;
-  }
-  const int tx_i = bid % tiles_x;
-  bid /= tiles_x;
-  const int ty_i = bid % tiles_y;
-  const int b = bid / tiles_y;
-  const int y0 = ty_i * TY, x0 = tx_i * TX;
+  const ConvTile tile = conv_tile_of_block<TY, TX>(tiles_x, tiles_y);
+  const int b = tile.b, y0 = tile.y0, x0 = tile.x0;
   const float* inb = in + (long)b * Y * X * Z * Cin;
   // weight ring: 14 steps x (hi, lo) x 1 KB, requested three steps ahead (see conv_taps27)
   occ_u32x4 w[4][2];
@@ -530,9 +511,9 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_c8_kernel(
       const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
       if (idx < ITEMS) {
         const float4 u = v[it];
-        const unsigned h01 = pack_bf16x2_rne(u.x, u.y), h23 = pack_bf16x2_rne(u.z, u.w);
-        const unsigned l01 = pack_bf16x2_rne(u.x - __uint_as_float(h01 << 16), u.y - __uint_as_float(h01 & 0xffff0000u));
-        const unsigned l23 = pack_bf16x2_rne(u.z - __uint_as_float(h23 << 16), u.w - __uint_as_float(h23 & 0xffff0000u));
+        unsigned h01, h23, l01, l23;
+        bf16_split2(u.x, u.y, h01, l01);
+        bf16_split2(u.z, u.w, h23, l23);
         char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;
         *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
         *reinterpret_cast<uint2*>(d + 16) = make_uint2(l01, l23);
@@ -559,8 +540,8 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_c8_kernel(
         char* d = ldsb + pil * PSB + (z4 * 4 + 1) * VSB + ci * 2;
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
-          const unsigned short hi = bf16_rne(f[q]);
-          const unsigned short lo = bf16_rne(f[q] - __uint_as_float((unsigned)hi << 16));
+          unsigned short hi, lo;
+          bf16_split(f[q], hi, lo);
           *reinterpret_cast<unsigned short*>(d + q * VSB) = hi;
           *reinterpret_cast<unsigned short*>(d + q * VSB + 16) = lo;
         }
@@ -744,22 +725,8 @@ static int launch_conv(const float* in, const float* wp, const float* scale, con
 // ReLU its registers 0-7 and 8-15, split into hi / lo bf16, ARE the two k-steps of the heads' first contraction
 // (k-slot j of lane half g = channel 16 s + 8 (j / 4) + 4 g + j % 4, the order the W1cat fragments are packed in) — no
 // LDS transpose, no HBM round trip.  The heads' fragments (32 KB, packed once by conv3d_heads_pack_kernel) replace the
-// halo in LDS once the taps are done; the rest is occ_heads_x3_kernel's body (csrc/occ_heads.hip) per 32-voxel tile.
+// halo in LDS once the taps are done; the rest is heads_tile (csrc/heads_x3.h, shared with occ_heads_x3_kernel) per 32-voxel tile.
 constexpr int kHeadsPackBytes = 16 * 1024 + 16 * 1024 + 128 * 4 + 32 * 4;
-
-// torch.nn.Softplus(beta=1, threshold=20) = max(x, 0) + log(1 + exp(-|x|)), branch-free on the two transcendental
-// instructions (v_exp_f32 / v_log_f32 on an argument in (1, 2]: ~1e-7 absolute).  Above the threshold exp(-x) < 2.1e-9 is below
-// half an ulp of x, 1 + e rounds to 1 and the expression returns x itself — what torch's cut-off returns.  (As
-// `x > 20 ? x : ... __logf(...)` hipcc emitted an exec-mask branch and a 12-instruction refined logarithm per element: the heads
-// phase of the fused kernel is VALU-bound.)
-__device__ __forceinline__ float cvh_softplus(float x) {
-  const float e = __builtin_amdgcn_exp2f(fabsf(x) * -1.44269504088896341f);
-  return fmaxf(x, 0.f) + __builtin_amdgcn_logf(1.f + e) * 0.693147180559945309f;
-}
-__device__ __forceinline__ void cvh_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
-  hi = pack_bf16x2_rne(x0, x1);
-  lo = pack_bf16x2_rne(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
-}
 
 // [W1cat fragments [(a*2 + s)*2 + plane][lane][8] | W2cat fragments [(kk*2 + plane)][lane][8] | b1 (128 f32) | b2 (32 f32)]
 __global__ void conv3d_heads_pack_kernel(const float* __restrict__ w1o, const float* __restrict__ b1o,
@@ -767,31 +734,10 @@ __global__ void conv3d_heads_pack_kernel(const float* __restrict__ w1o, const fl
                                          const float* __restrict__ w1f, const float* __restrict__ b1f,
                                          const float* __restrict__ w2f, const float* __restrict__ b2f,
                                          unsigned short* __restrict__ packed, int ncls) {
-  constexpr int C = 32, HID = 64;
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
-  if (e < 4096) {
-    const int j = e & 7, l = (e >> 3) & 63, f = e >> 9;
-    const int m = l & 31, gg = l >> 5;
-    {   // W1cat: f = a*2 + s; k-slot (s, gg, j) stands for channel 16 s + 8 (j / 4) + 4 gg + j % 4 (the D-register order)
-      const int a = f >> 1, sk = f & 1, u = 32 * a + m, k = 16 * sk + 8 * (j >> 2) + 4 * gg + (j & 3);
-      const float w = u < HID ? w1o[u * C + k] : w1f[(u - HID) * C + k];
-      const unsigned short hi = bf16_rne(w), lo = bf16_rne(w - __uint_as_float((unsigned)hi << 16));
-      packed[((f * 2 + 0) * 64 + l) * 8 + j] = hi;
-      packed[((f * 2 + 1) * 64 + l) * 8 + j] = lo;
-    }
-    {   // W2cat: f = kk = 2a + ks; output row m, hidden unit u (occ_heads_x3_kernel's layout)
-      const int a = f >> 1, ks = f & 1, u = 32 * a + 16 * ks + 8 * (j >> 2) + 4 * gg + (j & 3);
-      float w = 0.f;
-      if (m < ncls) { if (u < HID) w = w2o[m * HID + u]; }
-      else if (m < ncls + 2) { if (u >= HID) w = w2f[(m - ncls) * HID + (u - HID)]; }
-      const unsigned short hi = bf16_rne(w), lo = bf16_rne(w - __uint_as_float((unsigned)hi << 16));
-      packed[8192 + ((f * 2 + 0) * 64 + l) * 8 + j] = hi;
-      packed[8192 + ((f * 2 + 1) * 64 + l) * 8 + j] = lo;
-    }
-  }
+  if (e < 4096) heads_pack_weights<true>(e, w1o, w2o, w1f, w2f, ncls, packed, packed + 8192);
   float* bp = reinterpret_cast<float*>(packed + 16384);
-  if (e < 128) bp[e] = e < HID ? b1o[e] : b1f[e - HID];
-  if (e < 32) bp[128 + e] = e < ncls ? b2o[e] : (e < ncls + 2 ? b2f[e - ncls] : 0.f);
+  heads_pack_bias(e, b1o, b2o, b1f, b2f, ncls, bp, bp + 128);
 }
 
 // NCLS: the class count as a compile-time constant (17: the reference's heads) or 0 = the run-time `ncls`
@@ -806,16 +752,8 @@ __global__ __launch_bounds__(256) void conv3d_heads_x3_kernel(
   static_assert(G::LDS_FLOATS * 4 >= kHeadsPackBytes + 4 * 32 * 33 * 4, "the heads' fragments + transposes overlay the halo");
   extern __shared__ __attribute__((aligned(16))) char ldsb[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  int bid;                                    // XCD-aware tile order (see conv3d_bf16x3_kernel)
-  {
-    const int n = (int)gridDim.x, q = n >> 3, r = n & 7, x = (int)blockIdx.x & 7, j = (int)blockIdx.x >> 3;
-    bid = x * q + (x < r ? x : r) + j;
-  }
-  const int tx_i = bid % tiles_x;
-  bid /= tiles_x;
-  const int ty_i = bid % tiles_y;
-  const int b = bid / tiles_y;
-  const int y0 = ty_i * TY, x0 = tx_i * TX;
+  const ConvTile tile = conv_tile_of_block<TY, TX>(tiles_x, tiles_y);
+  const int b = tile.b, y0 = tile.y0, x0 = tile.x0;
   const float* inb = in + (long)b * Y * X * Z * Cin;
 
   for (int i = tid; i < HY * HX * 2 * (VSB / 16); i += 256) {          // z-halo slots stay zero
@@ -867,8 +805,8 @@ __global__ __launch_bounds__(256) void conv3d_heads_x3_kernel(
         const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
         if (idx < ITEMS) {
           unsigned h01, h23, l01, l23;
-          cvh_split2(v[it].x, v[it].y, h01, l01);
-          cvh_split2(v[it].z, v[it].w, h23, l23);
+          bf16_split2(v[it].x, v[it].y, h01, l01);
+          bf16_split2(v[it].z, v[it].w, h23, l23);
           char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;
           *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
           *reinterpret_cast<uint2*>(d + 32) = make_uint2(l01, l23);
@@ -910,66 +848,11 @@ __global__ __launch_bounds__(256) void conv3d_heads_x3_kernel(
       }
 #pragma unroll
       for (int s2 = 0; s2 < 2; ++s2) {
-        cvh_split2(f[8 * s2 + 0], f[8 * s2 + 1], xh[s2].x, xl[s2].x); cvh_split2(f[8 * s2 + 2], f[8 * s2 + 3], xh[s2].y, xl[s2].y);
-        cvh_split2(f[8 * s2 + 4], f[8 * s2 + 5], xh[s2].z, xl[s2].z); cvh_split2(f[8 * s2 + 6], f[8 * s2 + 7], xh[s2].w, xl[s2].w);
+        bf16_split2(f[8 * s2 + 0], f[8 * s2 + 1], xh[s2].x, xl[s2].x); bf16_split2(f[8 * s2 + 2], f[8 * s2 + 3], xh[s2].y, xl[s2].y);
+        bf16_split2(f[8 * s2 + 4], f[8 * s2 + 5], xh[s2].z, xl[s2].z); bf16_split2(f[8 * s2 + 6], f[8 * s2 + 7], xh[s2].w, xl[s2].w);
       }
     }
-    f32x16 h[4];
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) h[t][r] = 0.f;
-#pragma unroll
-    for (int s2 = 0; s2 < 2; ++s2) {
-      const bf16x8 bxh = __builtin_bit_cast(bf16x8, xh[s2]), bxl = __builtin_bit_cast(bf16x8, xl[s2]);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) h[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W1[((t * 2 + s2) * 2 + 1) * 64], bxh, h[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) h[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W1[((t * 2 + s2) * 2 + 0) * 64], bxl, h[t], 0, 0, 0);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) h[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W1[((t * 2 + s2) * 2 + 0) * 64], bxh, h[t], 0, 0, 0);
-    }
-    f32x16 o0, o1, o2;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) o0[r] = o1[r] = o2[r] = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      float v[16];
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 bb = *reinterpret_cast<const float4*>(b1s + 32 * t + 8 * q4 + 4 * kh);
-        const float t0 = h[t][4 * q4 + 0] + bb.x, t1 = h[t][4 * q4 + 1] + bb.y;
-        const float t2 = h[t][4 * q4 + 2] + bb.z, t3 = h[t][4 * q4 + 3] + bb.w;
-        if (t < 2) {
-          v[4 * q4 + 0] = cvh_softplus(t0); v[4 * q4 + 1] = cvh_softplus(t1);
-          v[4 * q4 + 2] = cvh_softplus(t2); v[4 * q4 + 3] = cvh_softplus(t3);
-        } else {
-          v[4 * q4 + 0] = fmaxf(t0, 0.f); v[4 * q4 + 1] = fmaxf(t1, 0.f);
-          v[4 * q4 + 2] = fmaxf(t2, 0.f); v[4 * q4 + 3] = fmaxf(t3, 0.f);
-        }
-      }
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        uint4 hh, hl;
-        cvh_split2(v[8 * ks + 0], v[8 * ks + 1], hh.x, hl.x); cvh_split2(v[8 * ks + 2], v[8 * ks + 3], hh.y, hl.y);
-        cvh_split2(v[8 * ks + 4], v[8 * ks + 5], hh.z, hl.z); cvh_split2(v[8 * ks + 6], v[8 * ks + 7], hh.w, hl.w);
-        const int kk = 2 * t + ks;
-        const bf16x8 wh = W2[(kk * 2 + 0) * 64], wl = W2[(kk * 2 + 1) * 64];
-        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wl, __builtin_bit_cast(bf16x8, hh), o0, 0, 0, 0);
-        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, __builtin_bit_cast(bf16x8, hl), o1, 0, 0, 0);
-        o2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wh, __builtin_bit_cast(bf16x8, hh), o2, 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-      const float4 bb = *reinterpret_cast<const float4*>(b2s + 8 * q4 + 4 * kh);
-      const float bq[4] = {bb.x, bb.y, bb.z, bb.w};
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = 4 * q4 + i;
-        sm[vi * 33 + 8 * q4 + 4 * kh + i] = ((o0[r] + o1[r]) + o2[r]) + bq[i];
-      }
-    }
+    heads_tile(xh, xl, W1, W2, b1s, b2s, sm, vi, kh);
     wave_lds_sync();
     // output rows: voxel v of the tile = pillar (gy, gx0 + v / Z), height v % Z; outputs are (B, X, Y, Z, .)
     const int rt = wave * NACC + a;
@@ -994,17 +877,9 @@ __global__ __launch_bounds__(256) void conv3d_heads_x3_kernel(
         const int v = lane >> 1, gx = gx0 + v / Z;
         if (gx < X) flow[((((long)b * X + gx) * Y + gy) * Z + v % Z) * 2 + (lane & 1)] = sm[v * 33 + ncls + (lane & 1)];
       }
-      if (occ_cls != nullptr && lane < 32) {      // decode: argmax of the logits, first index on ties, 0 for a NaN row
-        const int gx = gx0 + lane / Z;
-        float best = sm[lane * 33];
-        int arg = 0;
-        bool nan = best != best;
-        for (int ch = 1; ch < ncls; ++ch) {
-          const float x = sm[lane * 33 + ch];
-          nan |= x != x;
-          if (x > best) { best = x; arg = ch; }
-        }
-        if (gx < X) occ_cls[(((long)b * X + gx) * Y + gy) * Z + lane % Z] = nan ? 0 : arg;
+      if (occ_cls != nullptr && lane < 32) {
+        const int gx = gx0 + lane / Z, cls = heads_argmax(sm, lane, ncls);
+        if (gx < X) occ_cls[(((long)b * X + gx) * Y + gy) * Z + lane % Z] = cls;
       }
     }
     wave_lds_sync();

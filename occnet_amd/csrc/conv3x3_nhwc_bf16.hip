@@ -26,9 +26,6 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kC3TW = 16;                             // output tile width (one MFMA row tile = 2 x 16 pixels)
 constexpr int kC3PX = 80;                             // bytes per halo pixel slot (32 bf16 + 16 pad)
 // Tile geometry per stride S: output tile TH x 16, input halo HH x HW.  Stride 2 keeps the halo columns
@@ -44,14 +41,6 @@ template <int S, int RT_> struct C3Geom {
   static constexpr int ITEMS = HH * HW * 4, NR = (ITEMS + 255) / 256;       // 16-byte staging items / roles
   __device__ static constexpr int slot(int hx) { return S == 1 ? hx : (hx & 1) * 17 + (hx >> 1); }
 };
-
-__device__ __forceinline__ unsigned short c3_f32_to_bf16(float f) { return bf16_rne(f); }
-
-typedef unsigned short c3_u16x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned c3_absmax2(unsigned m, unsigned x) {   // v_and + v_pk_max_u16
-  const c3_u16x2 a = __builtin_bit_cast(c3_u16x2, m), b = __builtin_bit_cast(c3_u16x2, x & 0x7fff7fffu);
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(a, b));
-}
 
 // torch weight (Cout, Cin, 3, 3) f32 -> bf16 in MFMA B-fragment order
 // packed[chunk = ci/32][tap = ky*3+kx][ks = 0,1][Cout/32][lane][8]:  element j of lane `lane` is
@@ -69,7 +58,7 @@ __global__ void conv3x3_pack_weight_kernel(const float* __restrict__ w, unsigned
   const int tap = (int)(r % 9);
   const int chunk = (int)(r / 9);
   const int co = nt * 32 + (lane & 31), ci = chunk * 32 + ks * 16 + (lane >> 5) * 8 + j;
-  packed[idx] = c3_f32_to_bf16(w[((long)co * Cin + ci) * 9 + tap]);
+  packed[idx] = bf16_rne(w[((long)co * Cin + ci) * 9 + tap]);
 }
 
 template <int NT, int S, int PF, int RT_, int MINW>
@@ -252,7 +241,7 @@ __global__ __launch_bounds__(256, MINW) void conv3x3_nhwc_bf16_kernel(
         }
         const uint2 o = make_uint2(pack_bf16x2_rne(v.x, v.y), pack_bf16x2_rne(v.z, v.w));
         *reinterpret_cast<uint2*>(out + (((long)img * Ho + oy) * Wo + ox) * Cout + n0 + c) = o;
-        amax2 = c3_absmax2(c3_absmax2(amax2, o.x), o.y);
+        amax2 = absmax_pk2(absmax_pk2(amax2, o.x), o.y);
       }
     }
   }

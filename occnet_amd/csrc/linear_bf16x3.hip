@@ -23,27 +23,8 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kXBK = 16;          // k per chunk = one 32x32x16 MFMA step
 constexpr int kXLD = 48;          // LDS row stride in BYTES: 16 bf16 (32 B) + 16 B pad
-
-__device__ __forceinline__ unsigned short x3_bf16_rne(float f) { return bf16_rne(f); }
-// two values at once: hi pair = cvt_pk(x0, x1), lo pair = cvt_pk(x0 - hi0, x1 - hi1)   (6 VALU ops per pair)
-__device__ __forceinline__ void x3_split(float x, unsigned short& hi, unsigned short& lo) {
-  hi = x3_bf16_rne(x);
-  lo = x3_bf16_rne(x - __uint_as_float((unsigned)hi << 16));
-}
-__device__ __forceinline__ void x3_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
-  hi = pack_bf16x2_rne(x0, x1);
-  lo = pack_bf16x2_rne(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
-}
-__device__ __forceinline__ float x3_wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 // (N, K) f32 -> packed[K/16][ceil(N/32)][plane: hi, lo][lane][8] bf16 (zero columns beyond N)
 __global__ void linear_pack_weight_bf16x3_kernel(const float* __restrict__ w,
@@ -57,7 +38,7 @@ __global__ void linear_pack_weight_bf16x3_kernel(const float* __restrict__ w,
   const int nt = (int)(rest % nt32), ks = (int)(rest / nt32);
   const int n = nt * 32 + (lane & 31), k = ks * 16 + (lane >> 5) * 8 + j;
   unsigned short hi = 0, lo = 0;
-  if (n < N) x3_split(w[(long)n * K + k], hi, lo);
+  if (n < N) bf16_split(w[(long)n * K + k], hi, lo);
   unsigned short* dst = packed + ((rest * 2) * 64 + lane) * 8 + j;
   dst[0] = hi;
   dst[64 * 8] = lo;
@@ -137,7 +118,7 @@ __global__ __launch_bounds__(256) void linear_bf16x3_kernel(
       const float f2 = ADD ? fmaf(as_##SA, vd_##SA.z, va_##SA.z) : va_##SA.z;                     \
       const float f3 = ADD ? fmaf(as_##SA, vd_##SA.w, va_##SA.w) : va_##SA.w;                     \
       unsigned h01, h23, l01, l23;                                                                \
-      x3_split2(f0, f1, h01, l01); x3_split2(f2, f3, h23, l23);                                   \
+      bf16_split2(f0, f1, h01, l01); bf16_split2(f2, f3, h23, l23);                               \
       *reinterpret_cast<uint2*>(sAh + arow * kXLD + sp * 8) = make_uint2(h01, h23);               \
       *reinterpret_cast<uint2*>(sAl + arow * kXLD + sp * 8) = make_uint2(l01, l23);               \
     }                                                                                             \
@@ -235,9 +216,9 @@ __global__ __launch_bounds__(256) void linear_bf16x3_kernel(
         v.x += rres[rr].x; v.y += rres[rr].y; v.z += rres[rr].z; v.w += rres[rr].w;
       }
       if (ln_g) {                              // LayerNorm over the N columns (N <= BN, one column block)
-        const float mean = x3_wave_sum(col_live ? (v.x + v.y) + (v.z + v.w) : 0.f) * inv_n;
+        const float mean = wave_sum(col_live ? (v.x + v.y) + (v.z + v.w) : 0.f) * inv_n;
         const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-        const float var = x3_wave_sum(col_live ? (dx * dx + dy * dy) + (dz * dz + dw * dw) : 0.f) * inv_n;
+        const float var = wave_sum(col_live ? (dx * dx + dy * dy) + (dz * dz + dw * dw) : 0.f) * inv_n;
         const float rstd = rsqrtf(var + ln_eps);
         v.x = dx * rstd * gv.x + bev.x; v.y = dy * rstd * gv.y + bev.y;
         v.z = dz * rstd * gv.z + bev.z; v.w = dw * rstd * gv.w + bev.w;

@@ -38,9 +38,6 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kChRows = 64;                       // rows per block
 constexpr int kChPlane = kChRows * 512;           // one bf16 plane of the operand tile: 64 rows x 256 k
 constexpr int kChRed = 2 * kChPlane;              // LayerNorm exchange: float[2][4][64]
@@ -69,16 +66,10 @@ struct ChainArgs {
   long long* trace;                               // TRACE builds: 24 wall-clock stamps per wave (development)
 };
 
-// Block barrier that orders LDS traffic only.  __syncthreads() is a full fence: hipcc puts `s_waitcnt vmcnt(0)` in front of
-// the s_barrier, so every barrier after a row-store phase waited for the stores' L2 acknowledgements and for the weight
-// ring's look-ahead (round 4 ISA reading).  Global memory is never shared between the threads of a block here (the one
-// re-read of a block's own stores, x2, is by the lane that wrote it and sits behind an explicit vmcnt(0)).
-__device__ __forceinline__ void ch_sync() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-__device__ __forceinline__ void ch_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
-  hi = pack_bf16x2_rne(x0, x1);
-  lo = pack_bf16x2_rne(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
-}
+// Every block barrier here is block_lds_sync() (common.h), not __syncthreads(): a full fence after a row-store phase waited
+// for the stores' L2 acknowledgements and for the weight ring's look-ahead (round 4 ISA reading).  Global memory is never
+// shared between the threads of a block here (the one re-read of a block's own stores, x2, is by the lane that wrote it and
+// sits behind an explicit vmcnt(0)).
 
 // (N rows of a (N, K) f32 weight) -> chain order: for every 256-row group g: packed[g][K/16][8 tiles][hi | lo][lane][8 bf16]
 // (rows beyond N are zero), i.e. 16 KB per k-step: exactly what one flat ring step of a pass fetches
@@ -96,8 +87,7 @@ __global__ void linear_chain_pack_kernel(const float* __restrict__ w, unsigned s
   unsigned short hi = 0, lo = 0;
   if (n < N) {
     const float x = w[(long)n * K + k];
-    hi = bf16_rne(x);
-    lo = bf16_rne(x - __uint_as_float((unsigned)hi << 16));
+    bf16_split(x, hi, lo);
   }
   unsigned short* dst = packed + ((rest * 2) * 64 + lane) * 8 + j;
   dst[0] = hi;
@@ -285,8 +275,8 @@ __device__ __forceinline__ void ch_to_tile(const f32x16 (&acc)[RT][2], char* tl,
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         unsigned h01, h23, l01, l23;
-        ch_split2(acc[rt][t][4 * q + 0], acc[rt][t][4 * q + 1], h01, l01);
-        ch_split2(acc[rt][t][4 * q + 2], acc[rt][t][4 * q + 3], h23, l23);
+        bf16_split2(acc[rt][t][4 * q + 0], acc[rt][t][4 * q + 1], h01, l01);
+        bf16_split2(acc[rt][t][4 * q + 2], acc[rt][t][4 * q + 3], h23, l23);
         char* p = tl + (rt * 32 + vi) * 512 + (((8 * wave + 4 * t + q) ^ vi) & 31) * 16 + kb * 8;
         *reinterpret_cast<uint2*>(p) = make_uint2(h01, h23);
         *reinterpret_cast<uint2*>(p + kChPlane) = make_uint2(l01, l23);
@@ -309,7 +299,7 @@ __device__ __forceinline__ void ch_layernorm(f32x16 (&acc)[RT][2], float* red, c
     s[rt] = v;
     if (kb == 0) red[wave * kChRows + rt * 32 + vi] = v;
   }
-  ch_sync();          // also: every wave is past its k loop, the operand tile may be rewritten after this point
+  block_lds_sync();          // also: every wave is past its k loop, the operand tile may be rewritten after this point
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int r = rt * 32 + vi;
@@ -326,7 +316,7 @@ __device__ __forceinline__ void ch_layernorm(f32x16 (&acc)[RT][2], float* red, c
     v += __shfl_xor(v, 32);
     if (kb == 0) red[4 * kChRows + wave * kChRows + r] = v;
   }
-  ch_sync();
+  block_lds_sync();
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     const int r = rt * 32 + vi;
@@ -453,14 +443,14 @@ __device__ __forceinline__ void chain_tile(const ChainArgs& p, char* tl, const l
   for (int j = 0; j < 8 * RT; ++j) {                // -> hi / lo planes
     const int row = j * 4 + wave;
     unsigned h01, h23, l01, l23;
-    ch_split2(v[j].x, v[j].y, h01, l01);
-    ch_split2(v[j].z, v[j].w, h23, l23);
+    bf16_split2(v[j].x, v[j].y, h01, l01);
+    bf16_split2(v[j].z, v[j].w, h23, l23);
     char* q = tl + row * 512 + (((lane >> 1) ^ row) & 31) * 16 + (lane & 1) * 8;
     *reinterpret_cast<uint2*>(q) = make_uint2(h01, h23);
     *reinterpret_cast<uint2*>(q + kChPlane) = make_uint2(l01, l23);
   }
   const unsigned abase = (unsigned)(vi * 512 + ((kb ^ vi) & 31) * 16);
-  ch_sync();
+  block_lds_sync();
   OCC_CH_STAMP(1)                                   // first-stage rows landed, tile built
   int step = 0;
   int bias_off = 0;
@@ -476,7 +466,7 @@ __device__ __forceinline__ void chain_tile(const ChainArgs& p, char* tl, const l
     if constexpr (PROG == 0) { OCC_CH_STAMP(5) }
     ch_to_tile(acc, tl, wave, vi, kb);
     if constexpr (PROG == 0) { OCC_CH_STAMP(6) }
-    ch_sync();
+    block_lds_sync();
     OCC_CH_STAMP(3)                                   // LayerNorm, row stores issued, tile rebuilt
   step = 16;
   bias_off = 256;
@@ -498,18 +488,18 @@ __device__ __forceinline__ void chain_tile(const ChainArgs& p, char* tl, const l
     ch_kloop<ABL>(hb, w, wr, wv, 32, (32) + 16, tl, abase, rot, hb, wr, row);
     ch_relu(hb);
     OCC_CH_STAMP(5)
-    ch_sync();                                // every wave has read the x2 tile for the last time
+    block_lds_sync();                                // every wave has read the x2 tile for the last time
     ch_to_tile(ha, tl, wave, vi, kb);
-    ch_sync();
+    block_lds_sync();
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                      // the x2 stores (two k loops ago) have landed
     ch_load_rows(acc, ry, ldy_b, row, wave * 64, kb);                    // x2 (this lane's own stores)
     ch_add_bias(acc, prm + 768 + wave * 64, kb);                         // + b2
     OCC_CH_STAMP(6)                                 // ha in the tile, x2 reloaded
     ch_kloop<ABL>(acc, w, wr, wv, 48, (48) + 16, tl, abase, rot, acc, wr, row);
     OCC_CH_STAMP(7)
-    ch_sync();
+    block_lds_sync();
     ch_to_tile(hb, tl, wave, vi, kb);
-    ch_sync();
+    block_lds_sync();
     OCC_CH_STAMP(8)
     ch_kloop<ABL>(acc, w, wr, wv, 64, (64) + 16, tl, abase, rot, acc, wr, row);
     OCC_CH_STAMP(9)
@@ -520,7 +510,7 @@ __device__ __forceinline__ void chain_tile(const ChainArgs& p, char* tl, const l
     if (p.npass > 0) {
       ch_to_tile(acc, tl, wave, vi, kb);
       OCC_CH_STAMP(17)
-      ch_sync();
+      block_lds_sync();
       OCC_CH_STAMP(10)                              // LayerNorm 2, tile rebuilt
       // tail pass 0 accumulates in `ha` (free by now) while x3 — still in `acc` — leaves one quad per k-step
       const int c0 = wave * 64;
@@ -638,7 +628,7 @@ int chain_launch(const occ::ChainArgs& args_in, hipStream_t st, const char* what
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return 2 * n;
   }();
-  static const bool half_tiles = [] { const char* e = getenv("OCC_CHAIN_HALF_TILES"); return !(e && e[0] == '0'); }();
+  static const bool half_tiles = env_default_on("OCC_CHAIN_HALF_TILES");
   const int n64 = (args.M + kChRows - 1) / kChRows;
   const int rem = n64 % slots;
   args.nfull = (half_tiles && n64 > slots && rem > 0 && 2 * rem <= slots) ? n64 - rem : n64;

@@ -27,15 +27,7 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int kLinBM = 32, kLinBK = 16, kLinLD = 20;
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
 
 template <int NT>
 __global__ __launch_bounds__(256) void linear_mfma_kernel(

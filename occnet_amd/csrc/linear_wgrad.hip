@@ -22,25 +22,16 @@
 
 namespace occ {
 
-typedef float wg_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 wg_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned wg_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void wg_split2(float x0, float x1, unsigned& hi, unsigned& lo) {
-  hi = pack_bf16x2_rne(x0, x1);
-  lo = pack_bf16x2_rne(x0 - __uint_as_float(hi << 16), x1 - __uint_as_float(hi & 0xffff0000u));
-}
-
 // 8 consecutive-m values of one column -> hi / lo fragments
-__device__ __forceinline__ void wg_frag(const float (&v)[8], wg_bf16x8& hi, wg_bf16x8& lo) {
-  wg_u32x4 h, l;
+__device__ __forceinline__ void wg_frag(const float (&v)[8], bf16x8& hi, bf16x8& lo) {
+  occ_u32x4 h, l;
   unsigned a, b;
-  wg_split2(v[0], v[1], a, b); h.x = a; l.x = b;
-  wg_split2(v[2], v[3], a, b); h.y = a; l.y = b;
-  wg_split2(v[4], v[5], a, b); h.z = a; l.z = b;
-  wg_split2(v[6], v[7], a, b); h.w = a; l.w = b;
-  hi = __builtin_bit_cast(wg_bf16x8, h);
-  lo = __builtin_bit_cast(wg_bf16x8, l);
+  bf16_split2(v[0], v[1], a, b); h.x = a; l.x = b;
+  bf16_split2(v[2], v[3], a, b); h.y = a; l.y = b;
+  bf16_split2(v[4], v[5], a, b); h.z = a; l.z = b;
+  bf16_split2(v[6], v[7], a, b); h.w = a; l.w = b;
+  hi = __builtin_bit_cast(bf16x8, h);
+  lo = __builtin_bit_cast(bf16x8, l);
 }
 
 // rows m .. m+15 of this wave's two dY column tiles and two X column tiles -> raw registers.  Rows are clamped to
@@ -71,8 +62,8 @@ __device__ __forceinline__ void wg_load(const float* __restrict__ pa0, const flo
 }
 
 __device__ __forceinline__ void wg_step(const float (&a0)[8], const float (&a1)[8], const float (&b0)[8],
-                                        const float (&b1)[8], wg_f32x16 (&acc)[4], float& s0, float& s1) {
-  wg_bf16x8 ah0, al0, ah1, al1, bh0, bl0, bh1, bl1;
+                                        const float (&b1)[8], f32x16 (&acc)[4], float& s0, float& s1) {
+  bf16x8 ah0, al0, ah1, al1, bh0, bl0, bh1, bl1;
   wg_frag(a0, ah0, al0);
   wg_frag(a1, ah1, al1);
   wg_frag(b0, bh0, bl0);
@@ -115,7 +106,7 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_x3_kernel(
   const float* pb0 = x + (kb0 < K ? kb0 : K - 1);
   const float* pb1 = x + (kb1 < K ? kb1 : K - 1);
 
-  wg_f32x16 acc[4];
+  f32x16 acc[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t)
 #pragma unroll
@@ -190,7 +181,7 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_n32_kernel(
       pb[t] = x + kk;
     }
   }
-  wg_f32x16 acc[2];
+  f32x16 acc[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -215,7 +206,7 @@ __global__ __launch_bounds__(256, 2) void linear_wgrad_n32_kernel(
     }
   };
   auto step = [&](const float (&a)[8], const float (&b0)[8], const float (&b1)[8]) {
-    wg_bf16x8 ah, al, bh0, bl0, bh1, bl1;
+    bf16x8 ah, al, bh0, bl0, bh1, bl1;
     wg_frag(a, ah, al);
     wg_frag(b0, bh0, bl0);
     wg_frag(b1, bh1, bl1);

@@ -24,12 +24,6 @@ __device__ __forceinline__ unsigned ln_hash(unsigned i, unsigned s0, unsigned s1
   return h;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
-  return v;
-}
-
 template <bool DROP>
 __global__ __launch_bounds__(256) void dropout_add_ln_fwd_kernel(
     const float* __restrict__ x, const float* __restrict__ res, const float* __restrict__ gamma,

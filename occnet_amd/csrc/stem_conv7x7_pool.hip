@@ -19,9 +19,6 @@
 
 namespace occ {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int kStP = 8;                        // pooled tile edge
 constexpr int kStC = 2 * kStP + 1;             // conv tile edge (17)
 constexpr int kStI = 2 * kStC + 5;             // input tile edge (39)

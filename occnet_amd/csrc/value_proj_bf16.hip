@@ -39,9 +39,6 @@ __device__ __forceinline__ unsigned vp_sat_half2(float a, float b) {
   return __builtin_bit_cast(unsigned, h);
 }
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 // one launch covers every FPN level: segment l = the (rows_l, K) pixel matrix of level l, whose groups (camera
 // images, rows_per_group_l = h_l*w_l rows each) land at out_row0_l inside the per-camera blocks of the output
 constexpr int kVpMaxSeg = 8;
@@ -238,7 +235,6 @@ __global__ __launch_bounds__(256, 2) void value_proj_bf16_kernel(
 constexpr int kVprRows = 128, kVprK = 256, kVprPitch = 80, kVprScratch = 32 * kVprPitch;
 constexpr int kVprTileBytes = kVprRows * kVprK * 2;
 constexpr int kVprLdsBytes = kVprTileBytes + 4 * kVprScratch;
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
 // OFMT: 0 = fp32 rows, 1 = fp16 pixel pairs, 2 = q16 pixel pairs (block floating point, common.h: 16 bits per element, one
 // 4-bit exponent per 16-byte piece of 8 channels)
@@ -494,7 +490,7 @@ static int value_proj_bf16_launch(int n_segments, const void* const* a, const in
   for (int i = 0; i < n_segments; ++i) total_rows += rows[i];
   // the activation-resident kernel: K = 256, whole 256-column passes, at most two groups per 128-row block, and a
   // plane never split inside a wave's 64 columns.  OCC_VPROJ_RESIDENT=0 (development switch) keeps the tiled kernel.
-  static const bool resident_on = [] { const char* e = getenv("OCC_VPROJ_RESIDENT"); return !(e && e[0] == '0'); }();
+  static const bool resident_on = env_default_on("OCC_VPROJ_RESIDENT");
   bool resident = resident_on && K == kVprK && N % 256 == 0 && plane_cols % 64 == 0 && ldo % 8 == 0 &&
                   (plane_stride == 0 || plane_stride % 8 == 0);
   for (int i = 0; i < n_segments && resident; ++i)

@@ -36,14 +36,8 @@ struct VrSegments {
 };
 constexpr int kVrAmaxWords = 8;       // producer-side maxima are sharded over 8 words (block id & 7): less same-address traffic
 
-typedef unsigned short vr_u16x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ unsigned vr_absmax2(unsigned m, unsigned x) {   // v_and + v_pk_max_u16
-  const vr_u16x2 a = __builtin_bit_cast(vr_u16x2, m), b = __builtin_bit_cast(vr_u16x2, x & 0x7fff7fffu);
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(a, b));
-}
 __device__ __forceinline__ unsigned vr_absmax8(unsigned m, const uint4 v) {
-  return vr_absmax2(vr_absmax2(vr_absmax2(vr_absmax2(m, v.x), v.y), v.z), v.w);
+  return absmax_pk2(absmax_pk2(absmax_pk2(absmax_pk2(m, v.x), v.y), v.z), v.w);
 }
 
 // s = 2^(15 - e) for bound = m 2^e; 1 when the bound is zero, Inf or NaN

@@ -45,8 +45,8 @@ __device__ __forceinline__ void pp_split_rows(const float4 (&v)[16], char* x, in
   for (int j = 0; j < 16; ++j) {
     const int row = j * 4 + lw;
     unsigned h01, h23, l01, l23;
-    ch_split2(v[j].x, v[j].y, h01, l01);
-    ch_split2(v[j].z, v[j].w, h23, l23);
+    bf16_split2(v[j].x, v[j].y, h01, l01);
+    bf16_split2(v[j].z, v[j].w, h23, l23);
     char* q = x + row * 512 + (((lane >> 1) ^ row) & 31) * 16 + (lane & 1) * 8;
     *reinterpret_cast<uint2*>(q) = make_uint2(h01, h23);
     *reinterpret_cast<uint2*>(q + kChPlane) = make_uint2(l01, l23);

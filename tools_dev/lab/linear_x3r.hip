@@ -74,8 +74,8 @@ __global__ __launch_bounds__(256, 2) void linear_x3r_kernel(
       for (int j = 0; j < 8; ++j) {
         const int row = wave * 16 + half * 8 + j;
         unsigned h01, h23, l01, l23;
-        x3_split2(v[j].x, v[j].y, h01, l01);
-        x3_split2(v[j].z, v[j].w, h23, l23);
+        bf16_split2(v[j].x, v[j].y, h01, l01);
+        bf16_split2(v[j].z, v[j].w, h23, l23);
         char* d = xl + row * 512 + (((lane >> 1) ^ (row & 31)) * 16) + (lane & 1) * 8;
         *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
         *reinterpret_cast<uint2*>(d + kXrPlane) = make_uint2(l01, l23);
@@ -259,9 +259,9 @@ __global__ __launch_bounds__(256, 2) void linear_x3r_kernel(
             v = *reinterpret_cast<const float4*>(sO + row * kXrLnPitch + c);
             v.x += rres[rr].x; v.y += rres[rr].y; v.z += rres[rr].z; v.w += rres[rr].w;
           }
-          const float mean = x3_wave_sum(col_live ? (v.x + v.y) + (v.z + v.w) : 0.f) * inv_n;
+          const float mean = wave_sum(col_live ? (v.x + v.y) + (v.z + v.w) : 0.f) * inv_n;
           const float dx = v.x - mean, dy = v.y - mean, dz = v.z - mean, dw = v.w - mean;
-          const float var = x3_wave_sum(col_live ? (dx * dx + dy * dy) + (dz * dz + dw * dw) : 0.f) * inv_n;
+          const float var = wave_sum(col_live ? (dx * dx + dy * dy) + (dz * dz + dw * dw) : 0.f) * inv_n;
           const float rstd = rsqrtf(var + ln_eps);
           v.x = dx * rstd * gv.x + bev.x; v.y = dy * rstd * gv.y + bev.y;
           v.z = dz * rstd * gv.z + bev.z; v.w = dw * rstd * gv.w + bev.w;
