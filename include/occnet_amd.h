@@ -27,6 +27,7 @@
  *   occ_occ_heads_f32                <- predicter / flow_predicter MLPs, transformer_occ.py:132-141,318-319
  *   occ_linear_f32                   <- the nn.Linear / FFN / LayerNorm call sites of a BEVFormerLayer
  *   occ_dvr_render_forward_f32       <- dvr.render_forward, tools/ray_iou/lib/dvr/dvr.cu:70-388
+ *   occ_ray_metrics_accumulate       <- process_one_sample + main + calc_metrics, P/datasets/ray_metrics.py:89-257
  */
 #ifndef OCCNET_AMD_H_
 #define OCCNET_AMD_H_
@@ -651,6 +652,41 @@ int occ_mfma_pack_b_frag_bf16(const float* weight, void* packed, int N, int K, v
 int occ_bottleneck64_nhwc_bf16(const void* x, const void* w1_frag, const float* b1, const void* w2_frag,
                                const float* b2, const void* w3_frag, const float* b3, void* out, int batch,
                                int H, int W, int Cin, int downsample, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (e) Evaluation: RayIoU / mAVE counters of a batch of samples in one fused pass (csrc/ray_metrics_fused.hip) — the
+ * reference's process_one_sample + main's non-free filter + calc_metrics (projects/mmdet3d_plugin/datasets/
+ * ray_metrics.py:89-257) without a host round trip: occupancy bit masks per pillar, the "test"-phase ray cast of
+ * occ_dvr_render_forward_f32 on the ground-truth and on the predicted grid, and the per-class scoring.
+ *   sem_pred, sem_gt (B, X, Y, Z) class ids, dtype code 0 = uint8, 1 = int64 (each grid its own); a voxel is occupied
+ *                    iff its class != free_id; classes outside 0..free_id are occupied and counted in no class
+ *   flow_pred, flow_gt (B, X, Y, Z, 2) f32
+ *   origins (B, Tmax, 3) f32 lidar origins in ego metres, 1 <= Tmax <= 8; origin_counts (B) i32 DEVICE, origins of
+ *                    sample b beyond origin_counts[b] are not cast (NULL: every sample has Tmax)
+ *   rays (R, 3) f32 unit directions; off_x/y/z = pc_range[:3], voxel_size: (p - off) / voxel_size in float32
+ *   state            occ_ray_metrics_state_words(free_id) = 14 * (free_id + 1) int64 words, ACCUMULATED into (the
+ *                    caller zeroes them once): gt_cnt[c] | pred_cnt[c] | tp_cnt[j][c] | ave_cnt[j][c] | ave_sum[j][c] |
+ *                    ave_bad[j][c], c = class, j = depth threshold 1 / 2 / 4 m.  ave_sum: flow errors of the true
+ *                    positives of classes 0..7 in fixed point, quantum 2^-28 m/s (sums below 2^35 m/s); ave_bad counts
+ *                    the non-finite (or >= 2^34 m/s) errors, which are left out of ave_sum.  Integer atomics only: the
+ *                    state is bit-identical run to run and for any split of the samples over calls.
+ *   rows_pred, rows_gt NULL, or (B, Tmax, R, 4) f32 out: (label, depth [m], flow_x, flow_y) per ray in
+ *                    process_one_sample's order; rows of origins beyond origin_counts[b] are not written.  When given,
+ *                    every ray is cast on both grids; otherwise the prediction cast of a ray whose ground truth is free
+ *                    is skipped (the state is the same).
+ *   workspace        occ_ray_metrics_workspace_bytes(B, X, Y, Z) bytes, 256-byte aligned, uninitialised: the pillar masks
+ *                    (uint16 for Z <= 16, uint32 for Z <= 32) of both grids.  Z > 32: OCC_E_UNSUPPORTED (query: 0).
+ * free_id in 1..31.  Two launches, no synchronisation, no allocation, no copy.
+ */
+int64_t occ_ray_metrics_state_words(int free_id);
+int64_t occ_ray_metrics_workspace_bytes(int B, int X, int Y, int Z);
+int occ_ray_metrics_accumulate(const void* sem_pred, int sem_pred_dtype, const float* flow_pred,
+                               const void* sem_gt, int sem_gt_dtype, const float* flow_gt,
+                               const float* origins, const int32_t* origin_counts, const float* rays,
+                               float off_x, float off_y, float off_z, float voxel_size, int free_id,
+                               int64_t* state, float* rows_pred, float* rows_gt, void* workspace,
+                               int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R,
+                               void* stream);
 
 #ifdef __cplusplus
 }

@@ -1521,6 +1521,77 @@ def dvr_render_forward(sigma, origin, points, tindex, grid=None, phase_name="tes
     return pred, gt, coord
 
 
+_SEM_DTYPE_CODES = {torch.uint8: 0, torch.int64: 1}
+
+
+def ray_metrics_state_words(free_id=16):
+    """int64 words of the RayIoU / mAVE state for classes 0..free_id (14 per class; layout: include/occnet_amd.h)."""
+    fn = _lib.lib().occ_ray_metrics_state_words
+    fn.restype = ctypes.c_int64
+    n = int(fn(i32(free_id)))
+    if n <= 0:
+        raise OccAmdError(f"ray_metrics_state_words: free_id must be 1..31, got {free_id}")
+    return n
+
+
+def ray_metrics_workspace_bytes(B, X, Y, Z):
+    fn = _lib.lib().occ_ray_metrics_workspace_bytes
+    fn.restype = ctypes.c_int64
+    return int(fn(i32(B), i32(X), i32(Y), i32(Z)))
+
+
+def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins, rays, pc_min, voxel_size, free_id=16,
+                           origin_counts=None, return_rays=False, workspace=None):
+    """Cast `rays` from every lidar origin through the ground-truth and the predicted grid and add the RayIoU / mAVE terms of
+    the rays whose ground truth is not free to `state` (int64 device tensor of ray_metrics_state_words(free_id) words), in two
+    launches on the current stream: no synchronisation, no copy (csrc/ray_metrics_fused.hip).
+    sem_pred / sem_gt (B, X, Y, Z) uint8 or int64, flow_pred / flow_gt (B, X, Y, Z, 2) float32, origins (B, Tmax, 3) float32 in
+    ego metres (Tmax <= 8), origin_counts None or (B) int32 DEVICE tensor, rays (R, 3) float32, pc_min = pc_range[:3].
+    workspace: None, or a uint8 device tensor of at least ray_metrics_workspace_bytes(B, X, Y, Z) bytes.
+    -> None, or with return_rays (rows_pred, rows_gt), each (B, Tmax, R, 4) float32 (label, depth, flow_x, flow_y); rows of
+    origins beyond origin_counts stay zero."""
+    for n, t in (("flow_pred", flow_pred), ("flow_gt", flow_gt), ("origins", origins), ("rays", rays)):
+        _need_cuda_f32(n, t)
+    for n, t in (("sem_pred", sem_pred), ("sem_gt", sem_gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise OccAmdError(f"{n} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+        if t.dtype not in _SEM_DTYPE_CODES or not t.is_contiguous():
+            raise OccAmdError(f"{n} must be a contiguous uint8 or int64 tensor, got {t.dtype}")
+    if not (state.is_cuda and state.dtype == torch.int64 and state.is_contiguous()
+            and state.numel() == ray_metrics_state_words(free_id)):
+        raise OccAmdError("ray_metrics_accumulate: state must be a contiguous int64 device tensor of "
+                          f"{ray_metrics_state_words(free_id)} words")
+    if sem_pred.dim() != 4 or sem_gt.shape != sem_pred.shape or origins.dim() != 3 or rays.dim() != 2:
+        raise OccAmdError("ray_metrics_accumulate: expected sem (B,X,Y,Z), flow (B,X,Y,Z,2), origins (B,T,3), rays (R,3)")
+    B, X, Y, Z = sem_pred.shape
+    Tmax, R = origins.shape[1], rays.shape[0]
+    if (tuple(flow_pred.shape) != (B, X, Y, Z, 2) or flow_gt.shape != flow_pred.shape or origins.shape[0] != B
+            or origins.shape[2] != 3 or rays.shape[1] != 3):
+        raise OccAmdError("ray_metrics_accumulate: inconsistent shapes")
+    if origin_counts is not None and not (origin_counts.is_cuda and origin_counts.dtype == torch.int32
+                                          and origin_counts.is_contiguous() and origin_counts.numel() == B):
+        raise OccAmdError("ray_metrics_accumulate: origin_counts must be a contiguous int32 device tensor of B entries")
+    dev = sem_pred.device
+    need = max(ray_metrics_workspace_bytes(B, X, Y, Z), 256)      # Z > 32 answers 0: the call itself reports it
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
+        raise OccAmdError(f"ray_metrics_accumulate: workspace must be a uint8 device tensor of >= {need} bytes")
+    rows_pred = rows_gt = None
+    if return_rays:
+        rows_pred = torch.zeros((B, Tmax, R, 4), dtype=torch.float32, device=dev)
+        rows_gt = torch.zeros((B, Tmax, R, 4), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev), _timed('ray_metrics_accumulate'):
+        rc = _lib.lib().occ_ray_metrics_accumulate(
+            ptr(sem_pred), i32(_SEM_DTYPE_CODES[sem_pred.dtype]), ptr(flow_pred), ptr(sem_gt),
+            i32(_SEM_DTYPE_CODES[sem_gt.dtype]), ptr(flow_gt), ptr(origins), ptr(origin_counts), ptr(rays),
+            f32(pc_min[0]), f32(pc_min[1]), f32(pc_min[2]), f32(voxel_size), i32(free_id), ptr(state), ptr(rows_pred),
+            ptr(rows_gt), ptr(workspace), i64(workspace.numel()), i32(B), i32(Tmax), i32(X), i32(Y), i32(Z), i32(R),
+            stream_ptr(dev))
+    _lib.check(rc, "ray_metrics_accumulate")
+    return (rows_pred, rows_gt) if return_rays else None
+
+
 def bias_act_nhwc_(x, bias, residual=None, relu=True):
     """In place x = relu?(x + bias[c] (+ residual)) on a channels_last bf16 (N, C, H, W) tensor (memory
     order N, H, W, C).  bias (C) float32.  Returns x."""
