@@ -633,6 +633,23 @@ int occ_conv3x3_nhwc_bf16_variant(const void* x, const void* weight_packed, cons
                                   int H, int W, int Cin, int Cout, int stride, int relu, uint32_t* amax8, int variant,
                                   void* stream);
 
+/* A 3x3 convolution and the 1x1 expansion after it (ResNet bottleneck conv2 + conv3) in one launch; the mid tensor stays
+ * in LDS (csrc/conv3x3_conv1x1_fused_bf16.hip):
+ *   out = relu( conv1x1( bf16( relu(conv3x3(x, W2, pad 1, stride) + b2) ), W3 ) + b3 + residual )
+ *   x (batch, H, W, Cmid) bf16 ; w3x3_packed = occ_conv3x3_pack_weight_bf16 of W2 (Cmid, Cmid, 3, 3) ; b2 (Cmid) f32 ;
+ *   w1x1_frag = occ_mfma_pack_b_frag_bf16 of W3 (Cout, Cmid) ; b3 (Cout) f32 ; residual / out (batch, Ho, Wo, Cout) bf16,
+ *   Ho = (H-1)/stride + 1.  Needs Cmid 128 or 256, Cout = 4 Cmid, stride 1 or 2, otherwise OCC_E_UNSUPPORTED.
+ * variant: the 3x3 tile id (10 * NT + RT, as occ_conv3x3_nhwc_bf16_variant) the block uses; it must hold all mid channels
+ * (Cmid 128: 12, and 13 at stride 2; Cmid 256: 22, and 23, 24 at stride 1).  0 = the tile occ_conv3x3_conv1x1_pick returns, and
+ * OCC_E_UNSUPPORTED where that is 0.  For a tile id the result is bit-identical to occ_conv3x3_nhwc_bf16_variant with that
+ * id followed by occ_conv1x1_nhwc_bf16_variant 2.  Argument checks run before any launch. */
+int occ_conv3x3_conv1x1_nhwc_bf16(const void* x, const void* w3x3_packed, const float* b2, const void* w1x1_frag,
+                                  const float* b3, const void* residual, void* out, int batch, int H, int W, int Cmid,
+                                  int Cout, int stride, int variant, void* stream);
+/* The tile id the entry point above uses for a shape at variant 0, or 0 when the shape should stay on the two launches
+ * (no fused kernel, or too few tiles to give every CU a block).  A pure function of its arguments; needs no GPU. */
+int occ_conv3x3_conv1x1_pick(int batch, int H, int W, int Cmid, int Cout, int stride);
+
 /* MFMA B-operand packing: f32 row-major (N, K) matrix -> bf16 in v_mfma_f32_32x32x16_bf16 fragment order
  * packed[((ks * N/32 + nt) * 64 + lane) * 8 + j] = w[nt*32 + (lane & 31)][ks*16 + (lane >> 5)*8 + j], so a wave
  * loads its operand of (k-step ks, column tile nt) as one coalesced 1 KB read.  Needs N % 32 == 0, K % 16 == 0.

@@ -1912,3 +1912,47 @@ def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None, varia
     _note_flops('bb_conv3x3', 2.0 * N * out.shape[2] * out.shape[3] * 9 * Cin * cout)
     _lib.check(rc, "conv3x3_nhwc")
     return out
+
+
+def conv3x3_conv1x1_pick(batch, H, W, cmid, cout, stride=1):
+    """Tile id (10 * NT + RT) conv3x3_conv1x1_nhwc uses for an input of (batch, cmid, H, W), or 0 when the shape stays on
+    conv3x3_nhwc + conv1x1_nhwc (occ_conv3x3_conv1x1_pick: a pure function of the shape, needs no GPU)."""
+    return int(_lib.lib().occ_conv3x3_conv1x1_pick(i32(batch), i32(H), i32(W), i32(cmid), i32(cout), i32(int(stride))))
+
+
+def conv3x3_conv1x1_nhwc(x, w3_packed, b2, cmid, w1_frag, b3, residual, stride=1, variant=None):
+    """relu(conv1x1(relu(conv3x3(x) + b2) rounded to bf16) + b3 + residual) in one launch: conv2 + conv3 of a ResNet
+    bottleneck with 128 or 256 mid channels; the mid tensor stays on chip.
+    x (N, cmid, H, W) channels_last bf16; w3_packed from conv3x3_pack_weight((cmid, cmid, 3, 3)); b2 (cmid) f32; w1_frag from
+    conv1x1_pack_weight((Cout, cmid)); b3 (Cout) f32, Cout = 4 * cmid; residual (N, Cout, Ho, Wo) channels_last bf16
+    -> (N, Cout, Ho, Wo) channels_last bf16, Ho = (H-1)//stride + 1.
+    variant: None = the tile conv3x3_conv1x1_pick returns (OccAmdUnsupported where that is 0); an int forces the 3x3 tile
+    id.  Bit-identical to conv1x1_nhwc(conv3x3_nhwc(x, ..., relu=True, variant=v), ..., relu=True, variant=2)."""
+    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
+            and x.is_contiguous(memory_format=torch.channels_last)):
+        raise OccAmdUnsupported("conv3x3_conv1x1_nhwc: x must be a channels_last bfloat16 device tensor")
+    _need_cuda_f32("b2", b2)
+    _need_cuda_f32("b3", b3)
+    N, Cin, H, W = x.shape
+    Cout = b3.numel()
+    if Cin != cmid or w3_packed.numel() != cmid * Cin * 9 or b2.numel() != cmid:
+        raise OccAmdError("conv3x3_conv1x1_nhwc: inconsistent 3x3 shapes")
+    if not (w1_frag.dtype == torch.int16 and w1_frag.dim() == 1 and w1_frag.is_contiguous()
+            and w1_frag.numel() == Cout * cmid):
+        raise OccAmdError("conv3x3_conv1x1_nhwc: w1_frag must come from conv1x1_pack_weight (Cout*cmid bf16, fragment order)")
+    st = int(stride)
+    if st not in (1, 2):
+        raise OccAmdUnsupported("conv3x3_conv1x1_nhwc: stride must be 1 or 2")
+    Ho, Wo = (H - 1) // st + 1, (W - 1) // st + 1
+    out = torch.empty((N, Cout, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    if residual is None or not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == tuple(out.shape) and
+                                residual.is_cuda and residual.is_contiguous(memory_format=torch.channels_last)):
+        raise OccAmdUnsupported("conv3x3_conv1x1_nhwc: residual must match the output (channels_last bfloat16)")
+    # timed under the 3x3 family (bench.py --full sums four fixed family names), with the FLOPs of both convolutions
+    with torch.cuda.device(x.device), _timed('bb_conv3x3'):
+        rc = _lib.lib().occ_conv3x3_conv1x1_nhwc_bf16(ptr(x), ptr(w3_packed), ptr(b2), ptr(w1_frag), ptr(b3), ptr(residual),
+                                                      ptr(out), i32(N), i32(H), i32(W), i32(cmid), i32(Cout), i32(st),
+                                                      i32(0 if variant is None else int(variant)), stream_ptr(x.device))
+    _note_flops('bb_conv3x3', 2.0 * N * Ho * Wo * (9 * Cin * cmid + cmid * Cout))
+    _lib.check(rc, "conv3x3_conv1x1_nhwc")
+    return out

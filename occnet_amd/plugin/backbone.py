@@ -617,9 +617,31 @@ class FusedInferenceBackbone(nn.Module):
                 x = ext.bottleneck64_nhwc(x, pk)
                 continue
             identity = x if ds is None else self._conv(ds, x)
-            y = self._conv(c2, self._conv(c1, x, relu=True), relu=True)
-            x = self._conv(c3, y, add=identity)
+            y = self._conv(c1, x, relu=True)
+            fused = self._conv23_fused(c2, c3, y, identity)
+            x = fused if fused is not None else self._conv(c3, self._conv(c2, y, relu=True), add=identity)
         return x
+
+    def _conv23_fused(self, c2, c3, y, identity):
+        """conv2 (3x3) + conv3 (1x1 + residual + ReLU) as one launch where ext.conv3x3_conv1x1_pick fuses the shape
+        (OCC_CONV3X3_FUSE_1X1=0 keeps the two launches: development A/B inside one build); None otherwise."""
+        if not (self._c3.get(c2) and self._gemm.get(c3)) or self.fused_ops \
+                or os.environ.get('OCC_CONV3X3_FUSE_1X1', '1').startswith('0'):
+            return None
+        cl = torch.channels_last
+        if not (y.is_cuda and y.dtype == torch.bfloat16 and y.is_contiguous(memory_format=cl)
+                and identity.dtype == torch.bfloat16 and identity.is_contiguous(memory_format=cl)):
+            return None
+        from .. import ext
+        w2, w3 = getattr(self, f'w{c2}'), getattr(self, f'w{c3}')
+        stride = self._convs[c2][0][0]
+        if self._convs[c3][0] != (1, 1) or w3.shape[1] != w2.shape[0]:
+            return None
+        n, _, h, w = y.shape
+        if not ext.conv3x3_conv1x1_pick(n, h, w, w2.shape[0], w3.shape[0], stride):
+            return None
+        return ext.conv3x3_conv1x1_nhwc(y, getattr(self, f'p{c2}'), getattr(self, f'b{c2}'), w2.shape[0],
+                                        getattr(self, f'm{c3}'), getattr(self, f'b{c3}'), identity, stride=stride)
 
     @torch.no_grad()
     def forward_prefix(self, x):

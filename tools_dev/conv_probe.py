@@ -89,6 +89,30 @@ def main(which):
                 tag = 'auto' if v is None else f'v{v}'
                 print(f"conv1x1 {cin:4d}->{cout:4d} {h:3d}x{w:3d} s{s} res{res} {tag:5s}: {us:7.1f} us "
                       f"[{t[0]:6.1f} - {t[-1]:6.1f}]  {fl / us * 1e-6:6.1f} TF/s  {mb / us:5.2f} TB/s", flush=True)
+    if 'f31' in which:
+        # conv2 + conv3 of a layer2 / layer3 bottleneck: the pair of launches (the launchers' choices) against the fused
+        # launch (ext.conv3x3_conv1x1_nhwc) at every tile it has for the shape, 5 interleaved rounds, median and min-max
+        for (cmid, h, w, s) in [(128, 116, 200, 1), (128, 232, 400, 2), (256, 58, 100, 1), (256, 116, 200, 2)]:
+            cout = 4 * cmid
+            ho, wo = (h - 1) // s + 1, (w - 1) // s + 1
+            x, r = act(cmid, h, w), act(cout, ho, wo)
+            w2, b2 = ext.conv3x3_pack_weight(mk(cmid, cmid, 3, 3)), mk(cmid)
+            w3, b3 = ext.conv1x1_pack_weight(mk(cout, cmid)), mk(cout)
+            pick = ext.conv3x3_conv1x1_pick(N, h, w, cmid, cout, s)
+            tiles = {(128, 1): (12,), (128, 2): (12, 13), (256, 1): (22, 23, 24), (256, 2): (22,)}[(cmid, s)]
+            fns = {'pair': lambda: ext.conv1x1_nhwc(ext.conv3x3_nhwc(x, w2, b2, cmid, relu=True, stride=s), w3, b3,
+                                                    residual=r, relu=True)}
+            for v in tiles:
+                fns[f'f{v}'] = lambda v=v: ext.conv3x3_conv1x1_nhwc(x, w2, b2, cmid, w3, b3, r, stride=s, variant=v)
+            times = {k: [] for k in fns}
+            for _ in range(5):
+                for k, fn in fns.items():
+                    times[k].append(timeit(fn))
+            fl = 2.0 * N * ho * wo * (9 * cmid * cmid + cmid * cout)
+            for k in fns:
+                t = sorted(times[k])
+                print(f"conv3x3+1x1 {cmid:3d}->{cout:4d} {h:3d}x{w:3d} s{s} pick {pick:2d} {k:5s}: {t[2]:7.1f} us "
+                      f"[{t[0]:6.1f} - {t[-1]:6.1f}]  {fl / t[2] * 1e-6:6.1f} TF/s", flush=True)
 
 
 def vp():
