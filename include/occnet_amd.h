@@ -609,6 +609,23 @@ int occ_conv1x1_nhwc_bf16_variant(const void* x, const void* weight, const float
                                   void* out, int batch, int Hin, int Win, int Cin, int Cout, int stride, int relu,
                                   int residual_upsample2, int variant, void* stream);
 
+/* Training partner of occ_conv1x1_nhwc_bf16 (csrc/conv1x1_wgrad_bf16.hip): weight gradient of the 1x1 convolution,
+ *     dw[o][i] = sum over (n, yo, xo) of g[(n, yo, xo), o] * x[(n, yo*stride, xo*stride), i]
+ * bf16 in, f32 accumulation on the matrix cores.  g (N, Ho, Wo, Cout) bf16 NHWC with Ho = (H-1)/stride + 1, x (N, H, W, Cin)
+ * bf16 NHWC, both 4-byte aligned; dw (Cout, Cin) contiguous, f32 or (dw_bf16 != 0) bf16, overwritten, not accumulated.
+ * Needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048, stride 1 or 2, otherwise OCC_E_UNSUPPORTED (and
+ * ..._workspace_bytes() == 0): the caller keeps ATen's convolution_backward.
+ * The pixel dimension is reduced in `splits` ranges into `workspace` (occ_conv1x1_wgrad_workspace_bytes(...) bytes for the
+ * SAME arguments, owned by the caller, 8-byte aligned; every byte of it that is read has been written by this call) and
+ * the partial sums are added in a fixed order: the result is deterministic, no float atomics.  splits: 0 = the launcher's
+ * choice (enough blocks for 256 CUs), > 0 = at most that many equal ranges (ceil(pixels / splits) pixels each, as many as cover the pixels; at most
+ * min(pixels, 4096); tests, probes), < 0 OCC_E_INVALID.
+ * Argument checks run before any launch.  Replaces: the weight half of ATen's convolution_backward (MIOpen / CK) behind
+ * ConvBNActFunction.  The input gradient needs no entry point at stride 1: gx = occ_conv1x1_nhwc_bf16(g, pack(W^T)). */
+int64_t occ_conv1x1_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride, int splits);
+int occ_conv1x1_wgrad_nhwc_bf16(const void* g, const void* x, void* dw, int dw_bf16, void* workspace, int N, int H, int W,
+                                int Cin, int Cout, int stride, int splits, void* stream);
+
 /* Backbone 3x3 pad-1 convolution, stride 1 or 2, on NHWC bf16 with bias (+ ReLU) fused (outside the
  * hand-written hot path).  x (batch, H, W, Cin) bf16 ; weight packed by occ_conv3x3_pack_weight_bf16 from
  * torch's (Cout, Cin, 3, 3) f32 layout to [Cin/32][tap][co][32] bf16 ; bias (Cout) f32 ;

@@ -43,7 +43,7 @@ class _timed:
         self.name = name
 
     def __enter__(self):
-        self.on = _TIMING is not None and (_TIMING_ONLY is None or self.name in _TIMING_ONLY)
+        self.on = self.name is not None and _TIMING is not None and (_TIMING_ONLY is None or self.name in _TIMING_ONLY)
         if self.on:
             self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             self.ev[0].record()
@@ -57,7 +57,7 @@ class _timed:
 
 def _note_flops(name, flops):
     """bench.py's backbone roofline: the FLOPs of an instrumented launch, next to its event pair."""
-    if _TIMING is not None and (_TIMING_ONLY is None or name in _TIMING_ONLY):
+    if name is not None and _TIMING is not None and (_TIMING_ONLY is None or name in _TIMING_ONLY):
         _TIMING.setdefault(name + '_flops', []).append(float(flops))
 
 
@@ -1759,13 +1759,15 @@ def conv1x1_pack_weight(weight2d):
     return mfma_pack_b_frag(weight2d.float().contiguous())
 
 
-def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, residual_upsample2=False, variant=None):
+def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, residual_upsample2=False, variant=None,
+                 _timing='bb_conv1x1'):
     """1x1 convolution + bias (+ residual) (+ ReLU) on a channels_last bf16 activation, one launch.
     x (N, Cin, H, W) channels_last bf16; weight_frag = conv1x1_pack_weight((Cout, Cin) matrix); bias (Cout) f32;
     residual (N, Cout, Ho, Wo) channels_last bf16 or None -> (N, Cout, Ho, Wo) channels_last bf16.
     residual_upsample2: residual is (N, Cout, Ho/2, Wo/2) and is added nearest-upsampled x2 (FPN top-down).
     variant: None = the launcher's choice; an int forces the kernel (occ_conv1x1_nhwc_bf16_variant: 1 = tiled, 2 =
-    activation-resident, 22 / 24 = resident with the 64- / 128-row tile); OccAmdUnsupported where the shape has none."""
+    activation-resident, 22 / 24 = resident with the 64- / 128-row tile); OccAmdUnsupported where the shape has none.
+    _timing: the kernel_timing entry the launch is booked under (conv1x1_dgrad_nhwc books the whole call under its own)."""
     if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
             and x.is_contiguous(memory_format=torch.channels_last)):
         raise OccAmdUnsupported("conv1x1_nhwc: x must be a channels_last bfloat16 device tensor")
@@ -1785,7 +1787,7 @@ def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, resi
     if residual is not None and not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == want and
                                      residual.is_contiguous(memory_format=torch.channels_last)):
         raise OccAmdUnsupported("conv1x1_nhwc: residual must match the output (channels_last bfloat16)")
-    with torch.cuda.device(x.device), _timed('bb_conv1x1'):
+    with torch.cuda.device(x.device), _timed(_timing):
         if variant is None:
             rc = _lib.lib().occ_conv1x1_nhwc_bf16(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
                                                   i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
@@ -1796,9 +1798,70 @@ def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, resi
                                                           i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
                                                           i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
                                                           i32(int(variant)), stream_ptr(x.device))
-    _note_flops('bb_conv1x1', 2.0 * N * Ho * Wo * Cin * Cout)
+    _note_flops(_timing, 2.0 * N * Ho * Wo * Cin * Cout)
     _lib.check(rc, "conv1x1_nhwc")
     return out
+
+
+def _need_cl_bf16(what, name, t):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
+            and t.is_contiguous(memory_format=torch.channels_last)):
+        raise OccAmdUnsupported(f"{what}: {name} must be a channels_last bfloat16 device tensor")
+
+
+def conv1x1_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
+    """Weight gradient of conv1x1_nhwc (csrc/conv1x1_wgrad_bf16.hip): dw[o, i] = sum over output pixels of
+    g[n, o, yo, xo] * x[n, i, yo * stride, xo * stride], f32 accumulation on the matrix cores, deterministic.
+    g (N, Cout, Ho, Wo) and x (N, Cin, H, W) channels_last bf16 with Ho = (H - 1) // stride + 1 -> (Cout, Cin, 1, 1) in
+    out_dtype (float32 or bfloat16).  Cin % 32 == 0, Cout % 32 == 0, both <= 2048, stride 1 or 2: OccAmdUnsupported
+    otherwise.  splits: None = the launcher's choice of pixel ranges; an int forces it (tests, probes)."""
+    _need_cl_bf16("conv1x1_wgrad_nhwc", "g", g)
+    _need_cl_bf16("conv1x1_wgrad_nhwc", "x", x)
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise OccAmdUnsupported("conv1x1_wgrad_nhwc: out_dtype must be float32 or bfloat16")
+    N, Cin, H, W = x.shape
+    s = int(stride)
+    Cout = g.shape[1]
+    if s not in (1, 2) or tuple(g.shape) != (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1) or g.device != x.device:
+        raise OccAmdUnsupported("conv1x1_wgrad_nhwc: g must be (N, Cout, (H-1)//stride+1, (W-1)//stride+1) on x's device, "
+                                "stride 1 or 2")
+    sp = 0 if splits is None else int(splits)
+    if sp < 0 or (splits is not None and sp == 0):
+        raise OccAmdError("conv1x1_wgrad_nhwc: splits must be None or a positive int")
+    lib = _lib.lib()
+    lib.occ_conv1x1_wgrad_workspace_bytes.restype = ctypes.c_int64
+    nbytes = int(lib.occ_conv1x1_wgrad_workspace_bytes(i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp)))
+    if nbytes <= 0:
+        raise OccAmdUnsupported("conv1x1_wgrad_nhwc: needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048 "
+                                f"(Cin={Cin}, Cout={Cout})")
+    dw = torch.empty((Cout, Cin, 1, 1), dtype=out_dtype, device=x.device)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)     # torch's caching allocator
+    with torch.cuda.device(x.device), _timed('bb_conv1x1_wgrad'):
+        rc = lib.occ_conv1x1_wgrad_nhwc_bf16(ptr(g), ptr(x), ptr(dw), i32(1 if out_dtype == torch.bfloat16 else 0), ptr(ws),
+                                             i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp),
+                                             stream_ptr(x.device))
+    _note_flops('bb_conv1x1_wgrad', 2.0 * N * g.shape[2] * g.shape[3] * Cin * Cout)
+    _lib.check(rc, "conv1x1_wgrad_nhwc")
+    return dw
+
+
+def conv1x1_dgrad_nhwc(g, w16):
+    """Data gradient of a stride-1 conv1x1_nhwc: gx[n, i, y, x] = sum_o g[n, o, y, x] * w16[o, i] — the forward kernel on
+    the transposed weight (zero bias, no residual, no ReLU); no kernel of its own.
+    g (N, Cout, H, W) channels_last bf16; w16 (Cout, Cin, 1, 1) or (Cout, Cin) device weight -> (N, Cin, H, W) channels_last
+    bf16.  Cin % 32 == 0 and Cout % 32 == 0: OccAmdUnsupported otherwise."""
+    _need_cl_bf16("conv1x1_dgrad_nhwc", "g", g)
+    if not (isinstance(w16, torch.Tensor) and w16.is_cuda and w16.is_floating_point() and w16.dim() in (2, 4)
+            and w16.shape[0] == g.shape[1] and w16.numel() == w16.shape[0] * w16.shape[1] and w16.device == g.device):
+        raise OccAmdUnsupported("conv1x1_dgrad_nhwc: w16 must be a (Cout, Cin, 1, 1) device weight matching g's channels")
+    O, I = w16.shape[0], w16.shape[1]
+    # one kernel_timing entry for the whole call: the transpose + pack of the weight and the zero bias are paid per call, and the
+    # launch is not booked as a forward bb_conv1x1 launch as well
+    with torch.cuda.device(g.device), _timed('bb_conv1x1_dgrad'):
+        frag = conv1x1_pack_weight(w16.reshape(O, I).t())
+        gx = conv1x1_nhwc(g, frag, torch.zeros(I, dtype=torch.float32, device=g.device), _timing=None)
+    _note_flops('bb_conv1x1_dgrad', 2.0 * g.shape[0] * g.shape[2] * g.shape[3] * I * O)
+    return gx
 
 
 def mfma_pack_b_frag(weight2d):

@@ -57,7 +57,11 @@ class ConvBNActFunction(torch.autograd.Function):
     more passes over the activation.  Backward: ONE pass makes the ReLU-masked gradient and the bias gradient
     (ext.bias_act_bwd_nhwc; ATen: threshold_backward + a bf16 column reduction + an add at the residual join), MIOpen's data /
     weight gradients follow, and the fold's chain rule gives the gradients of W, gamma and beta.  Same function and the same
-    gradients as conv_bn_folded up to bf16 rounding (the tail adds in fp32 and rounds once instead of three times)."""
+    gradients as conv_bn_folded up to bf16 rounding (the tail adds in fp32 and rounds once instead of three times).
+    own_conv1x1_backward (opt-in, OCC_TRAIN_CONV1X1_BWD=1): the nodes whose forward ran conv1x1_nhwc take their weight
+    gradient from ext.conv1x1_wgrad_nhwc and, at stride 1, their data gradient from ext.conv1x1_dgrad_nhwc instead of MIOpen."""
+
+    own_conv1x1_backward = os.environ.get("OCC_TRAIN_CONV1X1_BWD", "0") == "1"
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, rstd, mean_rstd, conv_bias, residual, stride, padding, relu):
@@ -115,8 +119,23 @@ class ConvBNActFunction(torch.autograd.Function):
         if not (gy.dtype == torch.bfloat16 and gy.is_contiguous(memory_format=cl)):
             gy = gy.to(torch.bfloat16).contiguous(memory_format=cl)
         g, gb = ext.bias_act_bwd_nhwc(gy, y, relu=relu)
-        gx, gw, _ = torch.ops.aten.convolution_backward(g, x16, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
-                                                        (bool(need[0]), bool(need[1] or need[2]), False))
+        O, I, kh, kw = w16.shape
+        if (ConvBNActFunction.own_conv1x1_backward and (kh, kw) == (1, 1) and padding == (0, 0) and stride[0] == stride[1]
+                and I % 32 == 0 and O % 32 == 0 and g.data_ptr() % 4 == 0 and x16.data_ptr() % 4 == 0):
+            # the nodes whose forward took conv1x1_nhwc: the weight gradient on conv1x1_wgrad_nhwc, the stride-1 data gradient
+            # on the forward kernel with the transposed weight; the stride-2 data gradient (a scatter) stays on ATen (as does a
+            # view at an odd element offset: the kernels load dwords)
+            gx = gw = None
+            if need[1] or need[2]:
+                gw = ext.conv1x1_wgrad_nhwc(g, x16, stride[0], out_dtype=torch.bfloat16)
+            if need[0] and stride[0] == 1:
+                gx = ext.conv1x1_dgrad_nhwc(g, w16)
+            elif need[0]:
+                gx = torch.ops.aten.convolution_backward(g, x16, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
+                                                         (True, False, False))[0]
+        else:
+            gx, gw, _ = torch.ops.aten.convolution_backward(g, x16, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
+                                                            (bool(need[0]), bool(need[1] or need[2]), False))
         dW = dgamma = dbeta = dcb = None
         if gw is not None and one_launch:
             # the fold's chain rule, one launch, makes dW and dgamma together; a mask that wants one of them (frozen BatchNorm
