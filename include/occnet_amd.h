@@ -231,6 +231,10 @@ int occ_sca_rows_encode_q16(const float* v, void* out, const float* scale, int64
  *   offs     (B, Nq, M*2*P*2) f32, row stride offs_stride ; logits (B, Nq, M*2*P), stride logits_stride
  *   ref_2d   (B*2, Nq, 1, 2) f32
  *   out      (B, Nq, M*D) f32
+ *   order    NULL, or Nq int32: a permutation of 0..Nq-1, the query that wave r of a batch entry computes (locality
+ *            only; the values are NOT range-checked: anything but a permutation leaves rows unwritten or reads out of range)
+ * Alignment (checked, OCC_E_INVALID): value and out 16 bytes (value_bt_stride a multiple of 4 floats), offs and ref_2d
+ * 8 bytes, offs_stride even: the kernel reads float2 offset pairs and 16-byte pieces of value rows.
  * Fused kernel exists for M=8, D=32, P=4, one level; otherwise OCC_E_UNSUPPORTED.
  */
 int occ_tsa_fused_forward_f32(const float* value, int64_t value_bt_stride, const float* offs,

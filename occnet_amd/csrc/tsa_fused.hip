@@ -87,6 +87,13 @@ extern "C" int occ_tsa_fused_forward_f32(const float* value, int64_t value_bt_st
   OCC_CHECK_ARG(value_bt_stride >= 0, "tsa_fused_forward: negative value stride");
   OCC_CHECK_ARG(offs_stride >= (int64_t)M * 2 * P * 2 && logits_stride >= (int64_t)M * 2 * P,
                 "tsa_fused_forward: row strides smaller than a row");
+  // the kernel reads an offsets row and a reference point as float2, a value row as float4 pieces, and writes float4
+  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(offs) % 8 == 0, "tsa_fused_forward: offs must be 8-byte aligned");
+  OCC_CHECK_ARG(offs_stride % 2 == 0, "tsa_fused_forward: offs row stride must be even");
+  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(value) % 16 == 0 && value_bt_stride % 4 == 0,
+                "tsa_fused_forward: value must be 16-byte aligned");
+  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(ref_2d) % 8 == 0 && reinterpret_cast<uintptr_t>(out) % 16 == 0,
+                "tsa_fused_forward: ref_2d must be 8-byte aligned, out 16-byte aligned");
   OCC_CHECK_ARG((long)bev_h * bev_w * M * D < (1L << 31), "tsa_fused_forward: value map too large");
   if (M != 8 || D != 32 || P != 4) {
     set_error("tsa_fused_forward: no fused kernel for M=%d D=%d P=%d", M, D, P);

@@ -386,11 +386,19 @@ def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_
     (B,Nq,M*2*P), ref_2d (B*2,Nq,1,2).  -> (B, Nq, M*D).
     value_rows (B == 1 only): the queries are a ROW BAND of the BEV — offs / logits / ref_2d / order / the result cover
     Nq < bev_h*bev_w queries (order holds band-local indices) while `value` is the whole (bev_h*bev_w = value_rows)-pixel
-    map: the encoder's row pipeline (plugin/encoder.py)."""
+    map: the encoder's row pipeline (plugin/encoder.py).
+    order: None, or a contiguous int32 (Nq) tensor on value's device that must be a PERMUTATION of arange(Nq): wave r of a
+    batch entry computes query order[r], so only locality depends on it.  Its values are not range-checked (that would cost
+    a device sync): a repeated index leaves another row of the result unwritten, an index outside [0, Nq) reads and writes
+    out of range.
+    The kernel reads float2 offset pairs and 16-byte pieces of value rows: offs must start 8-byte aligned with an even row
+    stride, value 16-byte aligned (any slice of a Linear output at an even column is)."""
     _need_cuda_f32("value", value)
     _need_cuda_f32("ref_2d", ref_2d)
     _need_cuda_f32("offs", offs, contiguous=False)
     _need_cuda_f32("logits", logits, contiguous=False)
+    if offs.dim() != 3 or logits.dim() != 3:
+        raise OccAmdError("tsa_fused_forward: offs and logits must be (B,Nq,...)")
     B, Nq = offs.shape[:2]
     M, D, P = int(num_heads), value.shape[-1], int(num_points)
     Nv = Nq if value_rows is None else int(value_rows)
@@ -413,8 +421,18 @@ def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_
     if tuple(ref_2d.shape) != (B * 2, Nq, 1, 2):
         raise OccAmdError("tsa_fused_forward: ref_2d must be (B*2,Nq,1,2)")
     for n, t, w in (("offs", offs, M * 2 * P * 2), ("logits", logits, M * 2 * P)):
-        if t.shape[-1] != w or t.stride(-1) != 1 or t.stride(0) != Nq * t.stride(1):
+        # (the batch stride of a B == 1 tensor addresses nothing: a row band sliced out of a full-map Linear output keeps
+        # the full map's)
+        if tuple(t.shape[:2]) != (B, Nq) or t.shape[-1] != w or t.stride(-1) != 1 \
+                or (B > 1 and t.stride(0) != Nq * t.stride(1)):
             raise OccAmdError(f"tsa_fused_forward: {n} must be (B,Nq,{w}) with unit inner stride")
+    if offs.data_ptr() % 8 or offs.stride(1) % 2:
+        raise OccAmdError("tsa_fused_forward: offs must be 8-byte aligned with an even row stride (float2 reads)")
+    if value.data_ptr() % 16 or ref_2d.data_ptr() % 8:
+        raise OccAmdError("tsa_fused_forward: value must be 16-byte aligned (and ref_2d 8-byte aligned)")
+    if order is not None and not (isinstance(order, torch.Tensor) and order.dtype == torch.int32 and order.numel() == Nq
+                                  and order.device == value.device and order.is_contiguous()):
+        raise OccAmdError("tsa_fused_forward: order must be a contiguous int32 (Nq) tensor on value's device")
     out = torch.empty((B, Nq, M * D), dtype=torch.float32, device=value.device)
     with torch.cuda.device(value.device), _timed('tsa_fused_forward'):
         rc = _lib.lib().occ_tsa_fused_forward_f32(

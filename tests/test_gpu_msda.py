@@ -139,28 +139,3 @@ def test_generic_forward_never_reads_corners_outside_the_map():
     assert 0.0 < float(touched.float().mean()) < 0.5
     assert torch.equal(dirty.view(B, Lq, M, D)[~touched], clean.view(B, Lq, M, D)[~touched])
 
-
-def test_tsa_fused_never_reads_corners_outside_the_map():
-    """Same property for the fused temporal self-attention gather (its BEV value maps)."""
-    from occnet_amd import ext
-    g = torch.Generator().manual_seed(22)
-    B, M, D, P, bh, bw = 1, 8, 32, 4, 12, 14
-    Nq = bh * bw
-    value = torch.randn(B * 2, Nq, M, D, generator=g)
-    offs = torch.randn(B, Nq, M * 2 * P * 2, generator=g) * 4.0
-    logits = torch.randn(B, Nq, M * 2 * P, generator=g)
-    ref = torch.rand(B * 2, Nq, 1, 2, generator=g)
-    args = (offs.cuda(), logits.cuda(), ref.cuda(), bh, bw, M, P)
-    clean = ext.tsa_fused_forward(value.cuda(), *args).view(B, Nq, M, D)
-    value[:, 0] = float('inf')
-    value[:, 0, :, ::2] = float('nan')
-    dirty = ext.tsa_fused_forward(value.cuda(), *args).view(B, Nq, M, D)
-    touched = ~torch.isfinite(dirty).all(-1)
-    assert 0.0 < float(touched.float().mean()) < 0.6
-    assert torch.equal(dirty[~touched], clean[~touched])
-    # rows that cannot reach pixel (0, 0): all of a head's 8 samples at h_im >= 1 or w_im >= 1
-    o = offs.view(B, Nq, M, 2, P, 2)
-    lx = (ref.view(B, 2, Nq, 1, 1, 2)[..., 0].permute(0, 2, 3, 1, 4) + o[..., 0] / bw) * bw - 0.5   # (B,Nq,M,2,P)
-    ly = (ref.view(B, 2, Nq, 1, 1, 2)[..., 1].permute(0, 2, 3, 1, 4) + o[..., 1] / bh) * bh - 0.5
-    may = ((lx > -1) & (lx < 1) & (ly > -1) & (ly < 1)).flatten(3).any(-1)
-    assert not bool((touched.cpu() & ~may).any())
