@@ -31,6 +31,13 @@ def declared_symbols(header=HEADER_PATH):
     return sorted(set(re.findall(r"\b(occ_[a-z0-9_]+)\s*\(", src)))
 
 
+# the size queries of the header that return int64_t (ctypes assumes int)
+_INT64_RESULTS = (
+    "occ_ms_deform_attn_backward_workspace_bytes", "occ_sca_fused_backward_workspace_bytes", "occ_conv3d_heads_pack_bytes",
+    "occ_linear_chain_packed_bytes", "occ_linear_wgrad_workspace_bytes", "occ_conv3d_wgrad_workspace_bytes",
+    "occ_bias_act_bwd_partial_floats", "occ_dropout_add_ln_bwd_partial_floats", "occ_conv1x1_wgrad_workspace_bytes",
+    "occ_ray_metrics_state_words", "occ_ray_metrics_workspace_bytes")
+
 _lib = None
 ABI = 3     # include/occnet_amd.h: bumped whenever a signature changes (2: range scales of the fp16 value rows; 3: their weight terms in device memory)
 
@@ -45,6 +52,8 @@ def lib():
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.occ_last_error.restype = ctypes.c_char_p
         _lib.occ_abi_version.restype = ctypes.c_int
+        for name in _INT64_RESULTS:
+            getattr(_lib, name).restype = ctypes.c_int64
         if _lib.occ_abi_version() != ABI:
             got, _lib = _lib.occ_abi_version(), None
             raise OccAmdError(f"{LIB_PATH} has C ABI {got}, this package binds ABI {ABI}: rebuild it "

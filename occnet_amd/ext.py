@@ -129,7 +129,6 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
             grad_output.numel() != B * Lq * M * D):
         raise OccAmdError("ms_deform_attn_backward: inconsistent shapes")
     lib = _lib.lib()
-    lib.occ_ms_deform_attn_backward_workspace_bytes.restype = ctypes.c_int64
     # scratch of the atomic-free grad_value path from torch's caching allocator (not hipMallocAsync behind its back);
     # freed back to the pool when this call returns — stream-ordered, the kernels are already enqueued
     need = int(lib.occ_ms_deform_attn_backward_workspace_bytes(i32(B), i32(S), i32(M), i32(D), i32(L), i32(Lq),
@@ -294,7 +293,6 @@ def sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, re
 def sca_fused_backward_workspace_bytes(B, NC, S, M, D, L, P, Nq):
     """Bytes of scratch sca_fused_backward takes for these shapes (0: no backward kernel for them)."""
     lib = _lib.lib()
-    lib.occ_sca_fused_backward_workspace_bytes.restype = ctypes.c_int64
     return int(lib.occ_sca_fused_backward_workspace_bytes(i32(B), i32(NC), i32(S), i32(M), i32(D), i32(L), i32(P),
                                                           i32(Nq)))
 
@@ -521,7 +519,6 @@ def conv3d_heads_pack(w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow,
             or b1_occ.numel() != hidden or b1_flow.numel() != hidden or b2_occ.numel() != ncls or b2_flow.numel() != 2):
         raise OccAmdError("conv3d_heads_pack: inconsistent weight shapes")
     lib = _lib.lib()
-    lib.occ_conv3d_heads_pack_bytes.restype = ctypes.c_int64
     packed = torch.empty(int(lib.occ_conv3d_heads_pack_bytes()), dtype=torch.uint8, device=w1_occ.device)
     with torch.cuda.device(w1_occ.device):
         rc = lib.occ_conv3d_heads_pack(*[ptr(t) for t in ts], ptr(packed), i32(C), i32(hidden), i32(ncls),
@@ -989,7 +986,6 @@ def linear_chain_pack(weights):
     if hit is not None:
         return hit[1]
     lib = _lib.lib()
-    lib.occ_linear_chain_packed_bytes.restype = ctypes.c_int64
     sizes = []
     for w in weights:
         _need_cuda_f32("weight", w)
@@ -1194,7 +1190,6 @@ def linear_wgrad(dy, x, with_bias=True):
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     db = torch.empty((N,), dtype=torch.float32, device=dy.device) if with_bias else None
     lib = _lib.lib()
-    lib.occ_linear_wgrad_workspace_bytes.restype = ctypes.c_int64
     nbytes = int(lib.occ_linear_wgrad_workspace_bytes(i32(M), i32(N), i32(K)))
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dy.device)
     with torch.cuda.device(dy.device), _timed('linear_wgrad'):
@@ -1253,7 +1248,6 @@ class Conv3dX3Function(torch.autograd.Function):
             xp = torch.nn.functional.pad(xc, (0, 0, 1, 1, 1, 1, 1, 1)).contiguous()      # (B, Y+2, X+2, Z+2, cin)
             gp = torch.nn.functional.pad(gout, (0, 0, 1, 1, 1, 1, 1, 1)).contiguous()    # (B, Y+2, X+2, Z+2, 32)
             lib = _lib.lib()
-            lib.occ_conv3d_wgrad_workspace_bytes.restype = ctypes.c_int64
             nbytes = int(lib.occ_conv3d_wgrad_workspace_bytes(i32(B), i32(Z), i32(Y), i32(X), i32(cin)))
             if nbytes <= 0:
                 raise OccAmdUnsupported("conv3d wgrad: grid beyond the kernel's 32-bit row range")
@@ -1447,7 +1441,6 @@ class DropoutAddLayerNormFunction(torch.autograd.Function):
         rows, C = z.shape
         gy2 = gy.reshape(rows, C).contiguous()
         lib = _lib.lib()
-        lib.occ_dropout_add_ln_bwd_partial_floats.restype = ctypes.c_int64
         partial = torch.empty(int(lib.occ_dropout_add_ln_bwd_partial_floats(i64(rows), i32(C))), dtype=torch.float32,
                               device=z.device)
         gres = torch.empty_like(z)
@@ -1544,18 +1537,14 @@ _SEM_DTYPE_CODES = {torch.uint8: 0, torch.int64: 1}
 
 def ray_metrics_state_words(free_id=16):
     """int64 words of the RayIoU / mAVE state for classes 0..free_id (14 per class; layout: include/occnet_amd.h)."""
-    fn = _lib.lib().occ_ray_metrics_state_words
-    fn.restype = ctypes.c_int64
-    n = int(fn(i32(free_id)))
+    n = int(_lib.lib().occ_ray_metrics_state_words(i32(free_id)))
     if n <= 0:
         raise OccAmdError(f"ray_metrics_state_words: free_id must be 1..31, got {free_id}")
     return n
 
 
 def ray_metrics_workspace_bytes(B, X, Y, Z):
-    fn = _lib.lib().occ_ray_metrics_workspace_bytes
-    fn.restype = ctypes.c_int64
-    return int(fn(i32(B), i32(X), i32(Y), i32(Z)))
+    return int(_lib.lib().occ_ray_metrics_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z)))
 
 
 def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins, rays, pc_min, voxel_size, free_id=16,
@@ -1610,12 +1599,16 @@ def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins,
     return (rows_pred, rows_gt) if return_rays else None
 
 
+def _need_cl_bf16(what, name, t):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
+            and t.is_contiguous(memory_format=torch.channels_last)):
+        raise OccAmdUnsupported(f"{what}: {name} must be a channels_last bfloat16 device tensor")
+
+
 def bias_act_nhwc_(x, bias, residual=None, relu=True):
     """In place x = relu?(x + bias[c] (+ residual)) on a channels_last bf16 (N, C, H, W) tensor (memory
     order N, H, W, C).  bias (C) float32.  Returns x."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported("bias_act_nhwc_: x must be a channels_last bfloat16 device tensor")
+    _need_cl_bf16("bias_act_nhwc_", "x", x)
     _need_cuda_f32("bias", bias)
     N, C, H, W = x.shape
     if bias.numel() != C:
@@ -1640,7 +1633,6 @@ def bias_act_bwd_nhwc(grad_y, y=None, relu=True):
     N, C, H, W = grad_y.shape
     rows = N * H * W
     lib = _lib.lib()
-    lib.occ_bias_act_bwd_partial_floats.restype = ctypes.c_int64
     nfl = int(lib.occ_bias_act_bwd_partial_floats(i64(rows), i32(C)))
     if nfl <= 0:
         raise OccAmdUnsupported(f"bias_act_bwd_nhwc: no kernel for C={C}")
@@ -1752,9 +1744,7 @@ def stem_conv7x7_pool_u8(x_u8, weight_frag, bias, mean, std, to_rgb=False, size_
 def bias_relu_maxpool_nhwc(y, bias):
     """max_pool2d(relu(y + bias), 3, stride 2, padding 1) in one launch on a channels_last bf16 activation
     (the ResNet stem's tail).  y (N, C, H, W) channels_last bf16 raw convolution output; bias (C) f32."""
-    if not (y.is_cuda and y.dtype == torch.bfloat16 and y.dim() == 4
-            and y.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported("bias_relu_maxpool_nhwc: y must be a channels_last bfloat16 device tensor")
+    _need_cl_bf16("bias_relu_maxpool_nhwc", "y", y)
     _need_cuda_f32("bias", bias)
     N, C, H, W = y.shape
     if bias.numel() != C:
@@ -1786,9 +1776,7 @@ def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, resi
     variant: None = the launcher's choice; an int forces the kernel (occ_conv1x1_nhwc_bf16_variant: 1 = tiled, 2 =
     activation-resident, 22 / 24 = resident with the 64- / 128-row tile); OccAmdUnsupported where the shape has none.
     _timing: the kernel_timing entry the launch is booked under (conv1x1_dgrad_nhwc books the whole call under its own)."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported("conv1x1_nhwc: x must be a channels_last bfloat16 device tensor")
+    _need_cl_bf16("conv1x1_nhwc", "x", x)
     _need_cuda_f32("bias", bias)
     N, Cin, H, W = x.shape
     Cout = bias.numel()
@@ -1806,25 +1794,13 @@ def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, resi
                                      residual.is_contiguous(memory_format=torch.channels_last)):
         raise OccAmdUnsupported("conv1x1_nhwc: residual must match the output (channels_last bfloat16)")
     with torch.cuda.device(x.device), _timed(_timing):
-        if variant is None:
-            rc = _lib.lib().occ_conv1x1_nhwc_bf16(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
-                                                  i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
-                                                  i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
-                                                  stream_ptr(x.device))
-        else:
-            rc = _lib.lib().occ_conv1x1_nhwc_bf16_variant(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
-                                                          i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
-                                                          i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
-                                                          i32(int(variant)), stream_ptr(x.device))
+        rc = _lib.lib().occ_conv1x1_nhwc_bf16_variant(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
+                                                      i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
+                                                      i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
+                                                      i32(0 if variant is None else int(variant)), stream_ptr(x.device))
     _note_flops(_timing, 2.0 * N * Ho * Wo * Cin * Cout)
     _lib.check(rc, "conv1x1_nhwc")
     return out
-
-
-def _need_cl_bf16(what, name, t):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
-            and t.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported(f"{what}: {name} must be a channels_last bfloat16 device tensor")
 
 
 def conv1x1_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
@@ -1847,7 +1823,6 @@ def conv1x1_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
     if sp < 0 or (splits is not None and sp == 0):
         raise OccAmdError("conv1x1_wgrad_nhwc: splits must be None or a positive int")
     lib = _lib.lib()
-    lib.occ_conv1x1_wgrad_workspace_bytes.restype = ctypes.c_int64
     nbytes = int(lib.occ_conv1x1_wgrad_workspace_bytes(i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp)))
     if nbytes <= 0:
         raise OccAmdUnsupported("conv1x1_wgrad_nhwc: needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048 "
@@ -1922,9 +1897,7 @@ def bottleneck64_pack(w1, b1, w2, b2, w3, b3, wds=None, bds=None):
 def bottleneck64_nhwc(x, pack):
     """One whole stride-1 ResNet bottleneck (64 mid channels) on a channels_last bf16 activation, one launch.
     x (N, Cin, H, W) channels_last bf16; pack from bottleneck64_pack -> (N, 256, H, W) channels_last bf16."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported("bottleneck64_nhwc: x must be a channels_last bfloat16 device tensor")
+    _need_cl_bf16("bottleneck64_nhwc", "x", x)
     N, Cin, H, W = x.shape
     if Cin != pack['cin']:
         raise OccAmdError("bottleneck64_nhwc: x has %d channels, the pack was built for %d" % (Cin, pack['cin']))
@@ -1962,9 +1935,7 @@ def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None, varia
     variant: None = the launcher's choice; an int forces the tile (occ_conv3x3_nhwc_bf16_variant: 10 * NT + RT for
     (2 * RT) x 16 pixels x (128 * NT) channels per block; stride 1: 12, 13, 14, 16, 18, 22, 23, 24; stride 2: 12, 13,
     22; 0 = the launcher's choice through the same entry point)."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported("conv3x3_nhwc: x must be a channels_last bfloat16 device tensor")
+    _need_cl_bf16("conv3x3_nhwc", "x", x)
     _need_cuda_f32("bias", bias)
     N, Cin, H, W = x.shape
     if w_packed.numel() != cout * Cin * 9 or bias.numel() != cout:
@@ -1977,19 +1948,10 @@ def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None, varia
     out = torch.empty((N, cout, (H - 1) // st + 1, (W - 1) // st + 1), dtype=torch.bfloat16, device=x.device,
                       memory_format=torch.channels_last)
     with torch.cuda.device(x.device), _timed('bb_conv3x3'):
-        if variant is not None:
-            rc = _lib.lib().occ_conv3x3_nhwc_bf16_variant(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
-                                                          i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
-                                                          ptr(amax), i32(variant),
-                                                          stream_ptr(x.device))
-        elif amax is None:
-            rc = _lib.lib().occ_conv3x3_nhwc_bf16(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
-                                                  i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
-                                                  stream_ptr(x.device))
-        else:
-            rc = _lib.lib().occ_conv3x3_nhwc_bf16_amax(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
-                                                       i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
-                                                       ptr(amax), stream_ptr(x.device))
+        rc = _lib.lib().occ_conv3x3_nhwc_bf16_variant(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
+                                                      i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
+                                                      ptr(amax), i32(0 if variant is None else int(variant)),
+                                                      stream_ptr(x.device))
     _note_flops('bb_conv3x3', 2.0 * N * out.shape[2] * out.shape[3] * 9 * Cin * cout)
     _lib.check(rc, "conv3x3_nhwc")
     return out
@@ -2009,9 +1971,7 @@ def conv3x3_conv1x1_nhwc(x, w3_packed, b2, cmid, w1_frag, b3, residual, stride=1
     -> (N, Cout, Ho, Wo) channels_last bf16, Ho = (H-1)//stride + 1.
     variant: None = the tile conv3x3_conv1x1_pick returns (OccAmdUnsupported where that is 0); an int forces the 3x3 tile
     id.  Bit-identical to conv1x1_nhwc(conv3x3_nhwc(x, ..., relu=True, variant=v), ..., relu=True, variant=2)."""
-    if not (x.is_cuda and x.dtype == torch.bfloat16 and x.dim() == 4
-            and x.is_contiguous(memory_format=torch.channels_last)):
-        raise OccAmdUnsupported("conv3x3_conv1x1_nhwc: x must be a channels_last bfloat16 device tensor")
+    _need_cl_bf16("conv3x3_conv1x1_nhwc", "x", x)
     _need_cuda_f32("b2", b2)
     _need_cuda_f32("b3", b3)
     N, Cin, H, W = x.shape

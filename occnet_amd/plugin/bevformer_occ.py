@@ -152,27 +152,25 @@ class BEVFormerOcc(BaseModule):
                 out.append(f.view(int(B / len_queue), len_queue, int(BN / B), C, H, W))
             else:
                 out.append(f.view(B, int(BN / B), C, H, W))
-                # max|x| over the maps, accumulated by the plan's FPN output convolutions (backbone.py): rides on the views
+                # max|x| over the maps, accumulated by the plan's FPN output convolutions (backbone_plan.py): rides on the views
                 am = ext.absmax_of(f)
                 if am is not None:
                     ext.attach_absmax(out[-1], am)
         return out
 
-    def enable_fused_backbone(self, dtype=torch.bfloat16, fused_ops=False, hip_tail=True, use_graph=False,
-                              fused_bottleneck=True):
+    def enable_fused_backbone(self, dtype=torch.bfloat16, hip_tail=True, use_graph=False, fused_bottleneck=True):
         """Inference-only: run ResNet+FPN through FusedInferenceBackbone (eval BN folded into the
-        convolutions, NHWC, MIOpen's fused conv+bias(+add)+ReLU).  Call again after changing backbone
-        weights; pass dtype=None to disable."""
+        convolutions, NHWC; with hip_tail on bf16 the stem, the 64-channel bottlenecks and the 1x1 / 3x3
+        convolutions run on this repository's kernels with bias, residual and ReLU in their epilogues).  Call again
+        after changing backbone weights; pass dtype=None to disable."""
         from .backbone import FusedInferenceBackbone
         object.__setattr__(self, '_inference_backbone', None)
         object.__setattr__(self, '_inference_backbone_args', dict(
-            dtype=dtype, fused_ops=fused_ops, hip_tail=hip_tail, use_graph=use_graph,
-            fused_bottleneck=fused_bottleneck))
+            dtype=dtype, hip_tail=hip_tail, use_graph=use_graph, fused_bottleneck=fused_bottleneck))
         # folded while training (no explicit .train() call needed for that): the sources may move before the first forward
         object.__setattr__(self, '_plan_dirty', bool(self.training))
         if dtype is not None:
-            plan = FusedInferenceBackbone(self.img_backbone, self.img_neck, dtype=dtype,
-                                          fused_ops=fused_ops, hip_tail=hip_tail,
+            plan = FusedInferenceBackbone(self.img_backbone, self.img_neck, dtype=dtype, hip_tail=hip_tail,
                                           fused_bottleneck=fused_bottleneck)
             plan.use_graph = use_graph
             plan.built_epoch = cache_epoch()

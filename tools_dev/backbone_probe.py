@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--mode", choices=["autocast", "bf16", "fp16", "f32", "plan", "plan_fused", "plan_fused_fp16"], default="autocast")
+ap.add_argument("--mode", choices=["autocast", "bf16", "fp16", "f32", "plan"], default="autocast")
 ap.add_argument("--benchmark", type=int, default=0)
 ap.add_argument("--nhwc", type=int, default=1)
 ap.add_argument("--iters", type=int, default=10)
@@ -31,7 +31,7 @@ B, N, C, H, W = img.shape
 x = img.reshape(B * N, C, H, W)
 bb, neck = model.img_backbone, model.img_neck
 plan = None
-if args.mode.startswith("plan"):
+if args.mode == "plan":
     from occnet_amd.plugin.backbone import FusedInferenceBackbone
     # non-trivial BN statistics so the fold is exercised
     g = torch.Generator().manual_seed(0)
@@ -41,8 +41,7 @@ if args.mode.startswith("plan"):
             m.running_var.copy_(torch.rand(m.running_var.shape, generator=g).cuda() * 0.5 + 0.75)
     with torch.no_grad():
         ref = [t.float() for t in neck(bb(x[:1]))]
-    plan = FusedInferenceBackbone(bb, neck, dtype=torch.float16 if args.mode.endswith("fp16") else torch.bfloat16,
-                                  fused_ops="fused" in args.mode)
+    plan = FusedInferenceBackbone(bb, neck, dtype=torch.bfloat16)
     with torch.no_grad():
         got = plan(x[:1])
     for a, b in zip(ref, got):
