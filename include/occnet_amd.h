@@ -28,6 +28,8 @@
  *   occ_linear_f32                   <- the nn.Linear / FFN / LayerNorm call sites of a BEVFormerLayer
  *   occ_dvr_render_forward_f32       <- dvr.render_forward, tools/ray_iou/lib/dvr/dvr.cu:70-388
  *   occ_ray_metrics_accumulate       <- process_one_sample + main + calc_metrics, P/datasets/ray_metrics.py:89-257
+ *   occ_heads_loss_fwd_f32 / _bwd_f32 <- the heads (transformer_occ.py:132-141,318-319) + BEVFormerOccHead.loss /
+ *        loss_single, P/bevformer/dense_heads/bevformer_occ_head.py:163-196, and their autograd backward
  */
 #ifndef OCCNET_AMD_H_
 #define OCCNET_AMD_H_
@@ -725,6 +727,47 @@ int occ_ray_metrics_accumulate(const void* sem_pred, int sem_pred_dtype, const f
                                int64_t* state, float* rows_pred, float* rows_gt, void* workspace,
                                int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R,
                                void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * (f) Training tail: both occupancy heads AND their losses as one node (csrc/occ_heads_loss.hip) — the reference's
+ * predicter / flow_predicter (transformer_occ.py:132-141,318-319) followed by BEVFormerOccHead.loss / loss_single
+ * (bevformer_occ_head.py:163-196: CrossEntropyLoss on the logits, L1Loss on the flow) and the autograd graph between
+ * them.  Nothing but the inputs is kept between forward and backward: the backward recomputes each 32-voxel tile.
+ *   feat (n_rows, 32) f32, 16-byte aligned; the eight head tensors of occ_occ_heads_f32
+ *   labels (n_rows) class ids, dtype code 0 = uint8, 1 = int64; flow_gt (n_rows, 2) f32
+ *   mask NULL or (n_rows) bool bytes: multiplies the cross-entropy terms; class_weight NULL or (num_classes) f32
+ *   a voxel whose label equals ignore_index contributes 0 to loss_occ — and so does a label outside [0, num_classes)
+ *   (DEVIATION: torch raises a device assert there; nothing is read through such a label).  The flow term is unmasked.
+ *   Denominators (bricks.CrossEntropyLoss / L1Loss): occ — mask.sum() when a mask is given (either reduction: the
+ *   avg_factor rule; 0 / 0 stays NaN), else n_rows for reduction_mean = 1 and 1 for 0; flow — 2 n_rows or 1.
+ *   Loss weights stay with the caller.
+ * forward:  losses[0] = loss_occ, losses[1] = loss_flow, losses[2] = the occ denominator (three DEVICE floats; heads in
+ *   bf16x3 arithmetic as occ_occ_heads_decode_f32(exact_f32 = 0)); one launch + a one-wave finalise.
+ * backward: grad_losses = the two incoming gradient scalars, occ_denom = losses + 2 of the forward, both DEVICE
+ *   pointers (no host synchronisation); dfeat (n_rows, 32) fully written, or NULL; each of the eight parameter gradients
+ *   fully written, or NULL (all NULL: the weight-gradient products are skipped).  Exact f32 (v_mfma_f32_32x32x2_f32); one
+ *   launch + a small reduce; no float atomics: bit-identical run to run.
+ * workspace: occ_heads_loss_workspace_bytes(n_rows, num_classes, max_blocks) bytes, 16-byte aligned, uninitialised (0:
+ *   unsupported or invalid arguments).  max_blocks: 0 = the launcher's grid, > 0 caps the grid of every launch (a small
+ *   cap makes each wave walk several tiles: tests), < 0 OCC_E_INVALID.  The grids depend on n_rows and max_blocks only.
+ * C == 32, hidden == 64, num_classes + 2 <= 32, otherwise OCC_E_UNSUPPORTED.  Argument checks precede every launch; no
+ * allocation; everything on `stream`.
+ */
+int64_t occ_heads_loss_workspace_bytes(int64_t n_rows, int num_classes, int max_blocks);
+int occ_heads_loss_fwd_f32(const float* feat, const float* w1_occ, const float* b1_occ, const float* w2_occ,
+                           const float* b2_occ, const float* w1_flow, const float* b1_flow, const float* w2_flow,
+                           const float* b2_flow, const void* labels, int labels_dtype, const float* flow_gt,
+                           const uint8_t* mask, const float* class_weight, int64_t ignore_index, int reduction_mean,
+                           float* losses, void* workspace, int64_t workspace_bytes, int64_t n_rows, int C, int hidden,
+                           int num_classes, int max_blocks, void* stream);
+int occ_heads_loss_bwd_f32(const float* feat, const float* w1_occ, const float* b1_occ, const float* w2_occ,
+                           const float* b2_occ, const float* w1_flow, const float* b1_flow, const float* w2_flow,
+                           const float* b2_flow, const void* labels, int labels_dtype, const float* flow_gt,
+                           const uint8_t* mask, const float* class_weight, int64_t ignore_index, int reduction_mean,
+                           const float* grad_losses, const float* occ_denom, float* dfeat, float* dw1_occ,
+                           float* db1_occ, float* dw2_occ, float* db2_occ, float* dw1_flow, float* db1_flow,
+                           float* dw2_flow, float* db2_flow, void* workspace, int64_t workspace_bytes, int64_t n_rows,
+                           int C, int hidden, int num_classes, int max_blocks, void* stream);
 
 #ifdef __cplusplus
 }

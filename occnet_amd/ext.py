@@ -1599,6 +1599,131 @@ def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins,
     return (rows_pred, rows_gt) if return_rays else None
 
 
+_HEADS_LOSS_PARAMS = ("w1_occ", "b1_occ", "w2_occ", "b2_occ", "w1_flow", "b1_flow", "w2_flow", "b2_flow")
+
+
+def _heads_loss_check(what, feat, params, labels, flow_gt, mask, class_weight, reduction):
+    """Device, dtype, contiguity, shape and alignment conditions of the fused heads + loss node -> (n_rows, num_classes);
+    OccAmdUnsupported otherwise (the caller then runs the module chain)."""
+    def bad(msg):
+        raise OccAmdUnsupported(f"{what}: {msg}")
+    for n, t in (("feat", feat), ("flow_gt", flow_gt)) + tuple(zip(_HEADS_LOSS_PARAMS, params)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            bad(f"{n} must be a contiguous float32 device tensor")
+    if reduction not in ('mean', 'sum'):
+        bad(f"reduction {reduction!r} is not covered (mean, sum)")
+    w1o, b1o, w2o, b2o, w1f, b1f, w2f, b2f = params
+    C = feat.shape[-1] if feat.dim() else 0
+    ncls = w2o.shape[0] if w2o.dim() == 2 else 0
+    if (C != 32 or tuple(w1o.shape) != (64, 32) or tuple(w1f.shape) != (64, 32) or ncls < 1 or ncls > 30
+            or tuple(w2o.shape) != (ncls, 64) or tuple(w2f.shape) != (2, 64) or b1o.numel() != 64 or b1f.numel() != 64
+            or b2o.numel() != ncls or b2f.numel() != 2):
+        bad("needs C = 32, hidden = 64 and num_classes <= 30")
+    n_rows = feat.numel() // 32
+    if n_rows < 1:
+        bad("no rows")
+    if not (isinstance(labels, torch.Tensor) and labels.is_cuda and labels.dtype in _SEM_DTYPE_CODES
+            and labels.is_contiguous() and labels.numel() == n_rows):
+        bad("labels must be a contiguous uint8 or int64 device tensor with one entry per row")
+    if flow_gt.numel() != 2 * n_rows:
+        bad("flow_gt must hold (n_rows, 2) values")
+    if mask is not None and not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
+                                 and mask.is_contiguous() and mask.numel() == n_rows):
+        bad("mask must be a contiguous bool or uint8 device tensor with one entry per row")
+    if class_weight is not None and not (isinstance(class_weight, torch.Tensor) and class_weight.is_cuda
+                                         and class_weight.dtype == torch.float32 and class_weight.is_contiguous()
+                                         and class_weight.numel() == ncls):
+        bad("class_weight must be a contiguous float32 device tensor of num_classes entries")
+    if feat.data_ptr() % 16 or flow_gt.data_ptr() % 8:
+        bad("feat must be 16-byte aligned, flow_gt 8-byte aligned")
+    return n_rows, ncls
+
+
+def _heads_loss_workspace(n_rows, ncls, max_blocks, device):
+    nbytes = int(_lib.lib().occ_heads_loss_workspace_bytes(i64(n_rows), i32(ncls), i32(max_blocks)))
+    if nbytes <= 0:
+        raise OccAmdUnsupported(f"heads_loss: no kernel for num_classes={ncls}, max_blocks={max_blocks}")
+    return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
+
+
+def heads_loss_forward(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b2_flow, labels, flow_gt,
+                       mask=None, class_weight=None, ignore_index=-100, reduction='mean', max_blocks=0):
+    """Both decoder heads + CrossEntropyLoss + L1Loss in one launch and a one-wave finalise (csrc/occ_heads_loss.hip):
+    feat (..., 32), labels (...) uint8 / int64, flow_gt (..., 2), mask None or (...) bool, class_weight None or (ncls)
+    -> 3 device floats: loss_occ, loss_flow (both WITHOUT loss_weight), the occ denominator."""
+    params = (w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b2_flow)
+    n_rows, ncls = _heads_loss_check("heads_loss_forward", feat, params, labels, flow_gt, mask, class_weight, reduction)
+    ws, nbytes = _heads_loss_workspace(n_rows, ncls, max_blocks, feat.device)
+    losses = torch.empty(3, dtype=torch.float32, device=feat.device)
+    with torch.cuda.device(feat.device), _timed('heads_loss_fwd'):
+        rc = _lib.lib().occ_heads_loss_fwd_f32(
+            ptr(feat), *[ptr(t) for t in params], ptr(labels), i32(_SEM_DTYPE_CODES[labels.dtype]), ptr(flow_gt), ptr(mask),
+            ptr(class_weight), i64(int(ignore_index)), i32(1 if reduction == 'mean' else 0), ptr(losses), ptr(ws),
+            i64(nbytes), i64(n_rows), i32(32), i32(64), i32(ncls), i32(max_blocks), stream_ptr(feat.device))
+    _lib.check(rc, "heads_loss_forward")
+    return losses
+
+
+def heads_loss_backward(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b2_flow, labels, flow_gt,
+                        mask, class_weight, ignore_index, reduction, grad_losses, occ_denom, need_feat=True,
+                        need_params=(True,) * 8, max_blocks=0):
+    """Gradients of heads_loss_forward: grad_losses (2) and occ_denom (1) device floats (no host read) ->
+    (dfeat or None, [the eight parameter gradients, None where need_params is False]).  One launch + a small reduce."""
+    params = (w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b2_flow)
+    n_rows, ncls = _heads_loss_check("heads_loss_backward", feat, params, labels, flow_gt, mask, class_weight, reduction)
+    for n, t, k in (("grad_losses", grad_losses, 2), ("occ_denom", occ_denom, 1)):
+        if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == k):
+            raise OccAmdUnsupported(f"heads_loss_backward: {n} must be {k} contiguous float32 device value(s)")
+    ws, nbytes = _heads_loss_workspace(n_rows, ncls, max_blocks, feat.device)
+    dfeat = torch.empty_like(feat) if need_feat else None
+    grads = [torch.empty_like(p) if need else None for p, need in zip(params, need_params)]
+    with torch.cuda.device(feat.device), _timed('heads_loss_bwd'):
+        rc = _lib.lib().occ_heads_loss_bwd_f32(
+            ptr(feat), *[ptr(t) for t in params], ptr(labels), i32(_SEM_DTYPE_CODES[labels.dtype]), ptr(flow_gt), ptr(mask),
+            ptr(class_weight), i64(int(ignore_index)), i32(1 if reduction == 'mean' else 0), ptr(grad_losses),
+            ptr(occ_denom), ptr(dfeat), *[ptr(g) for g in grads], ptr(ws), i64(nbytes), i64(n_rows), i32(32), i32(64),
+            i32(ncls), i32(max_blocks), stream_ptr(feat.device))
+    _lib.check(rc, "heads_loss_backward")
+    return dfeat, grads
+
+
+class OccHeadsLossFunction(torch.autograd.Function):
+    """(loss_occ, loss_flow) = CrossEntropyLoss / L1Loss of the two decoder heads applied to feat, as ONE autograd node
+    (csrc/occ_heads_loss.hip): the training-mode replacement for predicter / flow_predicter (reference
+    transformer_occ.py:132-141,318-319) followed by BEVFormerOccHead.loss_single (bevformer_occ_head.py:163-196).  Saves its
+    tensor inputs and the occ denominator, nothing else: the backward recomputes the hidden layers tile by tile.  The losses
+    carry no loss_weight.  A label outside [0, num_classes) other than ignore_index contributes nothing (torch asserts)."""
+
+    @staticmethod
+    def forward(ctx, feat, w1o, b1o, w2o, b2o, w1f, b1f, w2f, b2f, labels, flow_gt, mask, class_weight, ignore_index,
+                reduction, max_blocks=0):
+        losses = heads_loss_forward(feat, w1o, b1o, w2o, b2o, w1f, b1f, w2f, b2f, labels, flow_gt, mask, class_weight,
+                                    ignore_index, reduction, max_blocks)
+        ctx.save_for_backward(feat, w1o, b1o, w2o, b2o, w1f, b1f, w2f, b2f, labels, flow_gt, mask, class_weight, losses[2:])
+        ctx.args = (int(ignore_index), reduction, int(max_blocks))
+        return losses[0], losses[1]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_occ, g_flow):
+        *ins, denom = ctx.saved_tensors
+        ignore_index, reduction, max_blocks = ctx.args
+        dev = ins[0].device
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        g = torch.stack([zero if t is None else t.to(device=dev, dtype=torch.float32).reshape(()) for t in (g_occ, g_flow)])
+        need = ctx.needs_input_grad
+        dfeat, grads = heads_loss_backward(*ins, ignore_index, reduction, g, denom, need_feat=need[0],
+                                           need_params=tuple(need[1:9]), max_blocks=max_blocks)
+        return (dfeat, *grads, None, None, None, None, None, None, None)
+
+
+def heads_loss(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b2_flow, labels, flow_gt, mask=None,
+               class_weight=None, ignore_index=-100, reduction='mean', max_blocks=0):
+    """Differentiable (loss_occ, loss_flow) of the decoder features (OccHeadsLossFunction); max_blocks caps the grids."""
+    return OccHeadsLossFunction.apply(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b2_flow, labels,
+                                      flow_gt, mask, class_weight, ignore_index, reduction, max_blocks)
+
+
 def _need_cl_bf16(what, name, t):
     if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
             and t.is_contiguous(memory_format=torch.channels_last)):

@@ -228,6 +228,8 @@ class BEVFormerOcc(BaseModule):
 
     def forward_pts_train(self, pts_feats, gt_bboxes_3d, gt_labels_3d, voxel_semantics, voxel_flow,
                           mask_camera, img_metas, gt_bboxes_ignore=None, prev_bev=None):
+        if getattr(self.pts_bbox_head, 'fused_loss', False):     # heads + losses as one node (OCC_TRAIN_FUSED_LOSS)
+            return self.pts_bbox_head.forward_loss(pts_feats, img_metas, prev_bev, voxel_semantics, voxel_flow, mask_camera)
         outs = self.pts_bbox_head(pts_feats, img_metas, prev_bev)
         return self.pts_bbox_head.loss(voxel_semantics, voxel_flow, mask_camera, outs,
                                        img_metas=img_metas)

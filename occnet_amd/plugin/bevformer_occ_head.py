@@ -5,16 +5,23 @@ Mirror of the reference's projects/mmdet3d_plugin/bevformer/dense_heads/bevforme
 test_cfg through **kwargs and reading kwargs['num_classes'] —, `bev_embedding`,
 `positional_encoding`, `transformer` attribute names, forward / loss / get_occ contracts).
 """
+import os
+
 import torch
 import torch.nn as nn
 
 from .. import cache_epoch
-from .bricks import BaseModule
+from .._lib import OccAmdUnsupported
+from .bricks import BaseModule, CrossEntropyLoss, L1Loss
 from .registry import HEADS, build_loss, build_positional_encoding, build_transformer
 
 
 @HEADS.register_module()
 class BEVFormerOccHead(BaseModule):
+
+    # training: heads + both losses as ONE autograd node (ext.OccHeadsLossFunction, csrc/occ_heads_loss.hip) instead of the
+    # two Sequential heads, F.cross_entropy and the elementwise L1 on materialised logits; opt-in (OCC_TRAIN_FUSED_LOSS=1)
+    fused_loss = os.environ.get("OCC_TRAIN_FUSED_LOSS", "0") == "1"
 
     def __init__(self, *args, with_box_refine=False, as_two_stage=False, transformer=None,
                  bbox_coder=None, num_cls_fcs=2, code_weights=None,
@@ -64,16 +71,20 @@ class BEVFormerOccHead(BaseModule):
             object.__setattr__(self, '_pos_val', bev_pos)
         return bev_pos
 
-    def forward(self, mlvl_feats, img_metas, prev_bev=None, only_bev=False, test=False):
-        """mlvl_feats: list of (B, N, C, H, W) -> {'bev_embed','occ','flow'}; with only_bev the
-        (bs, H*W, C) BEV embedding alone (history frames)."""
+    def _bev_inputs(self, mlvl_feats):
+        """-> (bev_queries, bev_pos, grid_length) of a forward pass over mlvl_feats."""
         bs = mlvl_feats[0].shape[0]
         # the reference takes the feature dtype (bevformer_occ_head.py:118); the MI355X hot path always
         # computes in fp32 (a half-precision backbone's maps are widened when they are flattened)
         dtype = mlvl_feats[0].dtype if mlvl_feats[0].dtype == torch.float64 else torch.float32
         bev_queries = self.bev_embedding.weight.to(dtype)
         bev_pos = self._bev_pos(bs, bev_queries.device, dtype)
-        grid_length = (self.real_h / self.bev_h, self.real_w / self.bev_w)
+        return bev_queries, bev_pos, (self.real_h / self.bev_h, self.real_w / self.bev_w)
+
+    def forward(self, mlvl_feats, img_metas, prev_bev=None, only_bev=False, test=False):
+        """mlvl_feats: list of (B, N, C, H, W) -> {'bev_embed','occ','flow'}; with only_bev the
+        (bs, H*W, C) BEV embedding alone (history frames)."""
+        bev_queries, bev_pos, grid_length = self._bev_inputs(mlvl_feats)
         if only_bev:
             return self.transformer.get_bev_features(
                 mlvl_feats, bev_queries, self.bev_h, self.bev_w, grid_length=grid_length,
@@ -94,6 +105,42 @@ class BEVFormerOccHead(BaseModule):
                                                preds_dicts['occ'].float(),
                                                preds_dicts['flow'].float())
         return dict(loss_occ=loss_occ, loss_flow=loss_flow)
+
+    def _fused_loss_ok(self, mlvl_feats):
+        """Everything the fused heads + loss node needs that is known BEFORE the decoder runs (its BatchNorms update their
+        statistics: no second pass after that): autograd on, device fp32 features, the heads and the two losses in the forms
+        the kernels compute, num_classes <= 30."""
+        t, lo, lf = self.transformer, self.loss_occ, self.loss_flow
+        return (self.fused_loss and torch.is_grad_enabled() and mlvl_feats[0].is_cuda
+                and mlvl_feats[0].dtype != torch.float64 and t._heads_fusable()
+                and t.out_dim == 32 and t.predicter[0].weight.dtype == torch.float32
+                and type(lo) is CrossEntropyLoss and type(lf) is L1Loss and lo.reduction in ('mean', 'sum')
+                and lf.reduction == lo.reduction and self.num_classes <= 30)
+
+    def forward_loss(self, mlvl_feats, img_metas, prev_bev, voxel_semantics, voxel_flow, mask_camera):
+        """loss(forward(...)) -> {'loss_occ', 'loss_flow'}; with `fused_loss` (and its conditions, _fused_loss_ok) the heads
+        and both losses run as one node on the decoder features, and the logits are never materialised.  Otherwise, or when
+        the node refuses its inputs, today's modules run and give today's numbers."""
+        if not self._fused_loss_ok(mlvl_feats):
+            return self.loss(voxel_semantics, voxel_flow, mask_camera, self(mlvl_feats, img_metas, prev_bev))
+        from .. import ext
+        bev_queries, bev_pos, grid_length = self._bev_inputs(mlvl_feats)
+        t = self.transformer
+        _, feats = t.decoder_features(mlvl_feats, bev_queries, self.bev_h, self.bev_w, grid_length=grid_length,
+                                      bev_pos=bev_pos, img_metas=img_metas, prev_bev=prev_bev)
+        p, f, lo, lf = t.predicter, t.flow_predicter, self.loss_occ, self.loss_flow
+        try:
+            labels = voxel_semantics if voxel_semantics.dtype in (torch.uint8, torch.int64) else voxel_semantics.long()
+            cw = None if lo.class_weight is None else feats.new_tensor(lo.class_weight)       # as bricks.CrossEntropyLoss
+            loss_occ, loss_flow = ext.heads_loss(
+                feats.contiguous(), p[0].weight, p[0].bias, p[2].weight, p[2].bias, f[0].weight, f[0].bias, f[2].weight,
+                f[2].bias, labels.contiguous(), voxel_flow.contiguous(),
+                mask_camera.reshape(-1).contiguous() if self.use_mask else None, cw, lo.ignore_index, lo.reduction)
+        except OccAmdUnsupported:
+            # the decoder has run (once): the modules take over from its features
+            flow, occ = f(feats), p(feats)
+            return self.loss(voxel_semantics, voxel_flow, mask_camera, {'occ': occ, 'flow': flow})
+        return dict(loss_occ=lo.loss_weight * loss_occ, loss_flow=lf.loss_weight * loss_flow)
 
     def loss_single(self, voxel_semantics, voxel_flow, mask_camera, occ, flow):
         voxel_semantics = voxel_semantics.long()

@@ -497,6 +497,11 @@ class TransformerOcc(BaseModule):
             if (c.kernel_size, c.stride, c.padding, c.dilation, c.groups) != \
                     ((3, 3, 3), (1, 1, 1), (1, 1, 1), (1, 1, 1), 1):
                 return False
+        return self._heads_fusable()
+
+    def _heads_fusable(self):
+        """The two heads are what the fused heads kernels compute: Linear -> Softplus(beta 1, threshold 20) -> Linear and
+        Linear -> ReLU -> Linear."""
         for head, act in ((self.predicter, nn.Softplus), (self.flow_predicter, nn.ReLU)):
             if len(head) != 3 or not isinstance(head[1], act):
                 return False
@@ -599,6 +604,30 @@ class TransformerOcc(BaseModule):
                 return bev_embed.permute(0, 2, 1).view(bs, -1, bev_h, bev_w), occ_pred, flow_pred
             except OccAmdUnsupported:
                 pass
+        bev_embed, outputs = self._stock_decoder(bev_embed, bev_h, bev_w)
+        flow_pred = self.flow_predicter(outputs)
+        occ_pred = self.predicter(outputs)
+        return bev_embed, occ_pred, flow_pred
+
+    def decoder_features(self, mlvl_feats, bev_queries, bev_h, bev_w, grid_length=[0.512, 0.512], bev_pos=None,
+                         prev_bev=None, **kwargs):
+        """forward() up to the heads: -> (bev_embed (bs, C, bev_h, bev_w), decoder features (bs, W, H, Z, out_dim)), on the
+        training decoder (_train_decoder) or the stock modules.  For the fused heads + loss node of BEVFormerOccHead."""
+        bev_embed = self.get_bev_features(mlvl_feats, bev_queries, bev_h, bev_w, grid_length=grid_length, bev_pos=bev_pos,
+                                          prev_bev=prev_bev, **kwargs)
+        bs = mlvl_feats[0].size(0)
+        if self.use_3d and self._train_decoder_ok(bev_embed):
+            try:
+                outputs = self._train_decoder(bev_embed.contiguous(), bev_h, bev_w)
+                return bev_embed.permute(0, 2, 1).view(bs, -1, bev_h, bev_w), outputs
+            except OccAmdUnsupported:
+                pass
+        return self._stock_decoder(bev_embed, bev_h, bev_w)
+
+    def _stock_decoder(self, bev_embed, bev_h, bev_w):
+        """bev_embed (bs, bev_h*bev_w, C) -> (bev_embed (bs, C, bev_h, bev_w), decoder features (bs, W, H, Z, out_dim)) on the
+        stock torch modules (reference transformer_occ.py:304-317)."""
+        bs = bev_embed.shape[0]
         bev_embed = bev_embed.permute(0, 2, 1).view(bs, -1, bev_h, bev_w)
         if self.use_3d:
             # lifter: channel c -> (feature c // pillar_h, height c % pillar_h): a free view
@@ -616,6 +645,4 @@ class TransformerOcc(BaseModule):
         else:
             outputs = self.decoder(bev_embed.permute(0, 2, 3, 1))
             outputs = outputs.view(bs, bev_h, bev_w, self.pillar_h, self.out_dim)
-        flow_pred = self.flow_predicter(outputs)
-        occ_pred = self.predicter(outputs)
-        return bev_embed, occ_pred, flow_pred
+        return bev_embed, outputs

@@ -13,7 +13,7 @@ going through MultiScaleDeformableAttnFunction_fp32 — the HIP forward and back
 training kernels behind autograd Functions: encoder / head Linears on ext.LinearX3Function (forward + dx on
 linear_bf16x3, dW/db on linear_wgrad), the SCA rebatch / scatter-back on ext.RowsGatherSumFunction, the
 norm_eval backbone as folded convolutions (plugin/backbone.py::conv_bn_folded) with its frozen stages on the
-inference-plan kernels.  DESIGN.md §9 lists what each of these bought on MI355X (137 -> 52.7 ms per sample).
+inference-plan kernels.  DESIGN.md §9 lists what each of these bought on MI355X (137 -> 43-45 ms per sample).
 """
 import torch
 import torch.distributed as dist
