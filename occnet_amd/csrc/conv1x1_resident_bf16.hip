@@ -24,13 +24,10 @@
 //     the tiled value projection does), so the tile comes from HBM once and from that XCD's L2 afterwards.
 // K is summed in a fixed order, independent of the grid: two launches on the same inputs are bit-identical.
 #include <cstdlib>
-#include "common.h"
+#include "conv1x1_resident_pass.h"
 
 namespace occ {
 
-constexpr int kC1rPitch = 80, kC1rScratch = 32 * kC1rPitch;     // per-wave epilogue scratch: 32 rows x 64 B, padded
-
-// LDS: activation tile + the four waves' scratch + the bias of the block's columns
 // output pixel m = (n, yo, xo) of a (Hout, Wout) map -> pixel (n, yo / 2, xo / 2) of the map of half the resolution
 __device__ __forceinline__ int up2_row(int m, int Hout, int Wout) {
   const unsigned hw = (unsigned)(Hout * Wout);
@@ -39,7 +36,22 @@ __device__ __forceinline__ int up2_row(int m, int Hout, int Wout) {
   return (int)((n * (unsigned)(Hout >> 1) + (yo >> 1)) * (unsigned)(Wout >> 1) + (xo >> 1));
 }
 
-constexpr int c1r_lds_bytes(int K, int RT, int bias_cols) { return 32 * RT * K * 2 + 4 * kC1rScratch + bias_cols * 4; }
+// What the pass loop (conv1x1_resident_pass.h) takes from this kernel: the block's run of passes, the switches, and rows
+// that are flat pixel indices m0 + tile row, clamped to the last pixel for loads and masked by m < M for stores
+#define OCC_C1R_P_BEGIN p0
+#define OCC_C1R_P_END (p0 + ppb)
+#define OCC_C1R_RESIDUAL RES
+#define OCC_C1R_RELU relu
+#define OCC_C1R_RES_ROW(RTI, J)                                                                   \
+  int m = m0 + (RTI) * 32 + (rlane >> 2) + 16 * (J);                                              \
+  if (m >= M) m = M - 1;                                                                          \
+  if (RES == 2) m = up2_row(m, Hout, Wout);
+#define OCC_C1R_RES_PIXEL (long)m
+#define OCC_C1R_PASS_LOCALS
+#define OCC_C1R_OUT_ROW(RTI, J)                                                                   \
+  const int m = m0 + (RTI) * 32 + (erow + 16 * (J));                                              \
+  const bool olive = m < M;                                                                       \
+  const long orow = m;
 
 // RES: 0 = no residual, 1 = residual of the output's size, 2 = residual of half the resolution, added nearest-upsampled x2
 template <int K, int RT, int NTW, int RES, int MINB, int RD>
@@ -48,6 +60,7 @@ __global__ __launch_bounds__(256, MINB) void conv1x1_resident_kernel(
     const unsigned short* __restrict__ residual, unsigned short* __restrict__ out, int M, int N, int Hin, int Win,
     int Hout, int Wout, int stride, int relu, int nrb, int ncb, int ppb) {
   extern __shared__ __attribute__((aligned(16))) char clds[];
+  char* const lds = clds;
   constexpr int BM = 32 * RT, PCS = K / 8, PITCH = K * 2, KS = K / 16;
   constexpr int MASK = (PCS < 32 ? PCS : 32) - 1;            // swizzle: slot s of row r holds piece s ^ (r & MASK)
   constexpr int RPI = 64 / PCS;                              // tile rows per DMA instruction (1 KB of LDS each)
@@ -65,7 +78,6 @@ __global__ __launch_bounds__(256, MINB) void conv1x1_resident_kernel(
   }
   if (rb >= nrb) return;                                     // padding of the last group of 8 row tiles
   const int m0 = rb * BM;
-  const int NT32 = N / 32;
 
   // activation tile
 #pragma unroll
@@ -81,25 +93,14 @@ __global__ __launch_bounds__(256, MINB) void conv1x1_resident_kernel(
       const unsigned yo = rem / (unsigned)Wout, xo = rem - yo * (unsigned)Wout;
       pix = (int)((n * (unsigned)Hin + yo * (unsigned)stride) * (unsigned)Win + xo * (unsigned)stride);
     }
-    __builtin_amdgcn_global_load_lds(x + (long)pix * PCS + (slot ^ (r & MASK)), (lds_ptr_t)(clds + inst * 1024), 16, 0, 0);
+    __builtin_amdgcn_global_load_lds(x + (long)pix * PCS + (slot ^ (r & MASK)), (lds_ptr_t)(lds + inst * 1024), 16, 0, 0);
   }
 
-  // weight ring: slot (step & 3) = the wave's NTW column tiles of flat step = pass * KS + k-step (buffer loads: one
-  // lane-offset VGPR for all of them, the step's offset in an SGPR, the tile in the immediate)
-  occ_u32x4 w[4][NTW];
-  const __amdgpu_buffer_rsrc_t wr = uniform_rsrc(wp, (unsigned)K * (unsigned)N * 2u);
-  const int wv = (wave * NTW * 64 + lane) * 16;
-  const int kstep_bytes = NT32 * 1024;
-#define OCC_C1R_LOAD(SLOT, PASS, KSTEP)                                                            \
-  {                                                                                               \
-    const int so = (KSTEP) * kstep_bytes + (PASS) * (4 * NTW * 1024);                             \
-    _Pragma("unroll") for (int t = 0; t < NTW; ++t)                                               \
-      w[SLOT][t] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv + t * 1024, so, 0);               \
-  }
+  OCC_C1R_RING(wp)
   const int p0 = cb * ppb;
   // the bias of the block's columns goes through LDS: read from global memory at the start of a pass it would be the
   // youngest request and waiting for it would drain the weight ring
-  float* const sbias = reinterpret_cast<float*>(clds + TILE_BYTES + 4 * kC1rScratch);
+  float* const sbias = reinterpret_cast<float*>(lds + TILE_BYTES + 4 * kC1rScratch);
   for (int i = tid; i < ppb * (32 * NTW); i += 256)
     *reinterpret_cast<float4*>(sbias + 4 * i) = *reinterpret_cast<const float4*>(bias + p0 * (128 * NTW) + 4 * i);
   OCC_C1R_LOAD(0, p0, 0)
@@ -107,137 +108,10 @@ __global__ __launch_bounds__(256, MINB) void conv1x1_resident_kernel(
   OCC_C1R_LOAD(2, p0, 2)
   __syncthreads();                                  // the tile and the bias have landed (the barrier waits for the DMA)
 
-  char* const scratch = clds + TILE_BYTES + wave * kC1rScratch;
-
-  // activation fragments of k-step ks (the same for every pass): double buffered, read one step ahead.  Slot of piece
-  // 2 ks + kb in row vi = (2 ks) ^ ((kb ^ vi) & MASK): one XOR per step on an address the compiler cannot see through
-  bf16x8 af[2][RT];
-  unsigned abase = (unsigned)(vi * PITCH + ((kb ^ vi) & MASK) * 16);
-#define OCC_C1R_AFRAG(BUF, KSTEP)                                                                  \
-  {                                                                                               \
-    asm volatile("" : "+v"(abase));                                                               \
-    const char* ap = clds + (abase ^ (unsigned)((KSTEP) * 32));                                   \
-    _Pragma("unroll") for (int rt = 0; rt < RT; ++rt)                                             \
-      af[BUF][rt] = *reinterpret_cast<const bf16x8*>(ap + rt * (32 * PITCH));                     \
-  }
-  // residual row segments of tile (rt, t) of the pass whose first column (for this wave) is NW: lane -> rows (lane >> 2)
-  // and + 16 of the tile, 16-byte piece lane & 3
-#define OCC_C1R_RES(DST, NW, RTI, TI)                                                              \
-  {                                                                                               \
-    _Pragma("unroll") for (int j = 0; j < 2; ++j) {                                               \
-      int m = m0 + (RTI) * 32 + (rlane >> 2) + 16 * j;                                            \
-      if (m >= M) m = M - 1;                                                                      \
-      if (RES == 2) m = up2_row(m, Hout, Wout);                                                   \
-      DST[j] = *reinterpret_cast<const uint4*>(residual + (long)m * N + (NW) + (TI) * 32 + (rlane & 3) * 8); \
-    }                                                                                             \
-  }
-  // the residual runs RD tiles ahead of the epilogue, across passes: rq[0] is the tile the epilogue takes next
-  uint4 rq[RD][2];
-  int rlane = lane;
-  if (RES) {
-    const int nw0 = p0 * (128 * NTW) + wave * (32 * NTW);
-#pragma unroll
-    for (int i = 0; i < RD; ++i) OCC_C1R_RES(rq[i], nw0, i / NTW, i % NTW)
-  }
-  OCC_C1R_AFRAG(0, 0)
-#pragma unroll 1
-  for (int p = p0; p < p0 + ppb; ++p) {
-    const int nw = p * (128 * NTW) + wave * (32 * NTW);         // the wave's first column of this pass
-    int elane = lane;                               // opaque per pass: the epilogue's offsets are recomputed here instead
-    asm volatile("" : "+v"(elane));                 // of living across the k loop
-    // D[column][row]: lane (vi, kb) holds row rt * 32 + vi, register 4 q + i = column 8 q + 4 kb + i of tile t.
-    // The accumulators start at the bias.
-    f32x16 acc[RT][NTW];
-#pragma unroll
-    for (int t = 0; t < NTW; ++t)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const float4 c0 = *reinterpret_cast<const float4*>(sbias + (nw - p0 * (128 * NTW)) + t * 32 + 8 * q + 4 * kb);
-#pragma unroll
-        for (int rt = 0; rt < RT; ++rt) {
-          acc[rt][t][4 * q + 0] = c0.x;
-          acc[rt][t][4 * q + 1] = c0.y;
-          acc[rt][t][4 * q + 2] = c0.z;
-          acc[rt][t][4 * q + 3] = c0.w;
-        }
-      }
-    const int pn = p + 1 < p0 + ppb ? p + 1 : p;     // the ring runs into the next pass (last pass: a harmless re-read)
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-      if (ks + 3 < KS) OCC_C1R_LOAD((ks + 3) & 3, p, ks + 3)
-      else OCC_C1R_LOAD((ks + 3) & 3, pn, ks + 3 - KS)
-      OCC_C1R_AFRAG((ks + 1) & 1, (ks + 1) & (KS - 1))
-#pragma unroll
-      for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-        for (int t = 0; t < NTW; ++t)
-          acc[rt][t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w[ks & 3][t]), af[ks & 1][rt],
-                                                               acc[rt][t], 0, 0, 0);
-      // pin the software pipeline (hipcc otherwise sinks every ring request down to its use: load, vmcnt(0), MFMA)
-      if (NTILES >= 4) {
-        constexpr int MQ = NTILES / 4;
-        __builtin_amdgcn_sched_group_barrier(0x008, MQ, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);        // ring request of step s + 3
-        __builtin_amdgcn_sched_group_barrier(0x008, MQ, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, RT / 2, 0);   // A fragments of step s + 1
-        __builtin_amdgcn_sched_group_barrier(0x008, MQ, 0);
-        if (NTW > 1) __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, MQ, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, RT / 2, 0);
-      } else {
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-    }
-
-    // ---- epilogue of the pass: one 32 x 32 tile at a time through the wave's scratch (row pitch 80 B) -------------------
-    const int erow = elane >> 2, epiece = elane & 3;
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-#pragma unroll
-      for (int t = 0; t < NTW; ++t) {
-        const int e = rt * NTW + t;
-        if (RES) {
-          const uint4 r0 = rq[0][0], r1 = rq[0][1];
-#pragma unroll
-          for (int i = 0; i + 1 < RD; ++i) { rq[i][0] = rq[i + 1][0]; rq[i][1] = rq[i + 1][1]; }
-          asm volatile("" : "+v"(rlane));
-          if (e + RD < NTILES) OCC_C1R_RES(rq[RD - 1], nw, (e + RD) / NTW, (e + RD) % NTW)
-          else if (p + 1 < p0 + ppb) OCC_C1R_RES(rq[RD - 1], nw + 128 * NTW, (e + RD - NTILES) / NTW, (e + RD - NTILES) % NTW)
-          *reinterpret_cast<uint4*>(scratch + erow * kC1rPitch + epiece * 16) = r0;
-          *reinterpret_cast<uint4*>(scratch + (erow + 16) * kC1rPitch + epiece * 16) = r1;
-          wave_lds_sync();
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          char* const sp = scratch + vi * kC1rPitch + 16 * q + 8 * kb;
-          float v0 = acc[rt][t][4 * q + 0], v1 = acc[rt][t][4 * q + 1], v2 = acc[rt][t][4 * q + 2],
-                v3 = acc[rt][t][4 * q + 3];
-          if (RES) {
-            const uint2 r = *reinterpret_cast<const uint2*>(sp);
-            v0 += bf16_lo_to_f32(r.x); v1 += bf16_hi_to_f32(r.x); v2 += bf16_lo_to_f32(r.y); v3 += bf16_hi_to_f32(r.y);
-          }
-          if (relu) { v0 = fmaxf(v0, 0.f); v1 = fmaxf(v1, 0.f); v2 = fmaxf(v2, 0.f); v3 = fmaxf(v3, 0.f); }
-          *reinterpret_cast<uint2*>(sp) = make_uint2(pack_bf16x2_rne(v0, v1), pack_bf16x2_rne(v2, v3));
-        }
-        wave_lds_sync();
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int row = erow + 16 * j;
-          const int m = m0 + rt * 32 + row;
-          const uint4 v = *reinterpret_cast<const uint4*>(scratch + row * kC1rPitch + epiece * 16);
-          if (m < M) *reinterpret_cast<uint4*>(out + (long)m * N + nw + t * 32 + epiece * 8) = v;
-        }
-        wave_lds_sync();
-      }
-    }
-  }
-#undef OCC_C1R_RES
-#undef OCC_C1R_AFRAG
-#undef OCC_C1R_LOAD
+  char* const scratch = lds + TILE_BYTES + wave * kC1rScratch;
+  OCC_C1R_AFRAG_STATE
+  OCC_C1R_RES_START
+  OCC_C1R_PASSES
 }
 
 // Which resident tile the arguments have a kernel for: 0 = none.  rt = 0 asks for the default tile of the shape, 2 / 4
