@@ -243,6 +243,28 @@ int occ_tsa_fused_forward_f32(const float* value, int64_t value_bt_stride, const
                               int64_t offs_stride, const float* logits, int64_t logits_stride,
                               const float* ref_2d, const int32_t* order, float* out, int B, int Nq,
                               int bev_h, int bev_w, int M, int D, int P, void* stream);
+/* Backward of occ_tsa_fused_forward_f32 (same geometry and arguments; Nq = bev_h*bev_w: no query bands; `order` only steers
+ * locality and has no counterpart here).  grad_out (B, Nq, M*D) f32 is the gradient of `out`.  spatial_shapes = {bev_h, bev_w}
+ * and level_start_index = {0} as int64 in DEVICE memory (the grad_value replay reads them).  Outputs:
+ *   grad_value  (B*2, Nq, M, D) f32 contiguous, one map per queue entry (also when value_bt_stride made the forward's entries
+ *               alias: the caller adds the two), ACCUMULATED into (the caller zeroes it);
+ *   grad_offs   (B, Nq, M*2*P*2) f32, row stride grad_offs_stride floats, every element overwritten;
+ *   grad_logits (B, Nq, M*2*P)   f32, row stride grad_logits_stride floats, every element overwritten.
+ * An output that is not wanted is NULL — grad_value, or grad_offs AND grad_logits together — and nothing is computed for it.
+ * A sample whose location is not finite contributes nothing, as in the forward.  grad_offs / grad_logits have one writer per
+ * element and a fixed summation order: bit-identical run to run.  grad_value runs through the binned, atomic-free path of the
+ * msda backward; with OCC_MSDA_BWD_DETERMINISTIC=1 (read per call) it is bit-identical run to run as well.  `workspace`:
+ * CALLER-OWNED scratch of at least occ_tsa_fused_backward_workspace_bytes(...) bytes, 256-byte aligned, uninitialised.
+ * Alignment (checked, OCC_E_INVALID): value, grad_out and grad_value 16 bytes (value_bt_stride a multiple of 4 floats), offs,
+ * grad_offs and ref_2d 8 bytes, offs_stride and grad_offs_stride even.  Kernel exists for M=8, D=32, P=4; other shapes (and
+ * ..._workspace_bytes() == 0) return OCC_E_UNSUPPORTED. */
+int64_t occ_tsa_fused_backward_workspace_bytes(int B, int Nq, int bev_h, int bev_w, int M, int D, int P);
+int occ_tsa_fused_backward_f32(const float* value, int64_t value_bt_stride, const float* offs, int64_t offs_stride,
+                               const float* logits, int64_t logits_stride, const float* ref_2d, const float* grad_out,
+                               const int64_t* spatial_shapes, const int64_t* level_start_index, float* grad_value,
+                               float* grad_offs, int64_t grad_offs_stride, float* grad_logits,
+                               int64_t grad_logits_stride, int B, int Nq, int bev_h, int bev_w, int M, int D, int P,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Lifter + Conv3d(k=3, pad=1, stride=1, no bias) + BatchNorm3d(eval) + ReLU, implicit GEMM on the f32

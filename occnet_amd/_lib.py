@@ -33,7 +33,8 @@ def declared_symbols(header=HEADER_PATH):
 
 # the size queries of the header that return int64_t (ctypes assumes int)
 _INT64_RESULTS = (
-    "occ_ms_deform_attn_backward_workspace_bytes", "occ_sca_fused_backward_workspace_bytes", "occ_conv3d_heads_pack_bytes",
+    "occ_ms_deform_attn_backward_workspace_bytes", "occ_sca_fused_backward_workspace_bytes",
+    "occ_tsa_fused_backward_workspace_bytes", "occ_conv3d_heads_pack_bytes",
     "occ_linear_chain_packed_bytes", "occ_linear_wgrad_workspace_bytes", "occ_conv3d_wgrad_workspace_bytes",
     "occ_bias_act_bwd_partial_floats", "occ_dropout_add_ln_bwd_partial_floats", "occ_conv1x1_wgrad_workspace_bytes",
     "occ_ray_metrics_state_words", "occ_ray_metrics_workspace_bytes", "occ_heads_loss_workspace_bytes")

@@ -829,7 +829,7 @@ bool bwd_block_bins_fit(int B, int S, int M, int L, int Lq, int P) {
 int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const int64_t* spatial_shapes,
                     const int64_t* level_start_index, const float* sampling_loc, const float* attn_weight,
                     const ScaBinSource* sca, const float* grad_output, long grad_out_n, float* grad_value, int B, int S,
-                    int M, int L, int Lq, int P, hipStream_t st) {
+                    int M, int L, int Lq, int P, hipStream_t st, int loc_batch_div) {
   unsigned char* flags = reinterpret_cast<unsigned char*>(ws);
   int* counts = reinterpret_cast<int*>(ws + w.off_cnt);
   int* cursor = reinterpret_cast<int*>(ws + w.off_cur);
@@ -837,7 +837,7 @@ int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const in
   int* work_count = reinterpret_cast<int*>(ws + w.off_work);
   int4* work = reinterpret_cast<int4*>(ws + w.off_work + 16);
   const ScaBinSource src = sca != nullptr ? *sca : ScaBinSource{nullptr, nullptr, nullptr, nullptr, 1, 1, 1};
-  const int bdiv = src.NC;
+  const int bdiv = sca != nullptr ? src.NC : loc_batch_div;
   const dim3 grid_s((unsigned)((w.n_samples + 255) / 256));
   // binning passes: block-aggregated (default) or the wave-aggregated kernels (OCC_MSDA_BWD_BIN=wave, or a
   // level with more bins than the LDS histogram holds); the SCA items exist in the block-aggregated form only (the

@@ -25,10 +25,12 @@ struct ScaBinSource {
 
 // Count -> scan -> fill -> replay into grad_value (B value batch entries; accumulated: the caller zeroes it).  Items come from
 // loc / attn / nzflag (ms_deform_attn layout) or, with `sca`, from the fused SCA gather's source; the output-gradient row of an
-// item of batch entry bv and query q is grad_out[((bv / NC) * Lq + q) * M + m][0 .. 31] (NC = 1 without `sca`).  grad_out_n:
-// floats in grad_out (the deterministic mode's range scan).  The flags / counts of the workspace must arrive zeroed.
+// item of batch entry bv and query q is grad_out[((bv / NC) * Lq + q) * M + m][0 .. 31]; without `sca`, NC is loc_batch_div
+// (1: one grad row per value batch entry, the msda backward; 2: the fused TSA backward, whose two queue entries of a batch
+// share the batch's grad row).  grad_out_n: floats in grad_out (the deterministic mode's range scan).  The flags / counts of
+// the workspace must arrive zeroed.
 int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const int64_t* shapes, const int64_t* lstart,
                     const float* loc, const float* attn, const ScaBinSource* sca, const float* grad_out, long grad_out_n,
-                    float* grad_value, int B, int S, int M, int L, int Lq, int P, hipStream_t st);
+                    float* grad_value, int B, int S, int M, int L, int Lq, int P, hipStream_t st, int loc_batch_div = 1);
 
 }  // namespace occ

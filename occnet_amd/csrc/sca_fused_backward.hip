@@ -34,23 +34,7 @@ namespace occ {
 
 constexpr int kScaBwdWaves = 4;
 
-// one resolved sample for the gradient: byte offsets of the four corner rows (kOobOffset outside the map: the buffer load
-// returns 0, which is mmcv's "only in-range corners"), the fractional weights (0 for a sample outside its map)
-struct __attribute__((aligned(16))) ScaBwdParam {
-  unsigned o[4];
-  float lh, lw, pad0, pad1;
-};
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-  return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w)));
-}
-
-// x (lane's copy) + the value held `mask` lanes away, where each lane keeps one half and sends the other: hi (0 / 1 lane
-// flag) selects which half this lane keeps
-__device__ __forceinline__ float rs_step(float lo, float hi_v, int hi, int mask) {
-  const float keep = hi ? hi_v : lo, send = hi ? lo : hi_v;
-  return keep + __shfl_xor(send, mask);
-}
+// BwdSampleParam, dot4, rs_step: common.h (shared with tsa_fused_backward.hip)
 
 template <int L, int P>
 __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
@@ -65,7 +49,7 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
   static_assert(LP >= 8 && LP <= 32 && (LP & (LP - 1)) == 0, "L*P must be a power of two in [8,32]");
   static_assert(64 % LP == 0, "the lane's level must not depend on k");
   constexpr int LPp = LP + 1;
-  __shared__ ScaBwdParam smem[kScaBwdWaves * M * LPp];
+  __shared__ BwdSampleParam smem[kScaBwdWaves * M * LPp];
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -74,7 +58,7 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
   const int b = (int)(wg / Nq);
   const int q = (int)(wg - (long)b * Nq);
   const long bq = (long)b * Nq + q;
-  ScaBwdParam* sp = smem + wave * M * LPp;
+  BwdSampleParam* sp = smem + wave * M * LPp;
   constexpr int row_stride = M * D;
   const uint32_t vis = vis_bits[q];                   // batch 0's mask picks the cameras
   const uint32_t own = vis_bits[bq];                  // this batch's mask gives the divisor
@@ -114,7 +98,7 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
       const float2 rxy = *reinterpret_cast<const float2*>(rp + 2 * z);
       const BilinearTerms t = bilinear_terms(rxy.x + ox[k], rxy.y + oy[k], lvH, lvW, 1);
       const unsigned base = (unsigned)(lvS + t.h_low * lvW + t.w_low);
-      ScaBwdParam p;
+      BwdSampleParam p;
       p.o[0] = t.c[0] ? base * (unsigned)row_stride * 4u : kOobOffset;
       p.o[1] = t.c[1] ? (base + 1u) * (unsigned)row_stride * 4u : kOobOffset;
       p.o[2] = t.c[2] ? (base + (unsigned)lvW) * (unsigned)row_stride * 4u : kOobOffset;
@@ -143,7 +127,7 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          const ScaBwdParam& pp = sp[g * LPp + 8 * j + 4 * h + u];
+          const BwdSampleParam& pp = sp[g * LPp + 8 * j + 4 * h + u];
           const float lh = pp.lh, lw = pp.lw, hh = 1.f - lh, hw = 1.f - lw;
           const float d1 = dot4(top, r[u][0]), d2 = dot4(top, r[u][1]), d3 = dot4(top, r[u][2]), d4 = dot4(top, r[u][3]);
           v[4 * h + u][0] = hh * hw * d1 + hh * lw * d2 + lh * hw * d3 + lh * lw * d4;

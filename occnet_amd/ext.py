@@ -391,6 +391,14 @@ def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_
     out of range.
     The kernel reads float2 offset pairs and 16-byte pieces of value rows: offs must start 8-byte aligned with an even row
     stride, value 16-byte aligned (any slice of a Linear output at an even column is)."""
+    return _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points, shared_queue, order,
+                              value_rows, 'tsa_fused_forward')
+
+
+def _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points, shared_queue, order, value_rows,
+                       timing):
+    """tsa_fused_forward under the timing label `timing` (the training node keeps its launches apart from the inference
+    gather's)."""
     _need_cuda_f32("value", value)
     _need_cuda_f32("ref_2d", ref_2d)
     _need_cuda_f32("offs", offs, contiguous=False)
@@ -432,13 +440,137 @@ def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_
                                   and order.device == value.device and order.is_contiguous()):
         raise OccAmdError("tsa_fused_forward: order must be a contiguous int32 (Nq) tensor on value's device")
     out = torch.empty((B, Nq, M * D), dtype=torch.float32, device=value.device)
-    with torch.cuda.device(value.device), _timed('tsa_fused_forward'):
+    with torch.cuda.device(value.device), _timed(timing):
         rc = _lib.lib().occ_tsa_fused_forward_f32(
             ptr(value), i64(stride), ptr(offs), i64(offs.stride(1)), ptr(logits),
             i64(logits.stride(1)), ptr(ref_2d), ptr(order), ptr(out), i32(B), i32(Nq), i32(bev_h),
             i32(bev_w), i32(M), i32(D), i32(P), stream_ptr(value.device))
     _lib.check(rc, "tsa_fused_forward")
     return out
+
+
+def tsa_fused_backward_workspace_bytes(B, Nq, bev_h, bev_w, M, D, P):
+    """Bytes of scratch tsa_fused_backward takes for these shapes (0: no backward kernel for them)."""
+    return int(_lib.lib().occ_tsa_fused_backward_workspace_bytes(i32(B), i32(Nq), i32(bev_h), i32(bev_w), i32(M), i32(D),
+                                                                 i32(P)))
+
+
+_TSA_LEVEL_TENSORS = {}
+
+
+def _tsa_level_tensors(device, bev_h, bev_w):
+    """spatial_shapes ((1, 2) int64) and level_start_index ((1,) int64) of the one BEV level on `device`, built by fill
+    kernels (no host-to-device copy, so no device sync) and kept."""
+    key = (str(device), int(bev_h), int(bev_w))
+    hit = _TSA_LEVEL_TENSORS.get(key)
+    if hit is None:
+        shapes = torch.empty((1, 2), dtype=torch.int64, device=device)
+        shapes[:, 0].fill_(int(bev_h))
+        shapes[:, 1].fill_(int(bev_w))
+        hit = _TSA_LEVEL_TENSORS[key] = (shapes, torch.zeros(1, dtype=torch.int64, device=device))
+    return hit
+
+
+def tsa_fused_backward(value, offs, logits, ref_2d, grad_out, bev_h, bev_w, num_heads, num_points, shared_queue=False,
+                       want_value=True, want_query=True):
+    """Gradient of tsa_fused_forward (csrc/tsa_fused_backward.hip).  Same inputs as the forward (no query bands, no `order`:
+    it only steers locality) plus grad_out (B, Nq, M*D) -> (grad_value in value's layout, grad_offs (B, Nq, M*2*P*2),
+    grad_logits (B, Nq, M*2*P)).  With shared_queue the kernel still writes one gradient map per queue entry and their sum
+    is returned as the gradient of the single map.  want_value / want_query = False: that part is not computed and comes
+    back as None.  grad_offs / grad_logits are bit-reproducible; grad_value too under OCC_MSDA_BWD_DETERMINISTIC=1.  Raises
+    OccAmdUnsupported for shapes without a backward kernel."""
+    _need_cuda_f32("value", value)
+    _need_cuda_f32("ref_2d", ref_2d)
+    _need_cuda_f32("offs", offs, contiguous=False)
+    _need_cuda_f32("logits", logits, contiguous=False)
+    _need_cuda_f32("grad_out", grad_out)
+    if offs.dim() != 3 or logits.dim() != 3:
+        raise OccAmdError("tsa_fused_backward: offs and logits must be (B,Nq,...)")
+    if not (want_value or want_query):
+        return None, None, None
+    B, Nq = offs.shape[:2]
+    M, D, P = int(num_heads), value.shape[-1], int(num_points)
+    need = tsa_fused_backward_workspace_bytes(B, Nq, bev_h, bev_w, M, D, P)
+    if need <= 0:
+        raise OccAmdUnsupported(f"tsa_fused_backward: no backward kernel for M={M} D={D} P={P}, {Nq} queries on a "
+                                f"{bev_h}x{bev_w} map")
+    per = Nq * M * D
+    if value.numel() != (B if shared_queue else 2 * B) * per:
+        raise OccAmdError("tsa_fused_backward: value must be (B*2,Nq,M,D), or (B,Nq,M,D) with shared_queue")
+    if shared_queue and B != 1:         # entry (b,t) lives at (b*2+t)*stride: the forward stacked the map as well
+        src = torch.stack([value.view(B, Nq, M, D)] * 2, 1).reshape(B * 2, Nq, M, D).contiguous()
+    else:
+        src = value
+    stride = 0 if shared_queue and B == 1 else per
+    if tuple(ref_2d.shape) != (B * 2, Nq, 1, 2):
+        raise OccAmdError("tsa_fused_backward: ref_2d must be (B*2,Nq,1,2)")
+    for n, t, w in (("offs", offs, M * 2 * P * 2), ("logits", logits, M * 2 * P)):
+        if tuple(t.shape[:2]) != (B, Nq) or t.shape[-1] != w or t.stride(-1) != 1 \
+                or (B > 1 and t.stride(0) != Nq * t.stride(1)):
+            raise OccAmdError(f"tsa_fused_backward: {n} must be (B,Nq,{w}) with unit inner stride")
+    if tuple(grad_out.shape) != (B, Nq, M * D):
+        raise OccAmdError(f"tsa_fused_backward: grad_out must be (B,Nq,{M * D})")
+    if offs.data_ptr() % 8 or offs.stride(1) % 2:
+        raise OccAmdError("tsa_fused_backward: offs must be 8-byte aligned with an even row stride (float2 reads)")
+    if src.data_ptr() % 16 or grad_out.data_ptr() % 16 or ref_2d.data_ptr() % 8:
+        raise OccAmdError("tsa_fused_backward: value and grad_out must be 16-byte aligned (and ref_2d 8-byte aligned)")
+    dev = value.device
+    shapes, lstart = _tsa_level_tensors(dev, bev_h, bev_w)
+    # scratch from torch's caching allocator, freed back to the pool when this call returns (stream-ordered)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    # one gradient map per queue entry, also where the forward read one map twice: no aliasing writes in the launch
+    gv2 = torch.zeros((B * 2, Nq, M, D), dtype=torch.float32, device=dev) if want_value else None
+    grad_offs = torch.empty((B, Nq, M * 2 * P * 2), dtype=torch.float32, device=dev) if want_query else None
+    grad_logits = torch.empty((B, Nq, M * 2 * P), dtype=torch.float32, device=dev) if want_query else None
+    with torch.cuda.device(dev), _timed('tsa_fused_backward'):
+        rc = _lib.lib().occ_tsa_fused_backward_f32(
+            ptr(src), i64(stride), ptr(offs), i64(offs.stride(1)), ptr(logits), i64(logits.stride(1)), ptr(ref_2d),
+            ptr(grad_out), ptr(shapes), ptr(lstart), ptr(gv2), ptr(grad_offs), i64(M * 2 * P * 2), ptr(grad_logits),
+            i64(M * 2 * P), i32(B), i32(Nq), i32(bev_h), i32(bev_w), i32(M), i32(D), i32(P), ptr(ws), i64(need),
+            stream_ptr(dev))
+    _lib.check(rc, "tsa_fused_backward")
+    grad_value = None
+    if want_value:
+        grad_value = (gv2.view(B, 2, Nq, M, D).sum(1) if shared_queue else gv2).view(value.shape)
+    return grad_value, grad_offs, grad_logits
+
+
+class TSAFusedFunction(torch.autograd.Function):
+    """The fused TSA gather as an autograd node: forward = occ_tsa_fused_forward_f32, backward = occ_tsa_fused_backward_f32.
+    value (B*2, Nq, M, D) float32, or (B, Nq, M, D) with shared_queue; offs / logits (B, Nq, ...) — column slices of one
+    Linear output are fine, autograd routes both gradients into it; ref_2d (B*2, Nq, 1, 2) is a constant -> (B, Nq, M*D).
+    `order` steers the forward's locality only and is ignored in the backward.  Raises OccAmdUnsupported (before anything
+    runs) for shapes without a backward kernel and for value_rows: the row pipeline is an inference device."""
+
+    @staticmethod
+    def forward(ctx, value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points, shared_queue=False, order=None,
+                value_rows=None):
+        if value_rows is not None:
+            raise OccAmdUnsupported("TSAFusedFunction: no backward for a query band (value_rows)")
+        if offs.dim() != 3:
+            raise OccAmdError("TSAFusedFunction: offs and logits must be (B,Nq,...)")
+        B, Nq = offs.shape[:2]
+        M, D, P = int(num_heads), value.shape[-1], int(num_points)
+        if tsa_fused_backward_workspace_bytes(B, Nq, int(bev_h), int(bev_w), M, D, P) <= 0:
+            raise OccAmdUnsupported(f"TSAFusedFunction: no backward kernel for M={M} D={D} P={P}, {Nq} queries on a "
+                                    f"{bev_h}x{bev_w} map")
+        value = value.contiguous()
+        # timed under a name of its own: 'tsa_fused_forward' is the inference gather's
+        out = _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points, shared_queue, order, None,
+                                 'tsa_fused_forward_train')
+        ctx.save_for_backward(value, offs, logits, ref_2d)
+        ctx.args = (int(bev_h), int(bev_w), M, P, bool(shared_queue))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        value, offs, logits, ref_2d = ctx.saved_tensors
+        need_v, need_o, need_l = ctx.needs_input_grad[:3]
+        bev_h, bev_w, M, P, shared = ctx.args
+        gv, go, gl = tsa_fused_backward(value, offs, logits, ref_2d, grad_out.contiguous(), bev_h, bev_w, M, P,
+                                        shared_queue=shared, want_value=need_v, want_query=need_o or need_l)
+        return (gv, go if need_o else None, gl if need_l else None) + (None,) * 8
 
 
 def conv3d_channel_block(cin):

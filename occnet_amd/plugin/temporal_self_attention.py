@@ -11,8 +11,12 @@ per head and queue entry; the two queue results are averaged, projected and adde
   twice (:177, :198); here it is projected once and both queue entries alias it.
 * unfused path (autograd / unsupported shapes): the reference's decomposition through
   MultiScaleDeformableAttnFunction_fp32.
+* fused training path (OCC_TSA_TRAIN_FUSED=1, default off): the same gather as an autograd node
+  (ext.TSAFusedFunction, csrc/tsa_fused_backward.hip) on column slices of the one query GEMM; without
+  history (bs = 1) the value is projected once and the node aliases it.
 """
 import math
+import os
 import warnings
 
 import torch
@@ -99,6 +103,28 @@ class TemporalSelfAttention(BaseModule):
             # the keyed tensors stay referenced so their addresses cannot be recycled under the cache
             self._fold_key, self._fold_src, self._fold_val = key, (w, b, query_pos), (w_sum, pos_term)
         return self._fold_val
+
+    # training through the fused gather and its backward (ext.TSAFusedFunction) instead of _unfused's decomposition
+    # (OCC_TSA_TRAIN_FUSED=1; default off)
+    train_fused = os.environ.get("OCC_TSA_TRAIN_FUSED", "0") == "1"
+
+    def _train_fused(self, query_cat, value, shared, reference_points, bev_h, bev_w, order):
+        """query_cat (bs, num_query, 2C); value (bs*2, num_query, C), or the single map (bs = 1) when `shared`
+        -> (bs, num_query, C) before output_proj.  Raises OccAmdUnsupported before anything runs."""
+        bs, num_query, _ = query_cat.shape
+        if ext.tsa_fused_backward_workspace_bytes(bs, num_query, bev_h, bev_w, self.num_heads,
+                                                  self.embed_dims // self.num_heads, self.num_points) <= 0:
+            raise OccAmdUnsupported("TemporalSelfAttention: no fused backward for these shapes")
+        n_off = self.sampling_offsets.out_features
+        wcat = torch.cat([self.sampling_offsets.weight, self.attention_weights.weight], 0)
+        wcat._occ_no_cache = True           # rebuilt every forward: its packed form must not pile up in the cache
+        proj = ext.linear_autograd(
+            query_cat, wcat, torch.cat([self.sampling_offsets.bias, self.attention_weights.bias], 0))
+        v = self.value_proj(value)
+        v = v.view(v.shape[0], num_query, self.num_heads, -1)
+        return ext.TSAFusedFunction.apply(v, proj[..., :n_off], proj[..., n_off:],
+                                          reference_points.float().contiguous(), bev_h, bev_w, self.num_heads,
+                                          self.num_points, shared, order)
 
     def _fusable(self, reference_points):
         return (self.batch_first and self.num_levels == 1 and self.num_bev_queue == 2
@@ -211,6 +237,16 @@ class TemporalSelfAttention(BaseModule):
             try:
                 output = self._fused(query, value_first if shared else value, shared,
                                      reference_points, bev_h, bev_w, kwargs.get('bev_order'))
+            except OccAmdUnsupported:
+                output = None
+        elif (needs_grad and self.train_fused and self.use_fused and key_padding_mask is None
+              and self._fusable(reference_points)):
+            bev_h, bev_w = kwargs.get('bev_h'), kwargs.get('bev_w')
+            if bev_h is None or bev_w is None:
+                bev_h, bev_w = [int(v) for v in spatial_shapes[0].tolist()]   # device sync
+            try:
+                output = self._train_fused(query, value_first if shared else value, shared, reference_points,
+                                           bev_h, bev_w, kwargs.get('bev_order'))
             except OccAmdUnsupported:
                 output = None
         if output is None:
