@@ -654,6 +654,27 @@ int64_t occ_conv1x1_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout
 int occ_conv1x1_wgrad_nhwc_bf16(const void* g, const void* x, void* dw, int dw_bf16, void* workspace, int N, int H, int W,
                                 int Cin, int Cout, int stride, int splits, void* stream);
 
+/* Training partner of occ_conv3x3_nhwc_bf16 (csrc/conv3x3_wgrad_bf16.hip): weight gradient of the 3x3 / pad 1 convolution,
+ *     dw[o][ky][kx][i] = sum over (n, yo, xo) of g[(n, yo, xo), o] * x[(n, yo*stride + ky - 1, xo*stride + kx - 1), i]
+ * (terms outside the map are zero).  bf16 in, f32 accumulation on the matrix cores.  g (N, Ho, Wo, Cout) bf16 NHWC with
+ * Ho = (H-1)/stride + 1, x (N, H, W, Cin) bf16 NHWC, both 4-byte aligned; dw in memory order [Cout][3][3][Cin] (torch: a
+ * (Cout, Cin, 3, 3) tensor in channels_last strides), f32 or (dw_bf16 != 0) bf16, overwritten, not accumulated.
+ * Needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048, stride 1 or 2, otherwise OCC_E_UNSUPPORTED (and
+ * ..._workspace_bytes() == 0): the caller keeps ATen's convolution_backward.
+ * The output rows (n, yo) are reduced in `splits` ranges of whole rows into `workspace` (occ_conv3x3_wgrad_workspace_bytes(...)
+ * bytes for the SAME arguments, owned by the caller, 8-byte aligned; every byte of it that is read has been written by this
+ * call) and the partial sums are added in a fixed order: the result is deterministic, no float atomics.  splits: 0 = the
+ * launcher's choice (about one block per CU), > 0 = that many balanced ranges, splits * 9 * Cout * Cin * 4 bytes (at most
+ * min(N * Ho, 4096) ranges; tests, probes), < 0 OCC_E_INVALID.
+ * A non-finite x value enters only the taps whose exact sum contains it; a non-finite g value at a pixel next to the map's
+ * border also makes the taps that fall outside the map there NaN (they are g * 0): exact border taps need finite g.
+ * Argument checks run before any launch.  Replaces: the weight half of ATen's convolution_backward (MIOpen / CK) behind
+ * ConvBNActFunction.  The input gradient needs no entry point at stride 1: gx = occ_conv3x3_nhwc_bf16(g, pack(Wd)) with
+ * Wd[i][o][ky][kx] = W[o][i][2-ky][2-kx]. */
+int64_t occ_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride, int splits);
+int occ_conv3x3_wgrad_nhwc_bf16(const void* g, const void* x, void* dw, int dw_bf16, void* workspace, int N, int H, int W,
+                                int Cin, int Cout, int stride, int splits, void* stream);
+
 /* Backbone 3x3 pad-1 convolution, stride 1 or 2, on NHWC bf16 with bias (+ ReLU) fused (outside the
  * hand-written hot path).  x (batch, H, W, Cin) bf16 ; weight packed by occ_conv3x3_pack_weight_bf16 from
  * torch's (Cout, Cin, 3, 3) f32 layout to [Cin/32][tap][co][32] bf16 ; bias (Cout) f32 ;

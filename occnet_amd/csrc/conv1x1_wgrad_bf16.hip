@@ -33,23 +33,13 @@
 //   conv1x1_wgrad_kernel<false> (strided)   130 VGPRs, 0 AGPRs, no scratch, no spills, 0 B LDS
 //   conv1x1_wgrad_reduce_kernel             32 VGPRs, 0 AGPRs, no scratch, no spills, 1 024 B LDS
 #include "common.h"
+#include "conv_wgrad.h"      // cw_frag, conv_wgrad_reduce_launch
 
 namespace occ {
 
 struct WgradGeo {       // pixel index -> x row, for the strided form
   int H, W, Ho, Wo, stride;
 };
-
-// 8 dwords (pixel j: channel 2c in the low half, 2c + 1 in the high half) -> the fragments of the even and the odd channel
-__device__ __forceinline__ void cw_frag(const unsigned (&v)[8], bf16x8& even, bf16x8& odd) {
-  occ_u32x4 e, o;
-  e.x = __builtin_amdgcn_perm(v[1], v[0], 0x05040100u); o.x = __builtin_amdgcn_perm(v[1], v[0], 0x07060302u);
-  e.y = __builtin_amdgcn_perm(v[3], v[2], 0x05040100u); o.y = __builtin_amdgcn_perm(v[3], v[2], 0x07060302u);
-  e.z = __builtin_amdgcn_perm(v[5], v[4], 0x05040100u); o.z = __builtin_amdgcn_perm(v[5], v[4], 0x07060302u);
-  e.w = __builtin_amdgcn_perm(v[7], v[6], 0x05040100u); o.w = __builtin_amdgcn_perm(v[7], v[6], 0x07060302u);
-  even = __builtin_bit_cast(bf16x8, e);
-  odd = __builtin_bit_cast(bf16x8, o);
-}
 
 // pixels m .. m+15 of this wave's g channel group and x channel group -> raw registers.  Pixels are clamped to P - 1 so
 // the load is always legal; `left` < 16 zeroes the pixels beyond the block's range (wave-uniform branch).
@@ -258,6 +248,12 @@ static bool cw_plan(int N, int H, int W, int Cin, int Cout, int stride, int spli
   return true;
 }
 
+hipError_t conv_wgrad_reduce_launch(const float* part, void* dw, long OI, int chunks, int dw_bf16, hipStream_t st) {
+  hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel, dim3((unsigned)((OI + 63) / 64)), dim3(256), 0, st, part, dw, OI, chunks,
+                     dw_bf16 ? 1 : 0);
+  return hipGetLastError();
+}
+
 }  // namespace occ
 
 extern "C" int64_t occ_conv1x1_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride, int splits) {
@@ -295,9 +291,10 @@ extern "C" int occ_conv1x1_wgrad_nhwc_bf16(const void* g, const void* x, void* d
     hipLaunchKernelGGL(conv1x1_wgrad_kernel<false>, grid, dim3(256), 0, st, gp, xp, part, (int)pl.P, Cin, Cout, pl.PC,
                        pl.tiles_i, geo);
   OCC_CHECK_LAUNCH("conv1x1_wgrad");
-  const long OI = (long)Cout * Cin;
-  hipLaunchKernelGGL(conv1x1_wgrad_reduce_kernel, dim3((unsigned)((OI + 63) / 64)), dim3(256), 0, st, part, dw, OI,
-                     pl.chunks, dw_bf16 ? 1 : 0);
-  OCC_CHECK_LAUNCH("conv1x1_wgrad_reduce");
+  const hipError_t e = conv_wgrad_reduce_launch(part, dw, (long)Cout * Cin, pl.chunks, dw_bf16, st);
+  if (e != hipSuccess) {
+    set_error("conv1x1_wgrad_reduce: launch failed: %s", hipGetErrorString(e));
+    return OCC_E_LAUNCH;
+  }
   return OCC_OK;
 }

@@ -2192,6 +2192,12 @@ def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None, varia
     variant: None = the launcher's choice; an int forces the tile (occ_conv3x3_nhwc_bf16_variant: 10 * NT + RT for
     (2 * RT) x 16 pixels x (128 * NT) channels per block; stride 1: 12, 13, 14, 16, 18, 22, 23, 24; stride 2: 12, 13,
     22; 0 = the launcher's choice through the same entry point)."""
+    return _conv3x3_nhwc(x, w_packed, bias, cout, relu, stride, amax, variant, 'bb_conv3x3')
+
+
+def _conv3x3_nhwc(x, w_packed, bias, cout, relu, stride, amax, variant, timing):
+    """conv3x3_nhwc booked under the kernel_timing entry `timing` (None: not booked; conv3x3_dgrad_nhwc books the whole call
+    under its own)."""
     _need_cl_bf16("conv3x3_nhwc", "x", x)
     _need_cuda_f32("bias", bias)
     N, Cin, H, W = x.shape
@@ -2204,14 +2210,81 @@ def conv3x3_nhwc(x, w_packed, bias, cout, relu=False, stride=1, amax=None, varia
         raise OccAmdError("conv3x3_nhwc: amax must be 8 contiguous int32 device words")
     out = torch.empty((N, cout, (H - 1) // st + 1, (W - 1) // st + 1), dtype=torch.bfloat16, device=x.device,
                       memory_format=torch.channels_last)
-    with torch.cuda.device(x.device), _timed('bb_conv3x3'):
+    with torch.cuda.device(x.device), _timed(timing):
         rc = _lib.lib().occ_conv3x3_nhwc_bf16_variant(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
                                                       i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
                                                       ptr(amax), i32(0 if variant is None else int(variant)),
                                                       stream_ptr(x.device))
-    _note_flops('bb_conv3x3', 2.0 * N * out.shape[2] * out.shape[3] * 9 * Cin * cout)
+    _note_flops(timing, 2.0 * N * out.shape[2] * out.shape[3] * 9 * Cin * cout)
     _lib.check(rc, "conv3x3_nhwc")
     return out
+
+
+def conv3x3_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
+    """Weight gradient of conv3x3_nhwc (csrc/conv3x3_wgrad_bf16.hip): dw[o, i, ky, kx] = sum over output pixels of
+    g[n, o, yo, xo] * x[n, i, yo * stride + ky - 1, xo * stride + kx - 1] (zero outside the map), f32 accumulation on the
+    matrix cores, deterministic.
+    g (N, Cout, Ho, Wo) and x (N, Cin, H, W) channels_last bf16 with Ho = (H - 1) // stride + 1 -> (Cout, Cin, 3, 3) in
+    out_dtype (float32 or bfloat16), channels_last strides (memory order [Cout][3][3][Cin]).  Cin % 32 == 0, Cout % 32 == 0,
+    both <= 2048, stride 1 or 2: OccAmdUnsupported otherwise.  splits: None = the launcher's choice of row ranges; an int
+    forces it (tests, probes)."""
+    _need_cl_bf16("conv3x3_wgrad_nhwc", "g", g)
+    _need_cl_bf16("conv3x3_wgrad_nhwc", "x", x)
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise OccAmdUnsupported("conv3x3_wgrad_nhwc: out_dtype must be float32 or bfloat16")
+    N, Cin, H, W = x.shape
+    s = int(stride)
+    Cout = g.shape[1]
+    if s not in (1, 2) or tuple(g.shape) != (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1) or g.device != x.device:
+        raise OccAmdUnsupported("conv3x3_wgrad_nhwc: g must be (N, Cout, (H-1)//stride+1, (W-1)//stride+1) on x's device, "
+                                "stride 1 or 2")
+    sp = 0 if splits is None else int(splits)
+    if sp < 0 or (splits is not None and sp == 0):
+        raise OccAmdError("conv3x3_wgrad_nhwc: splits must be None or a positive int")
+    lib = _lib.lib()
+    nbytes = int(lib.occ_conv3x3_wgrad_workspace_bytes(i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp)))
+    if nbytes <= 0:
+        raise OccAmdUnsupported("conv3x3_wgrad_nhwc: needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048 "
+                                f"(Cin={Cin}, Cout={Cout})")
+    dw = torch.empty((Cout, Cin, 3, 3), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)     # torch's caching allocator
+    with torch.cuda.device(x.device), _timed('bb_conv3x3_wgrad'):
+        rc = lib.occ_conv3x3_wgrad_nhwc_bf16(ptr(g), ptr(x), ptr(dw), i32(1 if out_dtype == torch.bfloat16 else 0), ptr(ws),
+                                             i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp),
+                                             stream_ptr(x.device))
+    _note_flops('bb_conv3x3_wgrad', 2.0 * N * g.shape[2] * g.shape[3] * 9 * Cin * Cout)
+    _lib.check(rc, "conv3x3_wgrad_nhwc")
+    return dw
+
+
+def conv3x3_dgrad_weight(weight):
+    """(Cout, Cin, 3, 3) weight -> the weight of the stride-1 data gradient as a convolution of g:
+    Wd[i, o, ky, kx] = weight[o, i, 2 - ky, 2 - kx] (spatially flipped, input and output channels transposed).  A view."""
+    if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+        raise OccAmdError("conv3x3_dgrad_weight: expected a (Cout, Cin, 3, 3) weight")
+    return weight.flip(2, 3).transpose(0, 1)
+
+
+def conv3x3_dgrad_nhwc(g, w16):
+    """Data gradient of a stride-1 conv3x3_nhwc: gx[n, i, y, x] = sum over (o, ky, kx) of g[n, o, y + 1 - ky, x + 1 - kx] *
+    w16[o, i, ky, kx] — the forward kernel on conv3x3_dgrad_weight(w16) (zero bias, no ReLU); no kernel of its own.
+    g (N, Cout, H, W) channels_last bf16; w16 (Cout, Cin, 3, 3) device weight (any strides) -> (N, Cin, H, W) channels_last
+    bf16.  Cin % 128 == 0 and Cout % 32 == 0 (the forward kernel's shapes with the channels swapped): OccAmdUnsupported
+    otherwise."""
+    _need_cl_bf16("conv3x3_dgrad_nhwc", "g", g)
+    if not (isinstance(w16, torch.Tensor) and w16.is_cuda and w16.is_floating_point() and w16.dim() == 4
+            and tuple(w16.shape[2:]) == (3, 3) and w16.shape[0] == g.shape[1] and w16.device == g.device):
+        raise OccAmdUnsupported("conv3x3_dgrad_nhwc: w16 must be a (Cout, Cin, 3, 3) device weight matching g's channels")
+    O, I = w16.shape[0], w16.shape[1]
+    if I % 128 or O % 32:
+        raise OccAmdUnsupported(f"conv3x3_dgrad_nhwc: needs Cin % 128 == 0 and Cout % 32 == 0 (Cin={I}, Cout={O})")
+    # one kernel_timing entry for the whole call: the flip + transpose + pack of the weight and the zero bias are paid per call,
+    # and the launch is not booked as a forward bb_conv3x3 launch as well
+    with torch.cuda.device(g.device), _timed('bb_conv3x3_dgrad'):
+        packed = conv3x3_pack_weight(conv3x3_dgrad_weight(w16).float().contiguous())
+        gx = _conv3x3_nhwc(g, packed, torch.zeros(I, dtype=torch.float32, device=g.device), I, False, 1, None, None, None)
+    _note_flops('bb_conv3x3_dgrad', 2.0 * g.shape[0] * g.shape[2] * g.shape[3] * 9 * I * O)
+    return gx
 
 
 def conv3x3_conv1x1_pick(batch, H, W, cmid, cout, stride=1):

@@ -60,9 +60,14 @@ class ConvBNActFunction(torch.autograd.Function):
     weight gradients follow, and the fold's chain rule gives the gradients of W, gamma and beta.  Same function and the same
     gradients as conv_bn_folded up to bf16 rounding (the tail adds in fp32 and rounds once instead of three times).
     own_conv1x1_backward (opt-in, OCC_TRAIN_CONV1X1_BWD=1): the nodes whose forward ran conv1x1_nhwc take their weight
-    gradient from ext.conv1x1_wgrad_nhwc and, at stride 1, their data gradient from ext.conv1x1_dgrad_nhwc instead of MIOpen."""
+    gradient from ext.conv1x1_wgrad_nhwc and, at stride 1, their data gradient from ext.conv1x1_dgrad_nhwc instead of MIOpen.
+    own_conv3x3_backward (opt-in, OCC_TRAIN_CONV3X3_BWD=1, independent of the 1x1 switch): the nodes whose forward ran
+    conv3x3_nhwc take their weight gradient from ext.conv3x3_wgrad_nhwc and, at stride 1, their data gradient from
+    ext.conv3x3_dgrad_nhwc (the forward kernel on the flipped, transposed weight); the data gradient at stride 2, and at
+    stride 1 where Cin is no multiple of 128 (the forward kernel needs that of its output channels), stays on ATen."""
 
     own_conv1x1_backward = os.environ.get("OCC_TRAIN_CONV1X1_BWD", "0") == "1"
+    own_conv3x3_backward = os.environ.get("OCC_TRAIN_CONV3X3_BWD", "0") == "1"
 
     @staticmethod
     def forward(ctx, x, weight, gamma, beta, rstd, mean_rstd, conv_bias, residual, stride, padding, relu):
@@ -131,6 +136,20 @@ class ConvBNActFunction(torch.autograd.Function):
             if need[0] and stride[0] == 1:
                 gx = ext.conv1x1_dgrad_nhwc(g, w16)
             elif need[0]:
+                gx = torch.ops.aten.convolution_backward(g, x16, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
+                                                         (True, False, False))[0]
+        elif (ConvBNActFunction.own_conv3x3_backward and route == '3x3' and g.data_ptr() % 4 == 0
+                and x16.data_ptr() % 4 == 0):
+            # the nodes whose forward took conv3x3_nhwc, in the same way: conv3x3_wgrad_nhwc, and at stride 1 the forward kernel
+            # on the flipped, transposed weight where that kernel has the shape (Cin % 128 == 0: its output channels); every
+            # other data gradient (stride 2 is a scatter) stays on ATen.  The stride-2 WEIGHT gradients are not gated back to
+            # ATen: ahead of it on all four base-config shapes (EXPERIMENTS.md 8o)
+            gx = gw = None
+            if need[1] or need[2]:
+                gw = ext.conv3x3_wgrad_nhwc(g, x16, stride[0], out_dtype=torch.bfloat16)
+            if need[0] and stride[0] == 1 and x16.shape[1] % 128 == 0:
+                gx = ext.conv3x3_dgrad_nhwc(g, w16)
+            elif need[0]:          # stride 2, or Cin % 128: the forward kernel on the swapped channels has no such shape
                 gx = torch.ops.aten.convolution_backward(g, x16, w16, None, stride, padding, (1, 1), False, (0, 0), 1,
                                                          (True, False, False))[0]
         else:
