@@ -162,6 +162,10 @@ int occ_point_sampling_f32(const float* ref_3d, const float* lidar2img, const fl
  *             [1] += bilinear corners that fall inside their map (the N_in of the roofline formula)
  * Fused kernels exist for M=8, D=32, (L,P) in {(4,8),(4,4),(2,8),(1,8)}, Z | P; other shapes
  * return OCC_E_UNSUPPORTED.
+ * Alignment (OCC_E_INVALID before any launch; the same for the f16v / q16v entries): value and slots 16 bytes; ref_cam
+ * 8 bytes; offs 8 bytes with an even offs_stride.  16-bit value rows with L*P = 32 read a lane's four logits and offset
+ * pairs as 16-byte loads: offs and logits 16 bytes, both strides multiples of 4, and — on the head-major kernel with
+ * Z % 4 == 0 — ref_cam 16 bytes.
  */
 int occ_sca_fused_forward_f32(const float* value, const int64_t* spatial_shapes,
                               const int64_t* level_start_index, const float* offs,

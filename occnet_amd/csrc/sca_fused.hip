@@ -527,6 +527,25 @@ static int sca_dispatch(const void* value, int rowfmt /* 0 f32, 1 f16, 2 q16 */,
   OCC_CHECK_ARG(offs_stride >= (int64_t)M * L * P * 2 && logits_stride >= (int64_t)M * L * P,
                 "sca_fused_forward: row strides smaller than a row");
   OCC_CHECK_ARG((long)S * M * D * 4 < (long)kOobOffset, "sca_fused_forward: value batch entry too large");
+  // alignment: 16-byte pieces of value rows and 16-byte stores of the result; float2 reads of the offset pairs and the anchors
+  const char* hm_env = getenv("OCC_SCA_HEAD_MAJOR");
+  const bool head_major = !(hm_env != nullptr && hm_env[0] == '0');
+  const auto misaligned = [](const void* p, unsigned n) { return reinterpret_cast<uintptr_t>(p) % n != 0; };
+  OCC_CHECK_ARG(!misaligned(value, 16), "sca_fused_forward: value must be 16-byte aligned");
+  OCC_CHECK_ARG(!misaligned(slots, 16), "sca_fused_forward: slots must be 16-byte aligned");
+  OCC_CHECK_ARG(!misaligned(ref_cam, 8), "sca_fused_forward: ref_cam must be 8-byte aligned");
+  OCC_CHECK_ARG(!misaligned(offs, 8), "sca_fused_forward: offs must be 8-byte aligned");
+  OCC_CHECK_ARG(offs_stride % 2 == 0, "sca_fused_forward: offs row stride must be even");
+  if (halfv && L * P == 32) {
+    // the 16-bit-row kernels read a lane's four logits and its four offset pairs as 16-byte loads
+    OCC_CHECK_ARG(!misaligned(offs, 16) && !misaligned(logits, 16),
+                  "sca_fused_forward: offs and logits must be 16-byte aligned for 16-bit value rows with L*P = 32");
+    OCC_CHECK_ARG(offs_stride % 4 == 0 && logits_stride % 4 == 0,
+                  "sca_fused_forward: offs and logits row strides must be multiples of 4 for 16-bit value rows with L*P = 32");
+    // the head-major kernel reads a lane's four consecutive anchors as two 16-byte loads
+    OCC_CHECK_ARG(!(head_major && Z % 4 == 0) || !misaligned(ref_cam, 16),
+                  "sca_fused_forward: ref_cam must be 16-byte aligned for the head-major kernel with L*P = 32 and Z %% 4 == 0");
+  }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (M != 8 || D != 32) {
     set_error("sca_fused_forward: no fused kernel for M=%d D=%d", M, D);
@@ -537,9 +556,7 @@ static int sca_dispatch(const void* value, int rowfmt /* 0 f32, 1 f16, 2 q16 */,
   // The 16-bit-row gathers run on the head-major kernel (default since round 6: 0.196 against 0.218 ms per launch, same box,
   // profiles/r06_c9_sca_head_major_sweep.txt); OCC_SCA_HEAD_MAJOR=0 selects the query-major kernel (read per call: tests
   // switch it inside one process).  (waves / SIMD, window, waves / block) = (4, 2, 4) measured best of (3, 4, 4) 0.2047,
-  // (4, 2, 8) 0.2051, (4, 1, 4) 0.2044 ms.
-  const char* hm_env = getenv("OCC_SCA_HEAD_MAJOR");
-  const bool head_major = !(hm_env != nullptr && hm_env[0] == '0');
+  // (4, 2, 8) 0.2051, (4, 1, 4) 0.2044 ms.  (`head_major` is read above, where the alignment checks need it.)
 #define OCC_SCA_CASE(LL, PP)                                                                       \
   if (L == LL && P == PP) {                                                                        \
     if (rowfmt == 2 && head_major)                                                                 \

@@ -238,7 +238,10 @@ def sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, re
     (what value_proj_bf16 / value_proj_bf16_planes write into an fp16 output); "rows" (default) converts a row-ordered
     fp16 tensor first (a copy: tests and the fp32-projection path only).
     value_scale (fp16 maps only): 1-element float32 device tensor s, a power of two — the maps hold s * value
-    (value_range_scale / f16_range_scaled), the kernel divides its fp32 sums by count * s: the same result, whatever s."""
+    (value_range_scale / f16_range_scaled), the kernel divides its fp32 sums by count * s: the same result, whatever s.
+    Alignment (refused before any launch): value 16 bytes; ref_cam 8 bytes; offs 8 bytes with an even row stride.  With 16-bit
+    rows and L*P = 32: offs and logits 16 bytes with row strides that are multiples of 4, and ref_cam 16 bytes on the
+    head-major kernel when Z % 4 == 0.  Slices of one Linear output at columns that are multiples of 4 satisfy all of it."""
     q16 = value.dtype == torch.int16
     half = value.dtype == torch.float16 or q16
     if q16 and value_layout != "pairs":
@@ -278,6 +281,21 @@ def sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, re
         raise OccAmdError("sca_fused_forward: vis_bits must be contiguous int32 (B,Nq)")
     if order is not None and (order.dtype != torch.int32 or order.numel() != Nq):
         raise OccAmdError("sca_fused_forward: order must be int32 (Nq)")
+    # the library refuses the same (sca_dispatch): float2 reads of offset pairs and anchors, 16-byte pieces of value rows; the
+    # 16-bit-row kernels with L*P = 32 read four logits / four offset pairs (head-major: four anchors) as 16-byte loads
+    if value.data_ptr() % 16:
+        raise OccAmdError("sca_fused_forward: value must be 16-byte aligned")
+    if ref_cam.data_ptr() % 8:
+        raise OccAmdError("sca_fused_forward: ref_cam must be 8-byte aligned")
+    if offs.data_ptr() % 8 or offs.stride(1) % 2:
+        raise OccAmdError("sca_fused_forward: offs must be 8-byte aligned with an even row stride (float2 reads)")
+    if half and L * P == 32:
+        if offs.data_ptr() % 16 or logits.data_ptr() % 16 or offs.stride(1) % 4 or logits.stride(1) % 4:
+            raise OccAmdError("sca_fused_forward: offs and logits must be 16-byte aligned with row strides that are multiples "
+                              "of 4 for 16-bit value rows with L*P = 32")
+        if Z % 4 == 0 and not os.environ.get("OCC_SCA_HEAD_MAJOR", "1").startswith("0") and ref_cam.data_ptr() % 16:
+            raise OccAmdError("sca_fused_forward: ref_cam must be 16-byte aligned for the head-major kernel with L*P = 32 "
+                              "and Z % 4 == 0")
     slots = torch.empty((B, Nq, M * D), dtype=torch.float32, device=value.device)
     fn = (_lib.lib().occ_sca_fused_forward_q16v if q16 else _lib.lib().occ_sca_fused_forward_f16v if half
           else _lib.lib().occ_sca_fused_forward_f32)

@@ -8,8 +8,8 @@ import pytest
 import torch
 
 from occnet_amd import ext, synthetic
-from oracle.msda import multi_scale_deformable_attn_pytorch
 from tests.grad_bounds import SCA_FUSED_GRAD_ABS, SCA_FUSED_GRAD_REL
+from tests.sca_ref import sca_gather_ref
 from tests.util import build_pair, small_cfg
 
 pytestmark = pytest.mark.gpu
@@ -47,26 +47,12 @@ def _case(B, L, P, Nq=400, NC=6, Z=4, seed=0):
 
 def _restated(c):
     """float64 autograd restatement -> (grad_value, grad_offs, grad_logits)."""
-    B, L, P, Nq, NC, Z = c['B'], c['L'], c['P'], c['Nq'], c['NC'], c['Z']
+    P, Z = c['P'], c['Z']
     value = c['value'].double().requires_grad_(True)
     lin = c['lin'].double().requires_grad_(True)
-    offs = lin[..., :c['n_off']].reshape(B, Nq, M, L, P // Z, Z, 2)
-    logits = lin[..., c['n_off']:c['n_off'] + c['n_att']].reshape(B, Nq, M, L * P)
-    aw = logits.softmax(-1).view(B, Nq, M, L, P)
-    norm = torch.stack([c['shapes'][:, 1], c['shapes'][:, 0]], -1).double()      # (W, H)
-    off = offs / norm[None, None, None, :, None, None, :]
-    vis = c['vis'].to(torch.int64)
-    slots = 0
-    for cam in range(NC):
-        ref = c['ref_cam'][cam].double()                                           # (B, Nq, Z, 2)
-        loc = (ref[:, :, None, None, None, :, :] + off).view(B, Nq, M, L, P, 2)
-        out = multi_scale_deformable_attn_pytorch(value[cam::NC], c['shapes'], loc, aw)
-        seen0 = ((vis[0] >> cam) & 1).double()                                     # batch 0's mask picks the cameras
-        slots = slots + out * seen0[None, :, None]
-    count = torch.zeros(B, Nq, dtype=torch.float64)
-    for cam in range(NC):
-        count += ((vis >> cam) & 1).double()
-    slots = slots / count.clamp(min=1.0)[..., None]
+    offs = lin[..., :c['n_off']]
+    logits = lin[..., c['n_off']:c['n_off'] + c['n_att']]
+    slots = sca_gather_ref(value, c['shapes'], offs, logits, c['ref_cam'], c['vis'], P, Z)      # the forward: tests/sca_ref.py
     (slots * c['grad_slots'].double()).sum().backward()
     g = lin.grad
     return value.grad, g[..., :c['n_off']], g[..., c['n_off']:c['n_off'] + c['n_att']]
