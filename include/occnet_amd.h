@@ -527,6 +527,33 @@ int occ_dropout_add_ln_bwd_f32(const float* grad_y, const float* z, const float*
                                uint64_t seed, float* grad_x, float* grad_residual, float* partial, float* grad_gamma_beta,
                                int64_t rows, int C, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-mode BatchNorm3d + ReLU of the voxel decoder on the convolution's channels-last output (reference:
+ * ConvModule(Conv3d -> BatchNorm3d -> ReLU), transformer_occ.py:106-126, and ATen's autograd of it: batch_norm's statistics /
+ * normalise kernels, relu, threshold_backward, batch_norm_backward's two kernels, the permute copies of layer 2).  C = 32
+ * only; OCC_E_UNSUPPORTED for another C, for fewer than 2 rows (torch raises there too) and for 2^31 elements or more
+ * (counted on the zero-haloed grid for the calls that take one).  y: (rows, 32) = (B, Y, X, Z, 32) contiguous fp32.
+ *   stats   : mean_rstd (2, 32) = per-channel mean | 1 / sqrt(biased variance + eps) over the rows (shifted sums, fp64 second
+ *             stage).  running_mean / running_var: both NULL (nothing is written) or both given, updated in place:
+ *             running_mean = (1 - eaf) running_mean + eaf mean ; running_var = (1 - eaf) running_var + eaf var rows / (rows - 1).
+ *   fwd     : out = max(0, (y - mean) rstd gamma + beta); element (b, y, x, z, c) of out at b out_sb + y out_sy + x out_sx +
+ *             32 z + c (as occ_conv3d_bn_relu_*: the (B, X, Y, Z, C) order of the reference's permute is a choice of strides).
+ *   bwd     : dz = grad_out [pre-activation > 0] with grad_out read through go_sb / go_sy / go_sx; grad_gamma_beta (2, 32) =
+ *             sum dz xhat | sum dz; dy = gamma rstd (dz - sum dz / rows - xhat sum(dz xhat) / rows) written to grad_y
+ *             (B, Y, X, Z, 32) contiguous and / or grad_y_pad (B, Y+2, X+2, Z+2, 32) INCLUDING its zero halo (no pre-zeroing;
+ *             the operand occ_conv3d_wgrad_bf16x3_f32 takes).  Either may be NULL.
+ * partial: occ_bn3d_relu_train_partial_floats(rows, C) floats of scratch (0: unsupported), shared by stats and bwd.  Sums are
+ * taken in a fixed order: every output is the same bits run to run. */
+int64_t occ_bn3d_relu_train_partial_floats(int64_t rows, int C);
+int occ_bn3d_relu_train_stats_f32(const float* y, float* partial, float* mean_rstd, float* running_mean, float* running_var,
+                                  float eaf, float eps, int64_t rows, int C, void* stream);
+int occ_bn3d_relu_train_fwd_f32(const float* y, const float* mean_rstd, const float* gamma, const float* beta, float* out, int B,
+                                int Z, int Y, int X, int C, int64_t out_sb, int64_t out_sy, int64_t out_sx, void* stream);
+int occ_bn3d_relu_train_bwd_f32(const float* grad_out, int64_t go_sb, int64_t go_sy, int64_t go_sx, const float* y,
+                                const float* mean_rstd, const float* gamma, const float* beta, float* partial,
+                                float* grad_gamma_beta, float* grad_y, float* grad_y_pad, int B, int Z, int Y, int X, int C,
+                                void* stream);
+
 /* SCA value projection straight off the backbone's bf16 feature maps (rows A3/A8: replaces the reference's
  * fp32 feature flatten + embedding adds, transformer_occ.py:204-222, AND MSDeformableAttention3D.value_proj,
  * spatial_cross_attention.py:366), all FPN levels in one launch.  For segment (= level) s, row m = g*rpg_s + i:

@@ -1374,41 +1374,53 @@ class Conv3dX3Function(torch.autograd.Function):
     def backward(ctx, gout):
         x, weight = ctx.saved_tensors
         Z, Y, X, in_layout = ctx.geom
-        cout, cin = weight.shape[:2]
-        B = x.shape[0]
         gout = gout.contiguous()
         gx = gw = None
-        one = torch.ones(32, dtype=torch.float32, device=x.device)
-        zero = torch.zeros(32, dtype=torch.float32, device=x.device)
         if ctx.needs_input_grad[0]:
-            wt = weight.detach().flip(2, 3, 4).transpose(0, 1)               # (cin, cout, 3, 3, 3): dY -> dX
-            parts = []
-            for c0 in range(0, cin, 32):                                     # the kernel writes 32 channels per launch
-                wg = wt[c0:c0 + 32]
-                if wg.shape[0] < 32:
-                    wg = torch.cat([wg, wg.new_zeros((32 - wg.shape[0],) + tuple(wg.shape[1:]))], 0)
-                g32 = conv3d_bn_relu(gout, conv3d_pack_weight(wg.contiguous()), one, zero, Z, Y, X, cout, 32, 0, relu=False)
-                parts.append(g32[..., :min(32, cin - c0)])
-            gx = parts[0] if len(parts) == 1 else torch.cat(parts, -1)
-            gx = gx.permute(0, 1, 2, 4, 3).reshape(B, Y * X, cin * Z) if in_layout == 1 else gx.contiguous()
+            gx = _conv3d_x3_dgrad(gout, weight, x.shape[0], Z, Y, X, in_layout)
         if ctx.needs_input_grad[1]:
-            xc = x.detach()
-            if in_layout == 1:
-                xc = xc.view(B, Y, X, cin, Z).permute(0, 1, 2, 4, 3)                # (B, Y, X, Z, cin) view
-            xp = torch.nn.functional.pad(xc, (0, 0, 1, 1, 1, 1, 1, 1)).contiguous()      # (B, Y+2, X+2, Z+2, cin)
             gp = torch.nn.functional.pad(gout, (0, 0, 1, 1, 1, 1, 1, 1)).contiguous()    # (B, Y+2, X+2, Z+2, 32)
-            lib = _lib.lib()
-            nbytes = int(lib.occ_conv3d_wgrad_workspace_bytes(i32(B), i32(Z), i32(Y), i32(X), i32(cin)))
-            if nbytes <= 0:
-                raise OccAmdUnsupported("conv3d wgrad: grid beyond the kernel's 32-bit row range")
-            ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
-            dw = torch.empty((cout, 27, cin), dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device), _timed('conv3d_wgrad'):
-                rc = lib.occ_conv3d_wgrad_bf16x3_f32(ptr(gp), ptr(xp), ptr(dw), ptr(ws), i64(nbytes), i32(B), i32(Z),
-                                                     i32(Y), i32(X), i32(cin), stream_ptr(x.device))
-            _lib.check(rc, "conv3d_wgrad")
-            gw = dw.permute(0, 2, 1).reshape(cout, cin, 3, 3, 3)
+            gw = _conv3d_x3_wgrad(gp, x, weight, Z, Y, X, in_layout)
         return gx, gw, None, None, None, None
+
+
+def _conv3d_x3_dgrad(gout, weight, B, Z, Y, X, in_layout):
+    """Data gradient of Conv3dX3Function's convolution: gout (B, Y, X, Z, 32) contiguous -> the gradient in x's layout."""
+    cout, cin = weight.shape[:2]
+    one = torch.ones(32, dtype=torch.float32, device=gout.device)
+    zero = torch.zeros(32, dtype=torch.float32, device=gout.device)
+    wt = weight.detach().flip(2, 3, 4).transpose(0, 1)               # (cin, cout, 3, 3, 3): dY -> dX
+    parts = []
+    for c0 in range(0, cin, 32):                                     # the kernel writes 32 channels per launch
+        wg = wt[c0:c0 + 32]
+        if wg.shape[0] < 32:
+            wg = torch.cat([wg, wg.new_zeros((32 - wg.shape[0],) + tuple(wg.shape[1:]))], 0)
+        g32 = conv3d_bn_relu(gout, conv3d_pack_weight(wg.contiguous()), one, zero, Z, Y, X, cout, 32, 0, relu=False)
+        parts.append(g32[..., :min(32, cin - c0)])
+    gx = parts[0] if len(parts) == 1 else torch.cat(parts, -1)
+    return gx.permute(0, 1, 2, 4, 3).reshape(B, Y * X, cin * Z) if in_layout == 1 else gx.contiguous()
+
+
+def _conv3d_x3_wgrad(gp, x, weight, Z, Y, X, in_layout):
+    """Weight gradient of Conv3dX3Function's convolution: gp (B, Y+2, X+2, Z+2, 32) the zero-padded output gradient, x the
+    node's input in its own layout (padded here) -> (32, cin, 3, 3, 3)."""
+    cout, cin = weight.shape[:2]
+    B = x.shape[0]
+    xc = x.detach()
+    if in_layout == 1:
+        xc = xc.view(B, Y, X, cin, Z).permute(0, 1, 2, 4, 3)                # (B, Y, X, Z, cin) view
+    xp = torch.nn.functional.pad(xc, (0, 0, 1, 1, 1, 1, 1, 1)).contiguous()      # (B, Y+2, X+2, Z+2, cin)
+    lib = _lib.lib()
+    nbytes = int(lib.occ_conv3d_wgrad_workspace_bytes(i32(B), i32(Z), i32(Y), i32(X), i32(cin)))
+    if nbytes <= 0:
+        raise OccAmdUnsupported("conv3d wgrad: grid beyond the kernel's 32-bit row range")
+    ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
+    dw = torch.empty((cout, 27, cin), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device), _timed('conv3d_wgrad'):
+        rc = lib.occ_conv3d_wgrad_bf16x3_f32(ptr(gp), ptr(xp), ptr(dw), ptr(ws), i64(nbytes), i32(B), i32(Z),
+                                             i32(Y), i32(X), i32(cin), stream_ptr(x.device))
+    _lib.check(rc, "conv3d_wgrad")
+    return dw.permute(0, 2, 1).reshape(cout, cin, 3, 3, 3)
 
 
 def conv3d_autograd(x, weight, Z, Y, X, in_layout=0):
@@ -1417,6 +1429,137 @@ def conv3d_autograd(x, weight, Z, Y, X, in_layout=0):
     if cout != 32 or not (cin % 16 == 0 or cin == 8) or Z not in (4, 8, 16, 32) or CONV3D_PRECISION != "bf16x3":
         raise OccAmdUnsupported("conv3d_autograd: needs Cout = 32, Cin % 16 == 0 or Cin == 8, Z in {4, 8, 16, 32}")
     return Conv3dX3Function.apply(x, weight, Z, Y, X, in_layout)
+
+
+def bn3d_relu_train_partial(rows, C, device):
+    """Scratch of bn3d_relu_train_stats / bn3d_relu_train_bwd for (rows, C) rows; OccAmdUnsupported outside C = 32,
+    rows >= 2, fewer than 2^31 elements."""
+    n = int(_lib.lib().occ_bn3d_relu_train_partial_floats(i64(rows), i32(C)))
+    if n <= 0:
+        raise OccAmdUnsupported(f"bn3d_relu_train: rows={rows} C={C}: needs C = 32, rows >= 2, fewer than 2^31 elements")
+    return torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bn3d_relu_train_stats(y, running_mean, running_var, eaf, eps):
+    """Batch statistics of y (..., 32) over all leading dimensions (csrc/bn3d_relu_train.hip) -> mean_rstd (2, 32) = mean |
+    1 / sqrt(biased var + eps).  running_mean / running_var (both or neither; fp32 device tensors) are updated in place as
+    nn.BatchNorm3d does in training, with the exponential average factor eaf."""
+    _need_cuda_f32("y", y)
+    if (running_mean is None) != (running_var is None):
+        raise OccAmdError("bn3d_relu_train_stats: running_mean and running_var come together or not at all")
+    C = y.shape[-1]
+    for n, t in (("running_mean", running_mean), ("running_var", running_var)):
+        if t is not None:
+            _need_cuda_f32(n, t)
+            if t.numel() != C:
+                raise OccAmdError(f"bn3d_relu_train_stats: {n} must have {C} elements")
+    rows = y.numel() // C
+    partial = bn3d_relu_train_partial(rows, C, y.device)
+    mean_rstd = torch.empty((2, C), dtype=torch.float32, device=y.device)
+    with torch.cuda.device(y.device), _timed('bn3d_relu_train'):
+        rc = _lib.lib().occ_bn3d_relu_train_stats_f32(ptr(y), ptr(partial), ptr(mean_rstd), ptr(running_mean),
+                                                      ptr(running_var), f32(eaf), f32(eps), i64(rows), i32(C),
+                                                      stream_ptr(y.device))
+    _lib.check(rc, "bn3d_relu_train_stats")
+    if running_mean is not None:        # written through raw pointers: tell autograd (and every version-keyed cache)
+        torch._C._increment_version((running_mean, running_var))
+    return mean_rstd
+
+
+def _bn3d_strides(Z, Y, X, C, xy_major):
+    """(batch, y, x) element strides of a (B, Y, X, Z, C) tensor, or of its (B, X, Y, Z, C) arrangement"""
+    return (Y * X * Z * C,) + ((Z * C, Y * Z * C) if xy_major else (X * Z * C, Z * C))
+
+
+def bn3d_relu_train_fwd(y, mean_rstd, gamma, beta, Z, Y, X, out_xy_major=False):
+    """relu((y - mean) * rstd * gamma + beta) of y (B, Y, X, Z, 32) -> (B, Y, X, Z, 32), or (B, X, Y, Z, 32) with out_xy_major
+    (the reference's permute(0, 4, 3, 2, 1) order, written directly)."""
+    for n, t in (("y", y), ("mean_rstd", mean_rstd), ("gamma", gamma), ("beta", beta)):
+        _need_cuda_f32(n, t)
+    C = y.shape[-1]
+    B = y.numel() // (Z * Y * X * C)
+    if y.numel() != B * Z * Y * X * C or mean_rstd.numel() != 2 * C or gamma.numel() != C or beta.numel() != C:
+        raise OccAmdError("bn3d_relu_train_fwd: inconsistent shapes")
+    out = torch.empty((B, X, Y, Z, C) if out_xy_major else (B, Y, X, Z, C), dtype=torch.float32, device=y.device)
+    sb, sy, sx = _bn3d_strides(Z, Y, X, C, out_xy_major)
+    with torch.cuda.device(y.device), _timed('bn3d_relu_train'):
+        rc = _lib.lib().occ_bn3d_relu_train_fwd_f32(ptr(y), ptr(mean_rstd), ptr(gamma), ptr(beta), ptr(out), i32(B), i32(Z),
+                                                    i32(Y), i32(X), i32(C), i64(sb), i64(sy), i64(sx), stream_ptr(y.device))
+    _lib.check(rc, "bn3d_relu_train_fwd")
+    return out
+
+
+def bn3d_relu_train_bwd(grad_out, y, mean_rstd, gamma, beta, Z, Y, X, grad_xy_major=False, want_grad_y=True,
+                        want_grad_y_pad=False):
+    """Backward of bn3d_relu_train_fwd.  grad_out: contiguous in the forward output's own shape ((B, X, Y, Z, 32) with
+    grad_xy_major).  -> (grad_y (B, Y, X, Z, 32) or None, grad_y_pad (B, Y+2, X+2, Z+2, 32) with its zero halo or None,
+    dgamma (32), dbeta (32))."""
+    for n, t in (("grad_out", grad_out), ("y", y), ("mean_rstd", mean_rstd), ("gamma", gamma), ("beta", beta)):
+        _need_cuda_f32(n, t)
+    C = y.shape[-1]
+    B = y.numel() // (Z * Y * X * C)
+    if (y.numel() != B * Z * Y * X * C or grad_out.numel() != y.numel() or mean_rstd.numel() != 2 * C or gamma.numel() != C
+            or beta.numel() != C):
+        raise OccAmdError("bn3d_relu_train_bwd: inconsistent shapes")
+    partial = bn3d_relu_train_partial(B * Z * Y * X, C, y.device)
+    ggb = torch.empty((2, C), dtype=torch.float32, device=y.device)
+    gy = torch.empty((B, Y, X, Z, C), dtype=torch.float32, device=y.device) if want_grad_y else None
+    gp = torch.empty((B, Y + 2, X + 2, Z + 2, C), dtype=torch.float32, device=y.device) if want_grad_y_pad else None
+    sb, sy, sx = _bn3d_strides(Z, Y, X, C, grad_xy_major)
+    with torch.cuda.device(y.device), _timed('bn3d_relu_train'):
+        rc = _lib.lib().occ_bn3d_relu_train_bwd_f32(ptr(grad_out), i64(sb), i64(sy), i64(sx), ptr(y), ptr(mean_rstd), ptr(gamma),
+                                                    ptr(beta), ptr(partial), ptr(ggb), ptr(gy), ptr(gp), i32(B), i32(Z), i32(Y),
+                                                    i32(X), i32(C), stream_ptr(y.device))
+    _lib.check(rc, "bn3d_relu_train_bwd")
+    return gy, gp, ggb[0], ggb[1]
+
+
+class Conv3dBNReLUFunction(torch.autograd.Function):
+    """One decoder layer in training, Conv3d(k3, s1, p1, no bias, Cout = 32) -> BatchNorm3d (batch statistics) -> ReLU, as ONE
+    autograd node (reference: ConvModule, transformer_occ.py:106-126, under ATen autograd).  The convolution, its data and
+    weight gradients are Conv3dX3Function's; statistics, normalise + ReLU and their backward are csrc/bn3d_relu_train.hip.  Saves
+    the convolution's output y, not the activation: the backward recomputes the ReLU mask from y with the forward's own
+    expression, and writes dy both as the contiguous tensor of the data-gradient convolution and as the zero-padded tensor of
+    the weight-gradient kernel.  running_mean / running_var (or None, None) are updated in place with the exponential average
+    factor eaf.  -> (B, Y, X, Z, 32), or (B, X, Y, Z, 32) with out_xy_major."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, running_mean, running_var, eaf, eps, Z, Y, X, in_layout, out_xy_major):
+        cout, cin = weight.shape[:2]
+        one = torch.ones(cout, dtype=torch.float32, device=x.device)
+        zero = torch.zeros(cout, dtype=torch.float32, device=x.device)
+        y = conv3d_bn_relu(x.contiguous(), conv3d_pack_weight(weight.detach().contiguous()), one, zero, Z, Y, X, cin, cout,
+                           in_layout, relu=False)
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        mean_rstd = bn3d_relu_train_stats(y, running_mean, running_var, eaf, eps)
+        out = bn3d_relu_train_fwd(y, mean_rstd, g, b, Z, Y, X, out_xy_major)
+        ctx.save_for_backward(x, weight, y, mean_rstd, gamma, beta)
+        ctx.geom = (int(Z), int(Y), int(X), int(in_layout), bool(out_xy_major))
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        x, weight, y, mean_rstd, gamma, beta = ctx.saved_tensors
+        Z, Y, X, in_layout, xy_major = ctx.geom
+        need_x, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        gy, gp, dgamma, dbeta = bn3d_relu_train_bwd(gout.contiguous(), y, mean_rstd, gamma.detach().contiguous(),
+                                                    beta.detach().contiguous(), Z, Y, X, grad_xy_major=xy_major,
+                                                    want_grad_y=need_x, want_grad_y_pad=need_w)
+        gx = _conv3d_x3_dgrad(gy, weight, x.shape[0], Z, Y, X, in_layout) if need_x else None
+        gw = _conv3d_x3_wgrad(gp, x, weight, Z, Y, X, in_layout) if need_w else None
+        return (gx, gw, dgamma.view(gamma.shape) if ctx.needs_input_grad[2] else None,
+                dbeta.view(beta.shape) if ctx.needs_input_grad[3] else None) + (None,) * 9
+
+
+def conv3d_bn_relu_autograd(x, weight, gamma, beta, running_mean, running_var, eaf, eps, Z, Y, X, in_layout=0,
+                            out_xy_major=False):
+    """Differentiable Conv3d(k3, s1, p1, no bias, Cout = 32) -> BatchNorm3d(training) -> ReLU (Conv3dBNReLUFunction)."""
+    cout, cin = weight.shape[:2]
+    if cout != 32 or not (cin % 16 == 0 or cin == 8) or Z not in (4, 8, 16, 32) or CONV3D_PRECISION != "bf16x3":
+        raise OccAmdUnsupported("conv3d_bn_relu_autograd: needs Cout = 32, Cin % 16 == 0 or Cin == 8, Z in {4, 8, 16, 32}")
+    return Conv3dBNReLUFunction.apply(x, weight, gamma, beta, running_mean, running_var, eaf, eps, Z, Y, X, in_layout,
+                                      out_xy_major)
 
 
 class LinearX3Function(torch.autograd.Function):

@@ -561,21 +561,56 @@ class TransformerOcc(BaseModule):
         return True
 
     @staticmethod
-    def _bn_rows(bn, x2d):
-        """nn.BatchNorm3d.forward on channels-last rows (N, C): statistics over N = every voxel of the batch."""
+    def _bn_eaf(bn):
+        """The exponential average factor of this call, counted as nn.BatchNorm3d.forward does (a training call with tracked
+        statistics advances num_batches_tracked)."""
         eaf = 0.0 if bn.momentum is None else bn.momentum
         if bn.training and bn.track_running_stats and bn.num_batches_tracked is not None:
             bn.num_batches_tracked.add_(1)
             eaf = 1.0 / float(bn.num_batches_tracked) if bn.momentum is None else bn.momentum
+        return eaf
+
+    @staticmethod
+    def _bn_rows(bn, x2d):
+        """nn.BatchNorm3d.forward on channels-last rows (N, C): statistics over N = every voxel of the batch."""
+        eaf = TransformerOcc._bn_eaf(bn)
         use_batch = bn.training or (bn.running_mean is None and bn.running_var is None)
         keep = not bn.training or bn.track_running_stats
         return F.batch_norm(x2d, bn.running_mean if keep else None, bn.running_var if keep else None, bn.weight,
                             bn.bias, use_batch, eaf, bn.eps)
 
+    # training: each decoder layer's Conv3d -> BatchNorm3d(batch statistics) -> ReLU as ONE autograd node
+    # (ext.Conv3dBNReLUFunction: statistics, normalise + ReLU and their backward on csrc/bn3d_relu_train.hip).  Opt-in.
+    train_decoder_fused_bn = os.environ.get("OCC_TRAIN_DECODER_BN", "0") == "1"
+
+    def _train_decoder_bn_ok(self, bev):
+        """Both norms are what Conv3dBNReLUFunction computes; asked before the first convolution runs (as in
+        _train_decoder_ok: the running statistics must update exactly once per call)."""
+        if not (self.train_decoder_fused_bn and self._train_decoder_ok(bev)):
+            return False
+        for m in (self.decoder[0], self.decoder[1]):
+            bn = m.norm
+            if not (bn.training and bn.affine and bn.num_features == 32):
+                return False
+            ts = [bn.weight, bn.bias] + ([bn.running_mean, bn.running_var] if bn.track_running_stats else [])
+            if any(t is None or t.dtype != torch.float32 or t.device != bev.device for t in ts):
+                return False
+        return True
+
     def _train_decoder(self, bev, bev_h, bev_w):
         """bev (bs, bev_h*bev_w, C) -> decoder features (bs, W, H, Z, out_dim), differentiable: lifter view + 2 x
         (Conv3d -> BatchNorm3d -> ReLU) + permute (reference transformer_occ.py:305-308)."""
         Z, bs = self.pillar_h, bev.shape[0]
+        # (the kernels' own size limit, on the zero-haloed grid, is asked here too: nothing may refuse after the first update)
+        if self._train_decoder_bn_ok(bev) and bs * (bev_h + 2) * (bev_w + 2) * (Z + 2) * 32 < 2 ** 31:
+            x = bev
+            for k, m in enumerate((self.decoder[0], self.decoder[1])):
+                bn = m.norm
+                keep = bn.track_running_stats
+                x = ext.conv3d_bn_relu_autograd(x, m.conv.weight, bn.weight, bn.bias, bn.running_mean if keep else None,
+                                                bn.running_var if keep else None, self._bn_eaf(bn), bn.eps, Z, bev_h, bev_w,
+                                                in_layout=1 - k, out_xy_major=k == 1)
+            return x                                                   # (bs, W, H, Z, C), written in that order
         x = ext.conv3d_autograd(bev, self.decoder[0].conv.weight, Z, bev_h, bev_w, in_layout=1)
         x = torch.relu_(self._bn_rows(self.decoder[0].norm, x.view(-1, x.shape[-1]))).view(bs, bev_h, bev_w, Z, -1)
         x = ext.conv3d_autograd(x, self.decoder[1].conv.weight, Z, bev_h, bev_w, in_layout=0)
