@@ -767,6 +767,25 @@ int occ_bottleneck64_nhwc_bf16(const void* x, const void* w1_frag, const float* 
                                const float* b2, const void* w3_frag, const float* b3, void* out, int batch,
                                int H, int W, int Cin, int downsample, void* stream);
 
+/* The same bottleneck with the kernel forced (tests, probes).  variant: 0 = the launcher's choice, as the entry point above
+ * (the second kernel; OCC_BOTTLENECK64_V2=0 in the environment, read once, keeps the first); 1 = the first kernel (f32 LDS
+ * transpose in the epilogue, identity read from x a second time, block b computes tile b); 2 = the second kernel
+ * (csrc/bottleneck64_v2_nhwc_bf16.hip: identity kept in registers from the staged tile, x read once) with its default
+ * tile order, 0 (OCC_BOTTLENECK64_ORDER=0 / 1 / 2, read once, overrides it); 3 / 4 / 5 = the second kernel with tile
+ * order 0 / 1 / 2 of occ_bottleneck64_tile_of_block (1, 2: XCD-local, fewer bytes fetched, measured slower).  Every
+ * variant computes the same bits.  An unknown variant returns OCC_E_UNSUPPORTED ("no variant"); argument checks run
+ * before any launch. */
+int occ_bottleneck64_nhwc_bf16_variant(const void* x, const void* w1_frag, const float* b1, const void* w2_frag,
+                                       const float* b2, const void* w3_frag, const float* b3, void* out, int batch,
+                                       int H, int W, int Cin, int downsample, int variant, void* stream);
+/* The tile (row-major linear index over image, tile row, tile column; 8 x 16 pixel tiles) that block `block` of a grid of
+ * n_blocks = batch * tiles_y * tiles_x blocks computes in the second kernel.  Blocks b, b + 8, b + 16, ... run on one XCD
+ * (one L2).  order 0: tile = block.  order 1: group b % 8 takes a contiguous range of the row-major walk, position
+ * x*q + min(x, r) + b / 8 with x = b % 8, q = n / 8, r = n % 8.  order 2: the same ranges of a walk that goes through each
+ * image in bands of 4 tile rows, column by column inside a band.  A permutation of 0 .. n_blocks - 1 for every order; a
+ * pure function, needs no GPU.  Bad arguments: OCC_E_INVALID (negative). */
+int occ_bottleneck64_tile_of_block(int block, int n_blocks, int tiles_x, int tiles_y, int order);
+
 /* ------------------------------------------------------------------------------------------
  * (e) Evaluation: RayIoU / mAVE counters of a batch of samples in one fused pass (csrc/ray_metrics_fused.hip) — the
  * reference's process_one_sample + main's non-free filter + calc_metrics (projects/mmdet3d_plugin/datasets/

@@ -343,10 +343,20 @@ extern "C" int occ_mfma_pack_b_frag_bf16(const float* weight, void* packed, int 
   return OCC_OK;
 }
 
-extern "C" int occ_bottleneck64_nhwc_bf16(const void* x, const void* w1_frag, const float* b1,
-                                          const void* w2_frag, const float* b2, const void* w3_frag,
-                                          const float* b3, void* out, int batch, int H, int W, int Cin,
-                                          int downsample, void* stream) {
+namespace occ {
+// the second kernel (bottleneck64_v2_nhwc_bf16.hip): same arguments, same bits; order = its block -> tile map
+void bottleneck64_v2_launch(const void* x, const void* w1_frag, const float* b1, const void* w2_frag, const float* b2,
+                            const void* w3_frag, const float* b3, void* out, int batch, int H, int W, int downsample,
+                            int order, hipStream_t st);
+constexpr int kBnOrderDefault = 0;           // tile order of the second kernel where nothing else is asked for: 1 and 2 fetch
+                                             // less and run slower (EXPERIMENTS.md section 8q)
+}  // namespace occ
+
+// variant: 0 = chosen here, 1 = the kernel above, 2 = the second kernel with its default tile order, 3 / 4 / 5 = the second
+// kernel with tile order 0 (the first kernel's) / 1 (XCD-contiguous, row-major) / 2 (XCD-contiguous, banded).
+static int bottleneck64_nhwc_bf16_launch(const void* x, const void* w1_frag, const float* b1, const void* w2_frag,
+                                         const float* b2, const void* w3_frag, const float* b3, void* out, int batch,
+                                         int H, int W, int Cin, int downsample, int variant, void* stream) {
   using namespace occ;
   OCC_CHECK_ARG(x && w1_frag && b1 && w2_frag && b2 && w3_frag && b3 && out,
                 "bottleneck64_nhwc_bf16: null pointer argument");
@@ -356,8 +366,27 @@ extern "C" int occ_bottleneck64_nhwc_bf16(const void* x, const void* w1_frag, co
               downsample);
     return OCC_E_UNSUPPORTED;
   }
-  const int tiles_x = (W + kBnTW - 1) / kBnTW, tiles_y = (H + kBnTH - 1) / kBnTH;
+  if (variant < 0 || variant > 5) {
+    set_error("bottleneck64_nhwc_bf16: no variant %d (1 = first kernel; 2 = second kernel; 3, 4, 5 = second kernel with "
+              "tile order 0, 1, 2)", variant);
+    return OCC_E_UNSUPPORTED;
+  }
+  // development switches, read once: OCC_BOTTLENECK64_V2=0 keeps every default launch on the first kernel;
+  // OCC_BOTTLENECK64_ORDER=0 / 1 / 2 sets the tile order of variants 0 and 2 (EXPERIMENTS.md section 8q)
+  static const bool v2_on = env_default_on("OCC_BOTTLENECK64_V2");
+  static const int order_default = [] {
+    const char* e = getenv("OCC_BOTTLENECK64_ORDER");
+    return e && e[0] >= '0' && e[0] <= '2' && !e[1] ? e[0] - '0' : kBnOrderDefault;
+  }();
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (variant == 0) variant = v2_on ? 2 : 1;
+  if (variant != 1) {
+    bottleneck64_v2_launch(x, w1_frag, b1, w2_frag, b2, w3_frag, b3, out, batch, H, W, downsample,
+                           variant == 2 ? order_default : variant - 3, st);
+    OCC_CHECK_LAUNCH("bottleneck64_nhwc_bf16");
+    return OCC_OK;
+  }
+  const int tiles_x = (W + kBnTW - 1) / kBnTW, tiles_y = (H + kBnTH - 1) / kBnTH;
   const unsigned gx = (unsigned)((long)batch * tiles_x * tiles_y);
 #define OCC_BN_LAUNCH(CINN, DSS)                                                                     \
   hipLaunchKernelGGL((bottleneck64_nhwc_bf16_kernel<CINN, DSS>), dim3(gx), dim3(256), 0, st,            \
@@ -368,4 +397,22 @@ extern "C" int occ_bottleneck64_nhwc_bf16(const void* x, const void* w1_frag, co
 #undef OCC_BN_LAUNCH
   OCC_CHECK_LAUNCH("bottleneck64_nhwc_bf16");
   return OCC_OK;
+}
+
+extern "C" int occ_bottleneck64_nhwc_bf16(const void* x, const void* w1_frag, const float* b1,
+                                          const void* w2_frag, const float* b2, const void* w3_frag,
+                                          const float* b3, void* out, int batch, int H, int W, int Cin,
+                                          int downsample, void* stream) {
+  return bottleneck64_nhwc_bf16_launch(x, w1_frag, b1, w2_frag, b2, w3_frag, b3, out, batch, H, W, Cin, downsample, 0,
+                                       stream);
+}
+
+// The same bottleneck with the kernel forced (tests, probes): see bottleneck64_nhwc_bf16_launch.  An unknown variant
+// returns OCC_E_UNSUPPORTED before any launch.  Every variant computes the same bits.
+extern "C" int occ_bottleneck64_nhwc_bf16_variant(const void* x, const void* w1_frag, const float* b1,
+                                                  const void* w2_frag, const float* b2, const void* w3_frag,
+                                                  const float* b3, void* out, int batch, int H, int W, int Cin,
+                                                  int downsample, int variant, void* stream) {
+  return bottleneck64_nhwc_bf16_launch(x, w1_frag, b1, w2_frag, b2, w3_frag, b3, out, batch, H, W, Cin, downsample,
+                                       variant, stream);
 }

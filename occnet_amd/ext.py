@@ -2312,19 +2312,27 @@ def bottleneck64_pack(w1, b1, w2, b2, w3, b3, wds=None, bds=None):
                 b2=b2.float().contiguous(), w3=mfma_pack_b_frag(w3), b3=b3.contiguous(), cin=cin, ds=ds)
 
 
-def bottleneck64_nhwc(x, pack):
+def bottleneck64_nhwc(x, pack, variant=0, out=None):
     """One whole stride-1 ResNet bottleneck (64 mid channels) on a channels_last bf16 activation, one launch.
-    x (N, Cin, H, W) channels_last bf16; pack from bottleneck64_pack -> (N, 256, H, W) channels_last bf16."""
+    x (N, Cin, H, W) channels_last bf16; pack from bottleneck64_pack -> (N, 256, H, W) channels_last bf16.
+    variant: 0 = the launcher's choice; an int forces the kernel (occ_bottleneck64_nhwc_bf16_variant: 1 = first kernel,
+    2 = second kernel, 3 / 4 / 5 = second kernel with tile order 0 / 1 / 2); every variant computes the same bits.
+    out: a (N, 256, H, W) channels_last bf16 tensor on x's device to write into (every element is written), or None."""
     _need_cl_bf16("bottleneck64_nhwc", "x", x)
     N, Cin, H, W = x.shape
     if Cin != pack['cin']:
         raise OccAmdError("bottleneck64_nhwc: x has %d channels, the pack was built for %d" % (Cin, pack['cin']))
-    out = torch.empty((N, 256, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    if out is None:
+        out = torch.empty((N, 256, H, W), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+    else:
+        _need_cl_bf16("bottleneck64_nhwc", "out", out)
+        if tuple(out.shape) != (N, 256, H, W) or out.device != x.device or out.data_ptr() == x.data_ptr():
+            raise OccAmdError("bottleneck64_nhwc: out must be a (N, 256, H, W) tensor on x's device, not x itself")
     with torch.cuda.device(x.device), _timed('bb_bottleneck64'):
-        rc = _lib.lib().occ_bottleneck64_nhwc_bf16(ptr(x), ptr(pack['w1']), ptr(pack['b1']), ptr(pack['w2']),
-                                                   ptr(pack['b2']), ptr(pack['w3']), ptr(pack['b3']), ptr(out),
-                                                   i32(N), i32(H), i32(W), i32(Cin), i32(1 if pack['ds'] else 0),
-                                                   stream_ptr(x.device))
+        rc = _lib.lib().occ_bottleneck64_nhwc_bf16_variant(ptr(x), ptr(pack['w1']), ptr(pack['b1']), ptr(pack['w2']),
+                                                           ptr(pack['b2']), ptr(pack['w3']), ptr(pack['b3']), ptr(out),
+                                                           i32(N), i32(H), i32(W), i32(Cin), i32(1 if pack['ds'] else 0),
+                                                           i32(int(variant)), stream_ptr(x.device))
     _note_flops('bb_bottleneck64', 2.0 * N * H * W * (Cin * 64 + 9 * 64 * 64 + 64 * 256 + (Cin * 256 if pack['ds'] else 0)))
     _lib.check(rc, "bottleneck64_nhwc")
     return out

@@ -229,7 +229,9 @@ class FusedInferenceBackbone(nn.Module):
         for bi, (c1, c2, c3, ds) in enumerate(self.stages[si]):
             whole = self._bneck.get((si, bi))
             if whole is not None and x.is_contiguous(memory_format=_CL):
-                x = ext.bottleneck64_nhwc(x, whole)
+                # OCC_BOTTLENECK64_V2=0 keeps the first kernel (development A/B inside one build; the same bits)
+                first = os.environ.get('OCC_BOTTLENECK64_V2', '1').startswith('0')
+                x = ext.bottleneck64_nhwc(x, whole, variant=1 if first else 0)
                 continue
             identity = x if ds is None else self._conv(ds, x)
             y = self._conv(c1, x, relu=True)
