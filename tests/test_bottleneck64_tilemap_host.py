@@ -7,7 +7,7 @@ import pytest
 
 from occnet_amd import _lib
 
-BAND = 4     # tile rows per band of order 2 (csrc/bottleneck64_v2_nhwc_bf16.hip: kB2Band)
+BAND = 4     # tile rows per band of order 2 (csrc/bottleneck64_v2_nhwc_bf16.hip: kBnBand)
 
 GRIDS = sorted({(b, ty, tx) for b in (1, 2, 3) for ty in range(1, 7) for tx in range(1, 7)}) + [(6, 29, 25)]
 
