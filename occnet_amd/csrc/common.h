@@ -1,4 +1,4 @@
-// Shared device helpers for the gfx950 deformable-gather kernels.
+// Shared device and host helpers of every gfx950 kernel file of this library (the deformable gathers' among them).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -323,26 +323,6 @@ __device__ __forceinline__ void fma_mix_lo(float& acc, float w, unsigned packed)
 }
 __device__ __forceinline__ void fma_mix_hi(float& acc, float w, unsigned packed) {
   asm("v_fma_mix_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[0,1,0]" : "+v"(acc) : "v"(w), "v"(packed));
-}
-
-// ---- shared by the fused gathers' backward kernels (sca_fused_backward.hip, tsa_fused_backward.hip) -----------------------------
-// one resolved sample for the gradient: byte offsets of the four corner rows (kOobOffset outside the map: the buffer load
-// returns 0, which is mmcv's "only in-range corners"), the fractional weights (0 for a sample outside its map)
-struct __attribute__((aligned(16))) BwdSampleParam {
-  unsigned o[4];
-  float lh, lw, pad0, pad1;
-};
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-  return fmaf(a.x, b.x, fmaf(a.y, b.y, fmaf(a.z, b.z, a.w * b.w)));
-}
-
-// One step of the reduce-scatter that folds 8 lanes' partial sums of 8 samples (xor 4, 2, 1) so that lane c of the group ends
-// with sample c: x (lane's copy) + the value held `mask` lanes away, where each lane keeps one half and sends the other; hi
-// (0 / 1 lane flag) selects which half this lane keeps
-__device__ __forceinline__ float rs_step(float lo, float hi_v, int hi, int mask) {
-  const float keep = hi ? hi_v : lo, send = hi ? lo : hi_v;
-  return keep + __shfl_xor(send, mask);
 }
 
 // acc (channels 0-3 of this lane's 8) / acc2 (channels 4-7) += w * (eight fp16 values of one 16-byte load)

@@ -37,7 +37,7 @@
 // with the channel sums reduced through LDS.
 #include <cstdlib>
 #include <string>
-#include "common.h"
+#include "gather_pieces.h"
 #include "msda_bwd_bins.h"
 
 namespace occ {
@@ -113,18 +113,8 @@ __global__ __launch_bounds__(256) void msda_bwd_d32_kernel(
         const float4 v1 = ok[u][0] ? v[u][0] : z4, v2 = ok[u][1] ? v[u][1] : z4;
         const float4 v3 = ok[u][2] ? v[u][2] : z4, v4 = ok[u][3] ? v[u][3] : z4;
         const float lh = lh_[u], lw = lw_[u], hh = 1.f - lh, hw = 1.f - lw, a = a_[u];
-        const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
-        const float tx[4] = {top.x, top.y, top.z, top.w};
-        const float a1[4] = {v1.x, v1.y, v1.z, v1.w}, a2[4] = {v2.x, v2.y, v2.z, v2.w};
-        const float a3[4] = {v3.x, v3.y, v3.z, v3.w}, a4[4] = {v4.x, v4.y, v4.z, v4.w};
         float g_attn = 0.f, g_x = 0.f, g_y = 0.f;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          const float ta = tx[k] * a;
-          g_attn += tx[k] * (w1 * a1[k] + w2 * a2[k] + w3 * a3[k] + w4 * a4[k]);
-          g_x += ta * (hh * (a2[k] - a1[k]) + lh * (a4[k] - a3[k]));
-          g_y += ta * (hw * (a3[k] - a1[k]) + lw * (a4[k] - a2[k]));
-        }
+        OCC_D32_CORNER_GRAD()   // the same sums as the scalar path below: gather_pieces.h
         g_x *= Wf[u];
         g_y *= Hf[u];
         g_attn = group8_sum(g_attn);
@@ -160,23 +150,12 @@ __global__ __launch_bounds__(256) void msda_bwd_d32_kernel(
       const float4 r3 = *reinterpret_cast<const float4*>(vb + (t.c[2] ? o3 : 0));
       const float4 r4 = *reinterpret_cast<const float4*>(vb + (t.c[3] ? o4 : 0));
       const float4 v1 = t.c[0] ? r1 : z4, v2 = t.c[1] ? r2 : z4, v3 = t.c[2] ? r3 : z4, v4 = t.c[3] ? r4 : z4;
-      const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
-      const float tx[4] = {top.x, top.y, top.z, top.w};
-      const float a1[4] = {v1.x, v1.y, v1.z, v1.w}, a2[4] = {v2.x, v2.y, v2.z, v2.w};
-      const float a3[4] = {v3.x, v3.y, v3.z, v3.w}, a4[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const float ta = tx[k] * a;
-        g_attn += tx[k] * (w1 * a1[k] + w2 * a2[k] + w3 * a3[k] + w4 * a4[k]);
-        g_x += ta * (hh * (a2[k] - a1[k]) + lh * (a4[k] - a3[k]));
-        g_y += ta * (hw * (a3[k] - a1[k]) + lw * (a4[k] - a2[k]));
-        if (VALUE_ATOMICS) {
-          if (t.c[0]) unsafeAtomicAdd(gvb + o1 + k, ta * w1);
-          if (t.c[1]) unsafeAtomicAdd(gvb + o2 + k, ta * w2);
-          if (t.c[2]) unsafeAtomicAdd(gvb + o3 + k, ta * w3);
-          if (t.c[3]) unsafeAtomicAdd(gvb + o4 + k, ta * w4);
-        }
-      }
+      OCC_D32_CORNER_GRAD(if (VALUE_ATOMICS) {
+        if (t.c[0]) unsafeAtomicAdd(gvb + o1 + k, ta * w1);
+        if (t.c[1]) unsafeAtomicAdd(gvb + o2 + k, ta * w2);
+        if (t.c[2]) unsafeAtomicAdd(gvb + o3 + k, ta * w3);
+        if (t.c[3]) unsafeAtomicAdd(gvb + o4 + k, ta * w4);
+      })
       g_x *= (float)W;
       g_y *= (float)H;
     }

@@ -40,7 +40,7 @@
 // the fine-level gather (~60), the 164 MB stream of query-Linear outputs and results (~42), the prologue and the per-camera
 // set-up.  Not pursued: the restructuring needs per-camera query lists, a partial-sum side buffer and 8 waves per CU.
 #include <cstdlib>
-#include "common.h"
+#include "gather_pieces.h"
 
 namespace occ {
 
@@ -82,10 +82,7 @@ __global__ __launch_bounds__(256, 3) void sca_fused_kernel(
 
   // ---- camera-independent part: softmax(logits) and offsets / (W_l, H_l) ------------------
   float aw[K], ox[K], oy[K];
-  // sample index s = (lane + 64 k) % LP does not depend on k (64 % LP == 0): one level per lane
-  static_assert(64 % LP == 0, "the lane's level must not depend on k");
-  const int lane_l = (lane % LP) / P;
-  const int lvH = (int)shapes[2 * lane_l], lvW = (int)shapes[2 * lane_l + 1], lvS = (int)lstart[lane_l];
+  OCC_SCA32_LEVEL   // the set-up map idx = lane + 64 k, shared with sca_bwd_sample_kernel (gather_pieces.h)
   const float* lrow = logits + ((long)b * Nq + q) * logits_stride;
   const float* orow = offs + ((long)b * Nq + q) * offs_stride;
 #pragma unroll
@@ -100,9 +97,7 @@ __global__ __launch_bounds__(256, 3) void sca_fused_kernel(
 #pragma unroll
     for (int d = LP / 2; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
     aw[k] = fdiv(e, sum);                      // (fdiv, not `/`: common.h)
-    const float2 o = *reinterpret_cast<const float2*>(orow + 2 * idx);
-    ox[k] = fdiv(o.x, (float)lvW);
-    oy[k] = fdiv(o.y, (float)lvH);
+    OCC_SCA32_OFFSET(k)
     pre[wave][0][k][lane] = aw[k];
     pre[wave][1][k][lane] = ox[k];
     pre[wave][2][k][lane] = oy[k];
@@ -117,10 +112,7 @@ __global__ __launch_bounds__(256, 3) void sca_fused_kernel(
     const float* rp = ref_cam + (((long)c * B + b) * Nq + q) * Z * 2;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const int idx = lane + 64 * k;
-      const int m = idx / LP, s = idx % LP;
-      const int z = (s % P) % Z;  // point p pairs with z-anchor p % Z (view(.., P//Z, Z, 2))
-      const float2 rxy = *reinterpret_cast<const float2*>(rp + 2 * z);
+      OCC_SCA32_ANCHOR(k)
       SampleParamB p;
       const float aw_k = pre[wave][0][k][lane], ox_k = pre[wave][1][k][lane], oy_k = pre[wave][2][k][lane];
       n_in += bilinear_setup_b(rxy.x + ox_k, rxy.y + oy_k, aw_k, lvH, lvW, lvS,
@@ -141,25 +133,19 @@ __global__ __launch_bounds__(256, 3) void sca_fused_kernel(
   float4 o4 = make_float4(fdiv(acc.x, inv), fdiv(acc.y, inv), fdiv(acc.z, inv), fdiv(acc.w, inv));
   *reinterpret_cast<float4*>(slots + ((long)b * Nq + q) * row_stride + g * D + c4 * 4) = o4;
 
-  if (stats) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n_in += __shfl_xor(n_in, d);
-    if (lane == 0) {
-      atomicAdd(&stats[0], (unsigned long long)n_rows);
-      atomicAdd(&stats[1], (unsigned long long)n_in);
-    }
-  }
+  OCC_SCA_STATS(0)
 }
 
+// (the three launchers share one signature, ScaLaunch below: fp32 rows have no value_scale)
 template <int L, int P>
-static int launch_sca(const float* value, const int64_t* shapes, const int64_t* lstart,
+static int launch_sca(const void* value, const int64_t* shapes, const int64_t* lstart,
                       const float* offs, long offs_stride, const float* logits, long logits_stride,
                       const float* ref_cam, const uint32_t* vis_bits, const int32_t* order,
                       float* slots, uint64_t* stats, int B, int NC, int S, int Z, int Nq,
-                      hipStream_t st) {
+                      hipStream_t st, const float* /*value_scale*/) {
   const long waves = (long)B * Nq;
   const long blocks = (waves + kScaWaves - 1) / kScaWaves;
-  hipLaunchKernelGGL((sca_fused_kernel<L, P>), dim3((unsigned)blocks), dim3(256), 0, st, value,
+  hipLaunchKernelGGL((sca_fused_kernel<L, P>), dim3((unsigned)blocks), dim3(256), 0, st, reinterpret_cast<const float*>(value),
                      shapes, lstart, offs, offs_stride, logits, logits_stride, ref_cam, vis_bits,
                      order, slots, reinterpret_cast<unsigned long long*>(stats), B, NC, S, Z, Nq);
   OCC_CHECK_LAUNCH("sca_fused_forward");
@@ -210,40 +196,7 @@ __global__ __launch_bounds__(256, WPS) void sca_fused_h_kernel(
   const int hm = lane >> 3, sK = lane & 7;
   const int lane_l = (sK * K) / P;
   const int lvH = (int)shapes[2 * lane_l], lvW = (int)shapes[2 * lane_l + 1], lvS = (int)lstart[lane_l];
-  {
-    const float* lp = logits + ((long)b * Nq + q) * logits_stride + hm * LP + sK * K;
-    const float* op = offs + ((long)b * Nq + q) * offs_stride + 2 * (hm * LP + sK * K);
-    float x[K], o[2 * K];
-    if constexpr (K == 4) {
-      const float4 t = *reinterpret_cast<const float4*>(lp);
-      x[0] = t.x; x[1] = t.y; x[2] = t.z; x[3] = t.w;
-      const float4 u0 = *reinterpret_cast<const float4*>(op), u1 = *reinterpret_cast<const float4*>(op + 4);
-      o[0] = u0.x; o[1] = u0.y; o[2] = u0.z; o[3] = u0.w; o[4] = u1.x; o[5] = u1.y; o[6] = u1.z; o[7] = u1.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        x[k] = lp[k];
-        const float2 t = *reinterpret_cast<const float2*>(op + 2 * k);
-        o[2 * k] = t.x; o[2 * k + 1] = t.y;
-      }
-    }
-    float mx = x[0];
-#pragma unroll
-    for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { x[k] = expf(x[k] - mx); sum += x[k]; }
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      aw[k] = fdiv(x[k], sum);                 // (fdiv, not `/`: see common.h)
-      ox[k] = fdiv(o[2 * k], (float)lvW);
-      oy[k] = fdiv(o[2 * k + 1], (float)lvH);
-    }
-  }
+  OCC_SCA16_PROLOGUE(hm)
 
   // gather map: 4 lanes x 8 channels per head row, the two halves of the wave take the two halves of a head's samples
   const int g = (lane >> 2) & 7, c4 = lane & 3, half = lane >> 5;
@@ -256,28 +209,8 @@ __global__ __launch_bounds__(256, WPS) void sca_fused_h_kernel(
     // the K anchor points of this lane are requested together: inside the loop below each one sat behind the branches of
     // the previous sample's set-up — K serial round trips per (query, camera) (round 4 ISA reading)
     float2 rxy_k[K];
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int z = ((sK * K + k) % P) % Z;  // point p pairs with z-anchor p % Z (view(.., P//Z, Z, 2))
-      rxy_k[k] = *reinterpret_cast<const float2*>(rp + 2 * z);
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      const int m = hm;
-      const float2 rxy = rxy_k[k];
-      SampleParamB p;
-      const float aw_k = aw[k], ox_k = ox[k], oy_k = oy[k];
-      n_in += bilinear_setup_b(rxy.x + ox_k, rxy.y + oy_k, aw_k, lvH, lvW, lvS,
-                               (unsigned)row_stride * EV, kOobOffset, 1, p);
-      // pixel-pair layout (file header): byte offset pix * 512 -> (pix >> 1) * 1024 + (pix & 1) * 64; the out-of-range
-      // marker stays out of range
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) p.o[kk] = (p.o[kk] & ~1023u) | ((p.o[kk] >> 3) & 64u);
-      // slot k * 8 + sK, not s: the 8 lanes of a head write consecutive 32-byte entries (conflict-free); the gather
-      // sums a head's LP entries, so their order in the slab is free
-      sp[m * LPp + k * 8 + sK] = p;
-    }
+    OCC_SCA16_ANCHORS
+    OCC_SCA16_RESOLVE(hm * LPp, 1)   // pixel-pair layout, slab slot: gather_pieces.h
     wave_lds_sync();
     // corners outside their map carry an out-of-range byte offset: the buffer load returns 0 without a request
     // (round 1 issued a dummy load of row 0 for them: 9 % of the rows through the texture path, and 0 * Inf)
@@ -288,29 +221,10 @@ __global__ __launch_bounds__(256, WPS) void sca_fused_h_kernel(
     ++n_rows;
   }
 
-  // value_scale: the power-of-two range scale s the projection stored the fp16 rows with (value_range.hip); dividing by
-  // count * s undoes it exactly
-  // (q16 rows: the mantissas additionally carry 2^15 / 2 — stored under s / 2 —, common.h fma8q)
-  const float inv = (float)(count > 0 ? count : 1) * (value_scale != nullptr ? *value_scale : 1.f) * (Q ? 16384.f : 1.f);
-  // the two sample halves of a head sit 32 lanes apart
-  acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32);
-  acc.w += __shfl_xor(acc.w, 32);
-  acc2.x += __shfl_xor(acc2.x, 32); acc2.y += __shfl_xor(acc2.y, 32); acc2.z += __shfl_xor(acc2.z, 32);
-  acc2.w += __shfl_xor(acc2.w, 32);
-  if (half == 0) {
-    float* dst = slots + ((long)b * Nq + q) * row_stride + g * D + c4 * 8;
-    *reinterpret_cast<float4*>(dst) = make_float4(fdiv(acc.x, inv), fdiv(acc.y, inv), fdiv(acc.z, inv), fdiv(acc.w, inv));
-    *reinterpret_cast<float4*>(dst + 4) = make_float4(fdiv(acc2.x, inv), fdiv(acc2.y, inv), fdiv(acc2.z, inv), fdiv(acc2.w, inv));
-  }
+  // scale by 1 / (count * value_scale), merge the two sample halves, store: gather_pieces.h
+  OCC_SCA16_EPILOGUE(half == 0, slots + ((long)b * Nq + q) * row_stride + g * D + c4 * 8)
 
-  if (stats) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) n_in += __shfl_xor(n_in, d);
-    if (lane == 0) {
-      atomicAdd(&stats[0], (unsigned long long)n_rows);
-      atomicAdd(&stats[1], (unsigned long long)n_in);
-    }
-  }
+  OCC_SCA_STATS(0)
 }
 
 // ---- head-major variant (round 6) --------------------------------------------------------------------------------------------
@@ -374,40 +288,7 @@ __global__ __launch_bounds__(64 * WB, WPS * 4 / WB) void sca_fused_hm_kernel(
     const int hl = (int)shapes[2 * l], wl = (int)shapes[2 * l + 1], sl = (int)lstart[l];
     lvH = lane_l == l ? hl : lvH; lvW = lane_l == l ? wl : lvW; lvS = lane_l == l ? sl : lvS;
   }
-  {
-    const float* lp = logits + ((long)b * Nq + q) * logits_stride + m * LP + sK * K;
-    const float* op = offs + ((long)b * Nq + q) * offs_stride + 2 * (m * LP + sK * K);
-    float x[K], o[2 * K];
-    if constexpr (K == 4) {
-      const float4 tt = *reinterpret_cast<const float4*>(lp);
-      x[0] = tt.x; x[1] = tt.y; x[2] = tt.z; x[3] = tt.w;
-      const float4 u0 = *reinterpret_cast<const float4*>(op), u1 = *reinterpret_cast<const float4*>(op + 4);
-      o[0] = u0.x; o[1] = u0.y; o[2] = u0.z; o[3] = u0.w; o[4] = u1.x; o[5] = u1.y; o[6] = u1.z; o[7] = u1.w;
-    } else {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        x[k] = lp[k];
-        const float2 tt = *reinterpret_cast<const float2*>(op + 2 * k);
-        o[2 * k] = tt.x; o[2 * k + 1] = tt.y;
-      }
-    }
-    float mx = x[0];
-#pragma unroll
-    for (int k = 1; k < K; ++k) mx = fmaxf(mx, x[k]);
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) mx = fmaxf(mx, __shfl_xor(mx, d));
-    float sum = 0.f;
-#pragma unroll
-    for (int k = 0; k < K; ++k) { x[k] = expf(x[k] - mx); sum += x[k]; }
-#pragma unroll
-    for (int d = 4; d >= 1; d >>= 1) sum += __shfl_xor(sum, d);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      aw[k] = fdiv(x[k], sum);
-      ox[k] = fdiv(o[2 * k], (float)lvW);
-      oy[k] = fdiv(o[2 * k + 1], (float)lvH);
-    }
-  }
+  OCC_SCA16_PROLOGUE(m)
 
   // ---- gather mapping: lane = (query slot g, 16-byte piece c4, sample half) ------------------------------------------------
   const int g = (lane >> 2) & 7, c4 = lane & 3, half = lane >> 5;
@@ -431,22 +312,9 @@ __global__ __launch_bounds__(64 * WB, WPS * 4 / WB) void sca_fused_hm_kernel(
       rxy_k[0] = make_float2(t0.x, t0.y); rxy_k[1] = make_float2(t0.z, t0.w);
       rxy_k[2 % K] = make_float2(t1.x, t1.y); rxy_k[3 % K] = make_float2(t1.z, t1.w);
     } else {
-#pragma unroll
-      for (int k = 0; k < K; ++k) {
-        const int z = ((sK * K + k) % P) % Z;  // point p pairs with z-anchor p % Z (view(.., P//Z, Z, 2))
-        rxy_k[k] = *reinterpret_cast<const float2*>(rp + 2 * z);
-      }
+      OCC_SCA16_ANCHORS
     }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-      SampleParamB p;
-      n_in += bilinear_setup_b(rxy_k[k].x + ox[k], rxy_k[k].y + oy[k], aw[k], lvH, lvW, lvS,
-                               (unsigned)row_stride * EV, kOobOffset, live, p);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) p.o[kk] = (p.o[kk] & ~1023u) | ((p.o[kk] >> 3) & 64u);     // pixel-pair layout
-      sp[j * LPp + k * 8 + sK] = p;
-    }
+    OCC_SCA16_RESOLVE(j * LPp, live)
     wave_lds_sync();
     const __amdgpu_buffer_rsrc_t rsrc =
         uniform_rsrc(value + ((long)b * NC + c) * S * row_stride * EV, (unsigned)S * row_stride * EV);
@@ -455,25 +323,9 @@ __global__ __launch_bounds__(64 * WB, WPS * 4 / WB) void sca_fused_hm_kernel(
     n_rows += (unsigned)(live & (sK == 0) & (m == 0));
   }
 
-  const float inv = (float)(count > 0 ? count : 1) * (value_scale != nullptr ? *value_scale : 1.f) * (Q ? 16384.f : 1.f);
-  acc.x += __shfl_xor(acc.x, 32); acc.y += __shfl_xor(acc.y, 32); acc.z += __shfl_xor(acc.z, 32);
-  acc.w += __shfl_xor(acc.w, 32);
-  acc2.x += __shfl_xor(acc2.x, 32); acc2.y += __shfl_xor(acc2.y, 32); acc2.z += __shfl_xor(acc2.z, 32);
-  acc2.w += __shfl_xor(acc2.w, 32);
-  if (half == 0 && gvalid) {
-    float* dst = slots + ((long)b * Nq + qg) * row_stride + m * D + c4 * 8;
-    *reinterpret_cast<float4*>(dst) = make_float4(fdiv(acc.x, inv), fdiv(acc.y, inv), fdiv(acc.z, inv), fdiv(acc.w, inv));
-    *reinterpret_cast<float4*>(dst + 4) = make_float4(fdiv(acc2.x, inv), fdiv(acc2.y, inv), fdiv(acc2.z, inv), fdiv(acc2.w, inv));
-  }
+  OCC_SCA16_EPILOGUE(half == 0 && gvalid, slots + ((long)b * Nq + qg) * row_stride + m * D + c4 * 8)
 
-  if (stats) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) { n_in += __shfl_xor(n_in, d); n_rows += __shfl_xor(n_rows, d); }
-    if (lane == 0) {
-      if (n_rows) atomicAdd(&stats[0], (unsigned long long)n_rows);
-      atomicAdd(&stats[1], (unsigned long long)n_in);
-    }
-  }
+  OCC_SCA_STATS(1)   // n_rows was counted per lane here
 }
 
 template <int L, int P, bool Q, int WPS = 4, int DEPTH = 2, int WB = kScaWaves>
@@ -557,35 +409,25 @@ static int sca_dispatch(const void* value, int rowfmt /* 0 f32, 1 f16, 2 q16 */,
   // profiles/r06_c9_sca_head_major_sweep.txt); OCC_SCA_HEAD_MAJOR=0 selects the query-major kernel (read per call: tests
   // switch it inside one process).  (waves / SIMD, window, waves / block) = (4, 2, 4) measured best of (3, 4, 4) 0.2047,
   // (4, 2, 8) 0.2051, (4, 1, 4) 0.2044 ms.  (`head_major` is read above, where the alignment checks need it.)
-#define OCC_SCA_CASE(LL, PP)                                                                       \
-  if (L == LL && P == PP) {                                                                        \
-    if (rowfmt == 2 && head_major)                                                                 \
-      return launch_sca_hm<LL, PP, true>(value, spatial_shapes, level_start_index, offs, (long)offs_stride, logits, \
-                                         (long)logits_stride, ref_cam, vis_bits, order, slots, stats, B, NC, S, Z, Nq, st, \
-                                         value_scale);                                                           \
-    if (rowfmt == 1 && head_major)                                                                 \
-      return launch_sca_hm<LL, PP, false>(value, spatial_shapes, level_start_index, offs, (long)offs_stride, logits, \
-                                          (long)logits_stride, ref_cam, vis_bits, order, slots, stats, B, NC, S, Z, Nq, st, \
-                                          value_scale);                                                          \
-    if (rowfmt == 2)                                                                               \
-      return launch_sca_h<LL, PP, true>(value, spatial_shapes, level_start_index, offs, (long)offs_stride, logits, \
-                                        (long)logits_stride, ref_cam, vis_bits, order, slots, stats, B, NC, S, Z, Nq, st, \
-                                        value_scale);                                                            \
-    if (rowfmt == 1)                                                                               \
-      return launch_sca_h<LL, PP, false>(value, spatial_shapes, level_start_index, offs, (long)offs_stride, logits, \
-                                         (long)logits_stride, ref_cam, vis_bits, order, slots, stats, B, NC, S, Z, Nq, st, \
-                                         value_scale);                                                           \
-    return launch_sca<LL, PP>(reinterpret_cast<const float*>(value), spatial_shapes, level_start_index, offs,    \
-                              (long)offs_stride, logits, (long)logits_stride, ref_cam, vis_bits, order, slots,   \
-                              stats, B, NC, S, Z, Nq, st);                                                       \
-  }
+  using ScaLaunch = int (*)(const void*, const int64_t*, const int64_t*, const float*, long, const float*, long, const float*,
+                           const uint32_t*, const int32_t*, float*, uint64_t*, int, int, int, int, int, hipStream_t, const float*);
+  ScaLaunch launch = nullptr;
+#define OCC_SCA_CASE(LL, PP)                                                                                     \
+  if (L == LL && P == PP)                                                                                        \
+    launch = rowfmt == 0  ? launch_sca<LL, PP>                                                                   \
+             : head_major ? (rowfmt == 2 ? launch_sca_hm<LL, PP, true> : launch_sca_hm<LL, PP, false>)           \
+                          : (rowfmt == 2 ? launch_sca_h<LL, PP, true> : launch_sca_h<LL, PP, false>);
   OCC_SCA_CASE(4, 8)
   OCC_SCA_CASE(4, 4)
   OCC_SCA_CASE(2, 8)
   OCC_SCA_CASE(1, 8)
 #undef OCC_SCA_CASE
-  set_error("sca_fused_forward: no fused kernel for L=%d P=%d", L, P);
-  return OCC_E_UNSUPPORTED;
+  if (launch == nullptr) {
+    set_error("sca_fused_forward: no fused kernel for L=%d P=%d", L, P);
+    return OCC_E_UNSUPPORTED;
+  }
+  return launch(value, spatial_shapes, level_start_index, offs, (long)offs_stride, logits, (long)logits_stride, ref_cam,
+                vis_bits, order, slots, stats, B, NC, S, Z, Nq, st, value_scale);
 }
 }  // namespace occ
 

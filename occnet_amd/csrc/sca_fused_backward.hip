@@ -13,7 +13,7 @@
 //   grad_value[b * NC + c][corner k][m] += top * a_s * w_k                       (in-range corners)
 //
 // grad_offs / grad_logits: sca_bwd_sample_kernel, one 64-lane wave per (b, q) like the forward.  Per visible camera the wave
-// resolves the head's samples into LDS (set-up map: lane + 64 k = m * LP + s, the fp32 forward's), then every 8-lane group
+// resolves the head's samples into LDS (set-up map: lane + 64 k = m * LP + s, the fp32 forward's: gather_pieces.h), then every 8-lane group
 // (one head, 4 channels per lane) reads its head's samples 8 at a time, takes the dot products of the grad row with the four
 // corner rows, and folds the 8 lanes' partial sums of those 8 samples by a REDUCE-SCATTER (xor 4, 2, 1: 21 shuffles for 24
 // values) that leaves lane c4 of the group with sample 8 j + c4 — summed over the cameras in registers.  The softmax, the 1 / count
@@ -27,14 +27,14 @@
 // atomics outside the few split bins of the default mode; OCC_MSDA_BWD_DETERMINISTIC=1 takes the order-independent fixed-point
 // replay, so grad_value is bit-identical run to run as well.
 #include <cstdlib>
-#include "common.h"
+#include "gather_pieces.h"
 #include "msda_bwd_bins.h"
 
 namespace occ {
 
 constexpr int kScaBwdWaves = 4;
 
-// BwdSampleParam, dot4, rs_step: common.h (shared with tsa_fused_backward.hip)
+// BwdSampleParam, the sample builder, the 8-sample gradient chunk: gather_pieces.h (shared with tsa_fused_backward.hip)
 
 template <int L, int P>
 __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
@@ -47,7 +47,6 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
   constexpr int K = M * LP / 64;       // samples resolved per lane (set-up map)
   constexpr int J = LP / 8;            // samples per lane at the end (gradient map)
   static_assert(LP >= 8 && LP <= 32 && (LP & (LP - 1)) == 0, "L*P must be a power of two in [8,32]");
-  static_assert(64 % LP == 0, "the lane's level must not depend on k");
   constexpr int LPp = LP + 1;
   __shared__ BwdSampleParam smem[kScaBwdWaves * M * LPp];
 
@@ -65,16 +64,13 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
   const float inv = (float)(own != 0u ? __builtin_popcount(own) : 1);
 
   // ---- set-up map: normalised offsets of the lane's K samples (idx = lane + 64 k = m * LP + s) ---------------------------
-  const int lane_l = (lane % LP) / P;
-  const int lvH = (int)shapes[2 * lane_l], lvW = (int)shapes[2 * lane_l + 1], lvS = (int)lstart[lane_l];
+  OCC_SCA32_LEVEL
   float ox[K], oy[K];
   const float* orow = offs + bq * offs_stride;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     const int idx = lane + 64 * k;
-    const float2 o = *reinterpret_cast<const float2*>(orow + 2 * idx);
-    ox[k] = fdiv(o.x, (float)lvW);
-    oy[k] = fdiv(o.y, (float)lvH);
+    OCC_SCA32_OFFSET(k)
     *reinterpret_cast<float2*>(pre_oxy + (bq * M * LP + idx) * 2) = make_float2(ox[k], oy[k]);
   }
 
@@ -92,21 +88,9 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
     const float* rp = ref_cam + (((long)c * B + b) * Nq + q) * Z * 2;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
-      const int idx = lane + 64 * k;
-      const int m = idx / LP, s = idx % LP;
-      const int z = (s % P) % Z;       // point p pairs with z-anchor p % Z
-      const float2 rxy = *reinterpret_cast<const float2*>(rp + 2 * z);
+      OCC_SCA32_ANCHOR(k)
       const BilinearTerms t = bilinear_terms(rxy.x + ox[k], rxy.y + oy[k], lvH, lvW, 1);
-      const unsigned base = (unsigned)(lvS + t.h_low * lvW + t.w_low);
-      BwdSampleParam p;
-      p.o[0] = t.c[0] ? base * (unsigned)row_stride * 4u : kOobOffset;
-      p.o[1] = t.c[1] ? (base + 1u) * (unsigned)row_stride * 4u : kOobOffset;
-      p.o[2] = t.c[2] ? (base + (unsigned)lvW) * (unsigned)row_stride * 4u : kOobOffset;
-      p.o[3] = t.c[3] ? (base + (unsigned)lvW + 1u) * (unsigned)row_stride * 4u : kOobOffset;
-      p.lh = t.adm ? t.lh : 0.f;       // a sample outside its map: 0, not 0 * NaN
-      p.lw = t.adm ? t.lw : 0.f;
-      p.pad0 = p.pad1 = 0.f;
-      sp[m * LPp + s] = p;
+      sp[m * LPp + s] = bwd_sample_param(t, lvS, lvW, row_stride);
     }
     wave_lds_sync();
     const __amdgpu_buffer_rsrc_t rsrc =
@@ -115,39 +99,9 @@ __global__ __launch_bounds__(64 * kScaBwdWaves) void sca_bwd_sample_kernel(
     // and spills); the chunk's result is added to its accumulator by selects
 #pragma unroll 1
     for (int j = 0; j < J; ++j) {
-      float v[8][3];
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {    // two groups of 4 samples: 16 corner loads in flight
-        float4 r[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const occ_u32x4 o = *reinterpret_cast<const occ_u32x4*>(sp[g * LPp + 8 * j + 4 * h + u].o);
-#pragma unroll
-          for (int kk = 0; kk < 4; ++kk) r[u][kk] = buf_load16(rsrc, o[kk] + lane_off);
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const BwdSampleParam& pp = sp[g * LPp + 8 * j + 4 * h + u];
-          const float lh = pp.lh, lw = pp.lw, hh = 1.f - lh, hw = 1.f - lw;
-          const float d1 = dot4(top, r[u][0]), d2 = dot4(top, r[u][1]), d3 = dot4(top, r[u][2]), d4 = dot4(top, r[u][3]);
-          v[4 * h + u][0] = hh * hw * d1 + hh * lw * d2 + lh * hw * d3 + lh * lw * d4;
-          v[4 * h + u][1] = hh * (d2 - d1) + lh * (d4 - d3);
-          v[4 * h + u][2] = hw * (d3 - d1) + lw * (d4 - d2);
-        }
-      }
-      // reduce-scatter over the group's 8 lanes: lane c4 ends with the channel sums of sample 8 j + c4
-      float r1[4][3], r2[2][3];
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int e = 0; e < 3; ++e) r1[u][e] = rs_step(v[u][e], v[4 + u][e], b2, 4);
-#pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int e = 0; e < 3; ++e) r2[u][e] = rs_step(r1[u][e], r1[2 + u][e], b1, 2);
-      const float rA = rs_step(r2[0][0], r2[1][0], b0, 1);
-      const float rX = rs_step(r2[0][1], r2[1][1], b0, 1);
-      const float rY = rs_step(r2[0][2], r2[1][2], b0, 1);
+      // two groups of 4 samples (16 corner loads in flight), then the reduce-scatter: lane c4 ends with the channel sums of
+      // sample 8 j + c4
+      OCC_BWD_GRAD_CHUNK8(g * LPp + 8 * j, rsrc, rA, rX, rY)
 #pragma unroll
       for (int jj = 0; jj < J; ++jj) {
         if (jj == j) { accA[jj] += rA; accX[jj] += rX; accY[jj] += rY; }

@@ -13,7 +13,7 @@
 // (Round 6 measured what 16-bit value rows would buy here — a 4-lanes-per-row variant of this kernel on garbage data, timing only:
 // 53.4 -> 41.3 us per launch with the q16 decode, profiles/r06_c12_tsa_16bit_rows_timing.txt — against the q16 encoder it would need
 // in the chain kernels' tail epilogues (program B sits at 256 VGPRs): not built.)
-#include "common.h"
+#include "gather_pieces.h"
 
 namespace occ {
 
@@ -37,24 +37,14 @@ __global__ __launch_bounds__(256) void tsa_fused_kernel(
   SampleParamB* sp = smem + wave * M * NSp;
   constexpr int row_stride = M * D;
 
-  // lane = m*8 + t*4 + p : exactly the memory order of both Linear outputs
+  // lane = m*8 + t*4 + p : exactly the memory order of both Linear outputs (set-up shared with the backward: gather_pieces.h)
   const int m = lane >> 3, t = (lane >> 2) & 1;
-  const float x = logits[((long)b * Nq + q) * logits_stride + lane];
-  float mx = fmaxf(x, __shfl_xor(x, 1));
-  mx = fmaxf(mx, __shfl_xor(mx, 2));
-  const float e = expf(x - mx);
-  float sum = e + __shfl_xor(e, 1);
-  sum += __shfl_xor(sum, 2);
-  const float aw = fdiv(e, sum);                 // (fdiv, not `/`: see common.h)
-  float2 o = *reinterpret_cast<const float2*>(offs + ((long)b * Nq + q) * offs_stride + 2 * lane);
-  o.x = fdiv(o.x, (float)bev_w);
-  o.y = fdiv(o.y, (float)bev_h);
-  const float2 rf = *reinterpret_cast<const float2*>(ref_2d + (((long)b * 2 + t) * Nq + q) * 2);
+  float aw, lx, ly;
+  tsa_lane_setup(logits, logits_stride, offs, offs_stride, ref_2d, (long)b * Nq + q, lane, b, t, q, Nq, bev_h, bev_w, aw, lx, ly);
   // corners outside the BEV map carry an out-of-range byte offset: the buffer load returns 0 without a request (no
   // dummy load of row 0, no 0 * Inf)
   SampleParamB p;
-  bilinear_setup_b(rf.x + o.x, rf.y + o.y, aw, bev_h, bev_w, 0,
-                   (unsigned)row_stride * 4u, kOobOffset, 1, p);
+  bilinear_setup_b(lx, ly, aw, bev_h, bev_w, 0, (unsigned)row_stride * 4u, kOobOffset, 1, p);
   sp[m * NSp + (lane & 7)] = p;
   wave_lds_sync();
 

@@ -18,7 +18,7 @@
 // lane = m*8 + t*4 + p owns one sample (softmax = 4-lane shuffle), its corner offsets and fractional weights go to LDS.  Then
 // every 8-lane group (one head, 4 channels per lane) walks its head's 8 samples — samples 0-3 in queue entry 0's map, 4-7 in
 // entry 1's — takes the dot products of the grad row with the four corner rows and folds the 8 lanes' 3 x 8 partial sums by the
-// reduce-scatter shared with sca_fused_backward.hip (common.h rs_step; xor 4, 2, 1), which leaves lane c4 of the group with
+// reduce-scatter shared with sca_fused_backward.hip (gather_pieces.h; xor 4, 2, 1), which leaves lane c4 of the group with
 // sample c4 = t*4 + p: the lane that owns that sample's logit and offset pair.  One writer per element, fixed order of every sum: bit-reproducible.
 // `order` of the forward only steers locality and is ignored here.
 //
@@ -40,7 +40,7 @@
 // grad_logits alone, 24 and no LDS for the grad_value planes alone), 0 AGPRs, no scratch, 9216 bytes of LDS per 256-thread
 // block, 4 waves per SIMD.
 #include <cstdlib>
-#include "common.h"
+#include "gather_pieces.h"
 #include "msda_bwd_bins.h"
 
 namespace occ {
@@ -70,18 +70,8 @@ __global__ __launch_bounds__(64 * kTsaBwdWaves) void tsa_bwd_sample_kernel(
 
   // ---- set-up map: lane = m*8 + t*4 + p, the memory order of both Linear outputs ------------------------------------------
   const int m = lane >> 3, t = (lane >> 2) & 1, p = lane & 3;
-  const float x = logits[bq * logits_stride + lane];
-  float mx = fmaxf(x, __shfl_xor(x, 1));
-  mx = fmaxf(mx, __shfl_xor(mx, 2));
-  const float e = expf(x - mx);
-  float sum = e + __shfl_xor(e, 1);
-  sum += __shfl_xor(sum, 2);
-  const float aw = fdiv(e, sum);
-  float2 o = *reinterpret_cast<const float2*>(offs + bq * offs_stride + 2 * lane);
-  o.x = fdiv(o.x, (float)bev_w);
-  o.y = fdiv(o.y, (float)bev_h);
-  const float2 rf = *reinterpret_cast<const float2*>(ref_2d + (((long)b * 2 + t) * Nq + q) * 2);
-  const float lx = rf.x + o.x, ly = rf.y + o.y;
+  float aw, lx, ly;
+  tsa_lane_setup(logits, logits_stride, offs, offs_stride, ref_2d, bq, lane, b, t, q, Nq, bev_h, bev_w, aw, lx, ly);
   const int finite = lane_flag(fabsf(lx) < __builtin_huge_valf()) & lane_flag(fabsf(ly) < __builtin_huge_valf());
   if (WANT_V) {
     const long item = (((long)b * 2 + t) * Nq + q) * M + m;       // (b*2+t, q, m): ms_deform_attn order, L = 1
@@ -92,16 +82,7 @@ __global__ __launch_bounds__(64 * kTsaBwdWaves) void tsa_bwd_sample_kernel(
   if (!WANT_Q) return;
 
   const BilinearTerms bt = bilinear_terms(lx, ly, bev_h, bev_w, finite);
-  const unsigned base = (unsigned)(bt.h_low * bev_w + bt.w_low);
-  BwdSampleParam prm;
-  prm.o[0] = bt.c[0] ? base * (unsigned)row_stride * 4u : kOobOffset;
-  prm.o[1] = bt.c[1] ? (base + 1u) * (unsigned)row_stride * 4u : kOobOffset;
-  prm.o[2] = bt.c[2] ? (base + (unsigned)bev_w) * (unsigned)row_stride * 4u : kOobOffset;
-  prm.o[3] = bt.c[3] ? (base + (unsigned)bev_w + 1u) * (unsigned)row_stride * 4u : kOobOffset;
-  prm.lh = bt.adm ? bt.lh : 0.f;         // a sample outside the map (or dead): 0, not 0 * NaN
-  prm.lw = bt.adm ? bt.lw : 0.f;
-  prm.pad0 = prm.pad1 = 0.f;
-  sp[m * NSp + (lane & 7)] = prm;
+  sp[m * NSp + (lane & 7)] = bwd_sample_param(bt, 0, bev_w, row_stride);
   wave_lds_sync();
 
   // ---- gradient map: lane = (head g, channel piece c4); ends with sample c4 = t*4 + p of head g ---------------------------
@@ -111,41 +92,8 @@ __global__ __launch_bounds__(64 * kTsaBwdWaves) void tsa_bwd_sample_kernel(
   top.x *= 0.5f; top.y *= 0.5f; top.z *= 0.5f; top.w *= 0.5f;
   const unsigned lane_off = (unsigned)(g * D + c4 * 4) * 4u;
   const unsigned map_bytes = (unsigned)bev_h * (unsigned)bev_w * (unsigned)row_stride * 4u;
-  float v[8][3];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {          // queue entry h holds samples 4 h .. 4 h + 3: 16 corner loads in flight
-    const __amdgpu_buffer_rsrc_t rsrc = uniform_rsrc(value + ((long)b * 2 + h) * value_bt_stride, map_bytes);
-    float4 r[4][4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const occ_u32x4 oo = *reinterpret_cast<const occ_u32x4*>(sp[g * NSp + 4 * h + u].o);
-#pragma unroll
-      for (int kk = 0; kk < 4; ++kk) r[u][kk] = buf_load16(rsrc, oo[kk] + lane_off);
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const BwdSampleParam& pp = sp[g * NSp + 4 * h + u];
-      const float lh = pp.lh, lw = pp.lw, hh = 1.f - lh, hw = 1.f - lw;
-      const float d1 = dot4(top, r[u][0]), d2 = dot4(top, r[u][1]), d3 = dot4(top, r[u][2]),
-                  d4 = dot4(top, r[u][3]);
-      v[4 * h + u][0] = hh * hw * d1 + hh * lw * d2 + lh * hw * d3 + lh * lw * d4;
-      v[4 * h + u][1] = hh * (d2 - d1) + lh * (d4 - d3);
-      v[4 * h + u][2] = hw * (d3 - d1) + lw * (d4 - d2);
-    }
-  }
-  // reduce-scatter over the group's 8 lanes: lane c4 ends with the channel sums of sample c4
-  float r1[4][3], r2[2][3];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r1[u][k] = rs_step(v[u][k], v[4 + u][k], b2, 4);
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r2[u][k] = rs_step(r1[u][k], r1[2 + u][k], b1, 2);
-  const float dA = rs_step(r2[0][0], r2[1][0], b0, 1);
-  const float gX = rs_step(r2[0][1], r2[1][1], b0, 1);
-  const float gY = rs_step(r2[0][2], r2[1][2], b0, 1);
+  // queue entry h holds samples 4 h .. 4 h + 3; the reduce-scatter leaves lane c4 with the channel sums of sample c4
+  OCC_BWD_GRAD_CHUNK8(g * NSp, uniform_rsrc(value + ((long)b * 2 + h) * value_bt_stride, map_bytes), dA, gX, gY)
 
   // ---- softmax backward over the sample's 4-lane group (lane g*8 + c4 = m*8 + t*4 + p: `aw` is this sample's) -------------
   float dot = aw * dA;
