@@ -21,6 +21,8 @@
  *        padded rebatch + the softmax / normalisation / rebatch / camera-mean gradients) for fp32 value rows
  *   occ_tsa_fused_forward_f32        <- TemporalSelfAttention.forward :206-262 (softmax, locations,
  *        gather, mean over the 2-deep BEV queue), P/bevformer/modules/temporal_self_attention.py
+ *   occ_tsa_fused_forward_q16v       <- the same lines over q16 value rows; occ_linear_bf16x3_q16rows <- self.value_proj
+ *        (:198) writing them
  *   occ_conv3d_pack_weight_f32, occ_conv3d_bn_relu_f32 <- TransformerOcc.forward lifter view +
  *        decoder ConvModule(Conv3d k3 + BN3d + ReLU) x2 + permute, P/bevformer/modules/transformer_occ.py
  *        :305-308 (modules :106-126)
@@ -247,6 +249,20 @@ int occ_tsa_fused_forward_f32(const float* value, int64_t value_bt_stride, const
                               int64_t offs_stride, const float* logits, int64_t logits_stride,
                               const float* ref_2d, const int32_t* order, float* out, int B, int Nq,
                               int bev_h, int bev_w, int M, int D, int P, void* stream);
+/* The same gather over q16 VALUE maps (opt-in: OCC_TSA_VALUES=q16): block floating point as for occ_sca_fused_forward_q16v,
+ * in the pixel-pair layout occ_sca_rows_encode_q16 / occ_linear_bf16x3_q16rows write — queue entry t of batch b at
+ * value_q16 + (b*2+t)*value_bt_stride int16 elements, each [pix >> 1][head][pix & 1][32] with pix = y*bev_w + x and
+ * value_rows = bev_h*bev_w rounded up to even rows (the pad row of an odd map is never sampled).  value_bt_stride is 0 (both
+ * entries alias one map) or at least one padded map (value_rows*M*D), and a multiple of 8.  value_scale: NULL (= 1) or one
+ * DEVICE float s, the power-of-two range scale the rows were encoded with (stored under s / 2); the kernel divides
+ * 2^15 * s / 2 out together with the queue mean, so the result depends on s only through the encoder's rounding.  offs, logits,
+ * ref_2d, order, out, the alignment rules and the M=8, D=32, P=4 restriction (OCC_E_UNSUPPORTED) are those of
+ * occ_tsa_fused_forward_f32; softmax, sampling arithmetic and accumulation are fp32.  One buffer descriptor spans both maps of a
+ * batch entry: (value_bt_stride + value_rows*M*D) * 2 bytes must stay below 2^31 - 1280 (OCC_E_INVALID). */
+int occ_tsa_fused_forward_q16v(const void* value_q16, int64_t value_bt_stride, int value_rows, const float* offs,
+                               int64_t offs_stride, const float* logits, int64_t logits_stride,
+                               const float* ref_2d, const int32_t* order, float* out, int B, int Nq,
+                               int bev_h, int bev_w, int M, int D, int P, const float* value_scale, void* stream);
 /* Backward of occ_tsa_fused_forward_f32 (same geometry and arguments; Nq = bev_h*bev_w: no query bands; `order` only steers
  * locality and has no counterpart here).  grad_out (B, Nq, M*D) f32 is the gradient of `out`.  spatial_shapes = {bev_h, bev_w}
  * and level_start_index = {0} as int64 in DEVICE memory (the grad_value replay reads them).  Outputs:
@@ -381,6 +397,16 @@ int occ_linear_bf16x3_f32(const float* a1, int64_t lda1, int K1, const float* a2
                           const float* residual, int64_t ldres, const float* ln_gamma,
                           const float* ln_beta, float ln_eps, float* out, int64_t ldo, int M, int N,
                           void* stream);
+/* The plain Linear out = a.W^T + bias of occ_linear_bf16x3_f32 (same kernel, same tile choice: the SAME fp32 values) stored
+ * as q16 value rows for occ_tsa_fused_forward_q16v instead of fp32: the M rows are `groups` maps of S = M / groups rows
+ * (M % groups == 0), row r of map g goes to the pixel-pair position
+ *     out[(g*S_pad + (r & ~1))*256 + (n/32)*64 + (r & 1)*32 + n%32]     (int16, S_pad = S + (S & 1); pad rows are not written)
+ * with one exponent per 16-byte piece of 8 channels, exactly what occ_sca_rows_encode_q16 makes of the fp32 result — without
+ * the pass over it.  a (M, K) f32 with row stride lda; scale: NULL (= 1) or one DEVICE float s, a power of two with
+ * max|out| * s <= 2^15.  Covers N == 256 and K % 16 == 0 (lda % 4 == 0); no residual, activation or LayerNorm; anything
+ * else returns OCC_E_UNSUPPORTED. */
+int occ_linear_bf16x3_q16rows(const float* a, int64_t lda, int K, const void* weight_packed, const float* bias,
+                              const float* scale, void* out, int M, int N, int groups, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Row-local Linear CHAINS of a BEVFormerLayer, one launch each (csrc/linear_chain_x3.hip; bf16x3 arithmetic as

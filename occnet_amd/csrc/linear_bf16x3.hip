@@ -44,13 +44,17 @@ __global__ void linear_pack_weight_bf16x3_kernel(const float* __restrict__ w,
   dst[64 * 8] = lo;
 }
 
-template <int NT, int RT, bool ADD>
+// Q16 (occ_linear_bf16x3_q16rows; NT == 2, N == 256, plain bias epilogue): the row-major epilogue stores the rows as q16
+// pixel pairs (common.h q16_*; the layout of occ_sca_rows_encode_q16) instead of fp32: `out` is the int16 buffer, q_scale the
+// DEVICE range scale (or null), q_rows the rows S of one map.  A lane's 4 columns are half of a 16-byte piece of 8 channels:
+// the piece maximum is one exchange with the neighbouring lane, the even lane carries the two exponent-tagged elements.
+template <int NT, int RT, bool ADD, bool Q16 = false>
 __global__ __launch_bounds__(256) void linear_bf16x3_kernel(
     const float* __restrict__ a1, long lda1, int K1, const float* __restrict__ a2,
     const float* __restrict__ a2add, long lda2, int K2, const uint4* __restrict__ wp,
     const float* __restrict__ bias, int act, const float* __restrict__ residual, long ldres,
     const float* __restrict__ ln_g, const float* __restrict__ ln_b, float ln_eps,
-    float* __restrict__ out, long ldo, int M, int N) {
+    float* __restrict__ out, long ldo, int M, int N, const float* __restrict__ q_scale, int q_rows) {
   constexpr int BM = 32 * RT, BN = 128 * NT, WR = 32 * NT, OLD = BN + 4;
   constexpr int A_BYTES = BM * kXLD;                                 // one plane (hi or lo)
   // LDS: only the activation chunk (hi + lo planes), split and staged ONCE per block (double buffered, one
@@ -181,6 +185,8 @@ __global__ __launch_bounds__(256) void linear_bf16x3_kernel(
   }
   const float inv_n = fdiv(1.f, (float)N);     // (no `/` on fp32 in device code: common.h)
   float* sO = reinterpret_cast<float*>(lds);
+  const int q_eosc = Q16 ? __builtin_amdgcn_frexp_expf(q_scale != nullptr ? *q_scale : 1.f) - 2 : 0;      // log2(s / 2)
+  const int q_tag = Q16 ? lane_flag((lane & 1) == 0) : 0;     // this lane holds elements 0 .. 3 of its piece
 #pragma unroll
   for (int rt = 0; rt < RT; ++rt) {
     __syncthreads();
@@ -206,6 +212,24 @@ __global__ __launch_bounds__(256) void linear_bf16x3_kernel(
       const int row = wave * 8 + rr;
       const long m = m0 + rt * 32 + row;
       if (m >= M) break;                       // wave-uniform
+      if constexpr (Q16) {                     // N == BN == 256: every lane holds 4 live columns
+        float4 v = *reinterpret_cast<const float4*>(sO + row * OLD + c);
+        v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
+        float mx = fmaxf(fmaxf(fabsf(v.x), fabsf(v.y)), fmaxf(fabsf(v.z), fabsf(v.w)));
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        const int E = q16_group_exponent(mx, q_eosc);
+        const float f = ldexpf(1.f, q_eosc + 15 - E);
+        const int r0 = q_tag ? E & 3 : 0, r1 = q_tag ? E >> 2 : 0;
+        uint2 o;
+        o.x = q16_pair_tagged(v.x, v.y, q_tag ? f * 0.25f : f, -0.25f * (float)r0, -0.25f * (float)r1, r0, r1, q_tag ? 2 : 0);
+        o.y = q16_pair(v.z, v.w, f);
+        const long g = m / q_rows;
+        const int pr = (int)(m - g * q_rows);
+        // 8-byte units: a pixel pair is 8 heads x 2 pixels x 8 units; lane = head * 8 + unit
+        uint2* dst = reinterpret_cast<uint2*>(out) + (g * ((q_rows + 1) >> 1) + (pr >> 1)) * 128;
+        dst[(lane >> 3) * 16 + (pr & 1) * 8 + (lane & 7)] = o;
+        continue;
+      }
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if (col_live) {
         v = *reinterpret_cast<const float4*>(sO + row * OLD + c);
@@ -228,6 +252,10 @@ __global__ __launch_bounds__(256) void linear_bf16x3_kernel(
   }
 }
 
+
+// two row tiles per wave (W slice staged once per 64 rows: a third less L1 traffic per flop — the kernel's bound) whenever
+// 64-row blocks still give every CU at least two of them
+static inline bool linear_x3_rt2(int M, int N) { return ((long)(M + 63) / 64) * ((N + 255) / 256) >= 2L * 256; }
 
 }  // namespace occ
 
@@ -273,14 +301,12 @@ extern "C" int occ_linear_bf16x3_f32(const float* a1, int64_t lda1, int K1, cons
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const uint4* wp = reinterpret_cast<const uint4*>(weight_packed);
-  // two row tiles per wave (W slice staged once per 64 rows: a third less L1 traffic per flop — the
-  // kernel's bound) whenever 64-row blocks still give every CU at least two of them
-  const bool rt2 = ((long)(M + 63) / 64) * ((N + 255) / 256) >= 2L * 256;
+  const bool rt2 = linear_x3_rt2(M, N);
 #define OCC_X3_LAUNCH_(NTT, RTT, BNN, ADDD)                                                         \
   hipLaunchKernelGGL((linear_bf16x3_kernel<NTT, RTT, ADDD>),                                        \
                      dim3((unsigned)((M + 32 * RTT - 1) / (32 * RTT)), (unsigned)((N + BNN - 1) / BNN)), \
                      dim3(256), 0, st, a1, (long)lda1, K1, a2, a2_add, (long)lda2, K2, wp, bias, act, \
-                     residual, (long)ldres, ln_gamma, ln_beta, ln_eps, out, (long)ldo, M, N)
+                     residual, (long)ldres, ln_gamma, ln_beta, ln_eps, out, (long)ldo, M, N, nullptr, 0)
 #define OCC_X3_LAUNCH(NTT, RTT, BNN)                                                                \
   do {                                                                                              \
     if (a2_add) OCC_X3_LAUNCH_(NTT, RTT, BNN, true); else OCC_X3_LAUNCH_(NTT, RTT, BNN, false);      \
@@ -293,5 +319,34 @@ extern "C" int occ_linear_bf16x3_f32(const float* a1, int64_t lda1, int K1, cons
 #undef OCC_X3_LAUNCH
 #undef OCC_X3_LAUNCH_
   OCC_CHECK_LAUNCH("linear_bf16x3");
+  return OCC_OK;
+}
+
+// The plain Linear with the q16 pixel-pair epilogue (the value rows of occ_tsa_fused_forward_q16v): linear_bf16x3_kernel<2, RT>
+// with the tile choice of occ_linear_bf16x3_f32, so the encoded values are that entry point's fp32 results bit for bit.
+extern "C" int occ_linear_bf16x3_q16rows(const float* a, int64_t lda, int K, const void* weight_packed,
+                                         const float* bias, const float* scale, void* out, int M, int N, int groups,
+                                         void* stream) {
+  using namespace occ;
+  OCC_CHECK_ARG(a && weight_packed && out, "linear_bf16x3_q16rows: null pointer argument");
+  OCC_CHECK_ARG(M > 0 && N > 0 && K > 0 && groups > 0, "linear_bf16x3_q16rows: bad dimension (M=%d N=%d K=%d groups=%d)",
+                M, N, K, groups);
+  OCC_CHECK_ARG(M % groups == 0, "linear_bf16x3_q16rows: M=%d rows do not split into %d maps", M, groups);
+  OCC_CHECK_ARG(lda >= K, "linear_bf16x3_q16rows: leading dimension smaller than the row");
+  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(out) % 16 == 0, "linear_bf16x3_q16rows: out must be 16-byte aligned");
+  if (N != 256 || K % kXBK || lda % 4) {
+    set_error("linear_bf16x3_q16rows: no kernel for K=%d N=%d (need N == 256, K %% 16 == 0, 16-byte aligned rows)", K, N);
+    return OCC_E_UNSUPPORTED;
+  }
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const uint4* wp = reinterpret_cast<const uint4*>(weight_packed);
+  const int S = M / groups;
+#define OCC_X3_LAUNCH_Q(RTT)                                                                                          \
+  hipLaunchKernelGGL((linear_bf16x3_kernel<2, RTT, false, true>), dim3((unsigned)((M + 32 * RTT - 1) / (32 * RTT)), 1u), \
+                     dim3(256), 0, st, a, (long)lda, K, nullptr, nullptr, 0L, 0, wp, bias, 0, nullptr, 0L, nullptr,   \
+                     nullptr, 0.f, reinterpret_cast<float*>(out), 0L, M, N, scale, S)
+  if (linear_x3_rt2(M, N)) OCC_X3_LAUNCH_Q(2); else OCC_X3_LAUNCH_Q(1);
+#undef OCC_X3_LAUNCH_Q
+  OCC_CHECK_LAUNCH("linear_bf16x3_q16rows");
   return OCC_OK;
 }

@@ -180,6 +180,20 @@ SCA_VALUES = os.environ.get("OCC_SCA_VALUES", "q16")
 if SCA_VALUES not in ("f16", "f32", "q16"):
     raise OccAmdError(f"OCC_SCA_VALUES={SCA_VALUES!r}: expected f16, f32 or q16")
 
+# Storage type of the projected BEV maps the fused TSA gather reads at INFERENCE (TemporalSelfAttention.fused_gather; the
+# reference keeps them in fp32; the training node always reads fp32 rows).  Sampling arithmetic, softmax and accumulation are
+# fp32 either way.
+#   'f32' (default): 128-byte head rows, 8 lanes per row, 32 16-byte loads per lane (csrc/tsa_fused.hip tsa_fused_kernel);
+#   'q16' (OCC_TSA_VALUES=q16, opt-in): the block-floating-point rows of the SCA gather in its pixel-pair layout — 64-byte head
+#         rows, 4 lanes per row, 16 loads per lane (tsa_fused_q16_kernel).  The rows are written by the value projection
+#         itself where it is a stand-alone Linear (linear_q16rows: history BEV, bs > 1) and by one sca_rows_encode_q16 pass
+#         over the fp32 rows where they come out of a chain kernel (no history); their range scale comes from the LayerNorm
+#         bound of the producer of the BEV rows (layernorm_bound_words) or one amax pass (tsa_value_scale).  Measured step
+#         times and the storage error: DESIGN.md (TSA q16 rows), EXPERIMENTS.md.
+TSA_VALUES = os.environ.get("OCC_TSA_VALUES", "f32")
+if TSA_VALUES not in ("f32", "q16"):
+    raise OccAmdError(f"OCC_TSA_VALUES={TSA_VALUES!r}: expected f32 or q16")
+
 
 def sca_head_major():
     """The 16-bit-row SCA gather runs on the head-major kernel (one wave = 8 queries x one head, heads dealt to the XCDs;
@@ -396,10 +410,13 @@ class SCAFusedFunction(torch.autograd.Function):
 
 
 def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points,
-                      shared_queue=False, order=None, value_rows=None):
+                      shared_queue=False, order=None, value_rows=None, value_scale=None):
     """Fused TSA gather.  value: (B*2, Nq, M, D), or (B, Nq, M, D) with shared_queue=True when both
     queue entries are the same projected BEV (no history).  offs (B,Nq,M*2*P*2), logits
     (B,Nq,M*2*P), ref_2d (B*2,Nq,1,2).  -> (B, Nq, M*D).
+    An int16 value holds q16 rows in the pixel-pair layout (linear_q16rows / sca_rows_encode_q16): (B*2 or B, S_pad, M, D)
+    with S_pad = bev_h*bev_w rounded up to even, value_scale the 1-element float32 device tensor they were encoded with
+    (None = 1) — occ_tsa_fused_forward_q16v; everything else as for fp32 rows.
     value_rows (B == 1 only): the queries are a ROW BAND of the BEV — offs / logits / ref_2d / order / the result cover
     Nq < bev_h*bev_w queries (order holds band-local indices) while `value` is the whole (bev_h*bev_w = value_rows)-pixel
     map: the encoder's row pipeline (plugin/encoder.py).
@@ -410,31 +427,46 @@ def tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_
     The kernel reads float2 offset pairs and 16-byte pieces of value rows: offs must start 8-byte aligned with an even row
     stride, value 16-byte aligned (any slice of a Linear output at an even column is)."""
     return _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points, shared_queue, order,
-                              value_rows, 'tsa_fused_forward')
+                              value_rows, 'tsa_fused_forward', value_scale)
 
 
 def _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num_points, shared_queue, order, value_rows,
-                       timing):
+                       timing, value_scale=None):
     """tsa_fused_forward under the timing label `timing` (the training node keeps its launches apart from the inference
     gather's)."""
-    _need_cuda_f32("value", value)
+    q16 = isinstance(value, torch.Tensor) and value.dtype == torch.int16
+    if q16:
+        if not (value.is_cuda and value.is_contiguous() and value.dim() in (3, 4)):
+            raise OccAmdError("tsa_fused_forward: q16 value must be a contiguous int16 device tensor (B*2 or B, S_pad, M, D)")
+        if value_scale is not None and not (isinstance(value_scale, torch.Tensor) and value_scale.dtype == torch.float32
+                                            and value_scale.numel() == 1 and value_scale.device == value.device):
+            raise OccAmdError("tsa_fused_forward: value_scale must be a 1-element float32 tensor on value's device")
+    else:
+        if value_scale is not None:
+            raise OccAmdError("tsa_fused_forward: value_scale goes with q16 (int16) value rows")
+        _need_cuda_f32("value", value)
     _need_cuda_f32("ref_2d", ref_2d)
     _need_cuda_f32("offs", offs, contiguous=False)
     _need_cuda_f32("logits", logits, contiguous=False)
     if offs.dim() != 3 or logits.dim() != 3:
         raise OccAmdError("tsa_fused_forward: offs and logits must be (B,Nq,...)")
     B, Nq = offs.shape[:2]
-    M, D, P = int(num_heads), value.shape[-1], int(num_points)
+    M, P = int(num_heads), int(num_points)
     Nv = Nq if value_rows is None else int(value_rows)
     if Nv != bev_h * bev_w or (value_rows is not None and B != 1):
         raise OccAmdError("tsa_fused_forward: the value map must have bev_h*bev_w rows (a query band needs B == 1)")
-    per = Nv * M * D
+    # rows of one stored map: q16 maps are pixel pairs, padded to an even row count
+    Nr = value.shape[1] if q16 else Nv
+    D = value.shape[-1] // M if q16 and value.dim() == 3 else value.shape[-1]      # the encoders return (maps, S_pad, M*D)
+    if q16 and Nr != Nv + (Nv & 1):
+        raise OccAmdError("tsa_fused_forward: a q16 value map must have bev_h*bev_w rows rounded up to even")
+    per = Nr * M * D
     if shared_queue:
         if value.numel() != B * per:
             raise OccAmdError("tsa_fused_forward: shared value must be (B,Nq,M,D)")
         if B != 1:
             # entry (b,t) lives at (b*2+t)*stride: aliasing both entries needs stride 0 -> B == 1
-            value = torch.stack([value.view(B, Nq, M, D)] * 2, 1).reshape(B * 2, Nq, M, D).contiguous()
+            value = torch.stack([value.view(B, Nr, M, D)] * 2, 1).reshape(B * 2, Nr, M, D).contiguous()
             stride = per
         else:
             stride = 0
@@ -459,10 +491,16 @@ def _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num
         raise OccAmdError("tsa_fused_forward: order must be a contiguous int32 (Nq) tensor on value's device")
     out = torch.empty((B, Nq, M * D), dtype=torch.float32, device=value.device)
     with torch.cuda.device(value.device), _timed(timing):
-        rc = _lib.lib().occ_tsa_fused_forward_f32(
-            ptr(value), i64(stride), ptr(offs), i64(offs.stride(1)), ptr(logits),
-            i64(logits.stride(1)), ptr(ref_2d), ptr(order), ptr(out), i32(B), i32(Nq), i32(bev_h),
-            i32(bev_w), i32(M), i32(D), i32(P), stream_ptr(value.device))
+        if q16:
+            rc = _lib.lib().occ_tsa_fused_forward_q16v(
+                ptr(value), i64(stride), i32(Nr), ptr(offs), i64(offs.stride(1)), ptr(logits),
+                i64(logits.stride(1)), ptr(ref_2d), ptr(order), ptr(out), i32(B), i32(Nq), i32(bev_h),
+                i32(bev_w), i32(M), i32(D), i32(P), ptr(value_scale), stream_ptr(value.device))
+        else:
+            rc = _lib.lib().occ_tsa_fused_forward_f32(
+                ptr(value), i64(stride), ptr(offs), i64(offs.stride(1)), ptr(logits),
+                i64(logits.stride(1)), ptr(ref_2d), ptr(order), ptr(out), i32(B), i32(Nq), i32(bev_h),
+                i32(bev_w), i32(M), i32(D), i32(P), stream_ptr(value.device))
     _lib.check(rc, "tsa_fused_forward")
     return out
 
@@ -878,11 +916,17 @@ def value_range_scale_from_amax(amax8, row_l1, bias_max):
     if not (isinstance(amax8, torch.Tensor) and amax8.is_cuda and amax8.dtype == torch.int32 and amax8.numel() == 8
             and amax8.is_contiguous()):
         raise OccAmdError("value_range_scale_from_amax: amax8 must be 8 contiguous int32 device words")
+    return _range_scale_from_amax(amax8, row_l1, bias_max, 'value_range')
+
+
+def _range_scale_from_amax(amax8, row_l1, bias_max, timing):
+    """The launch of value_range_scale_from_amax, under the timing label `timing` (tsa_value_scale keeps its launches out of
+    the SCA planes' 'value_range' figure)."""
     dev = amax8.device
     r, b = _range_terms_dev(row_l1, bias_max, dev)
     P = r.numel()
     out = torch.empty(2 * P + 1, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed('value_range'):
+    with torch.cuda.device(dev), _timed(timing):
         rc = _lib.lib().occ_value_range_scale_from_amax(ptr(amax8), i32(P), ptr(r), ptr(b), ptr(out), stream_ptr(dev))
     _lib.check(rc, "value_range_scale_from_amax")
     return out
@@ -923,6 +967,114 @@ def q16_range_scaled(v):
     ok = torch.isfinite(amax) & (amax > 0)
     s = torch.where(ok, torch.ldexp(torch.ones_like(amax), (15 - e).clamp(-100, 100)), torch.ones_like(amax)).reshape(1)
     return sca_rows_encode_q16(v.contiguous(), s), s
+
+
+# ---- range scale of the q16 TSA value rows (OCC_TSA_VALUES=q16) from fp32 inputs, without a scale kernel of its own ---------
+def absmax_words_f32(a_or_bound):
+    """A float32 tensor (its max|a| is taken) or scalar bound -> the 8 int32 words value_range_scale_from_amax reads: the
+    bf16 pattern of the bound ROUNDED UP, (bits + 0xffff) >> 16 on the sign-stripped fp32 bits, so the pattern never decodes to
+    less than the bound (and to less than bound * (1 + 2^-7) for a normal number).  ATen ops on the tensor's device, no host
+    synchronisation.  Inf / NaN give an Inf / NaN pattern: the scale kernel then returns s = 1, as q16_range_scaled does."""
+    m = a_or_bound.detach().to(torch.float32).abs().reshape(-1).amax()
+    bits = m.view(torch.int32).to(torch.int64) & 0x7fffffff
+    pattern = ((bits + 0xffff) >> 16).clamp(max=0x7fff)           # (0x7fff: a NaN pattern, not the sign bit)
+    return pattern.to(torch.int32).reshape(1).repeat(8)
+
+
+_LN_BOUND = {}          # (gamma, beta identity, epoch) -> (sources kept alive, words)
+_TSA_RANGE_TERMS = {}   # (weight, bias identity, epoch) -> (sources kept alive, row_l1, bias_max)
+
+
+def layernorm_bound_words(ln):
+    """absmax_words_f32 of the analytic bound of a LayerNorm's output over N channels (ln: nn.LayerNorm or (gamma, beta, eps)):
+    sum_c (x_c - mean) = 0 gives (x_c - mean)^2 <= (N - 1) var, so |y_c| <= |gamma_c| sqrt(N - 1) + |beta_c| for any input row
+    and any eps >= 0; 2^-8 of slack covers the fp32 arithmetic of the kernels: both LayerNorm epilogues (csrc/linear_bf16x3.hip,
+    csrc/linear_chain_x3.hip) square the very deviations d_c they normalise, so |d_c| rstd <= sqrt(N) holds whatever the
+    rounding of the mean, and sqrt(N) / sqrt(N - 1) is inside the slack from N = 129 on (they run at N = 256).  Cached on
+    (gamma, beta) identity."""
+    g, b = (ln.weight, ln.bias) if isinstance(ln, torch.nn.LayerNorm) else (ln[0], ln[1])
+    key = (_ident(g), _ident(b), str(g.device), cache_epoch())
+    hit = _LN_BOUND.get(key)
+    if hit is not None:
+        return hit[1]
+    n = g.numel()
+    bound = g.detach().float().abs().amax() * (float(max(n - 1, 0)) ** 0.5 * 1.00390625)
+    if b is not None:
+        bound = bound + b.detach().float().abs().amax()
+    words = absmax_words_f32(bound)
+    if len(_LN_BOUND) >= 64:
+        _LN_BOUND.pop(next(iter(_LN_BOUND)))
+    _LN_BOUND[key] = ((g, b), words)
+    return words
+
+
+def _attach_ln_bound(t, gamma, beta):
+    """A LayerNorm output leaves linear(ln=) / linear_ln_chain / encoder_ffn_chain with its analytic bound attached
+    (attach_absmax: an in-place write drops it), for the q16 value projection that may consume it.  Only under
+    OCC_TSA_VALUES=q16: nobody reads the words otherwise, and the default path stays free of even the cache lookup."""
+    if TSA_VALUES == "q16":
+        attach_absmax(t, layernorm_bound_words((gamma, beta, 0.0)))
+
+
+def tsa_value_scale(value_proj, words):
+    """The power-of-two range scale s (1-element float32 device tensor) of the q16 rows of value_proj(x) for inputs with
+    max|x| <= the bound in `words` (absmax_words_f32 / layernorm_bound_words / absmax_of):
+    (bound * row_l1 * (1 + 2^-8) + bias_max) * s <= 2^15 with row_l1 = max_n sum_k |W_nk|, bias_max = max|b| (device tensors,
+    cached per weight version) — occ_value_range_scale_from_amax, one 64-thread launch."""
+    w, b = value_proj.weight, value_proj.bias
+    key = (_ident(w), _ident(b), str(w.device), cache_epoch())
+    hit = _TSA_RANGE_TERMS.get(key)
+    if hit is None:
+        row_l1 = w.detach().float().abs().sum(1).amax().reshape(1)
+        bias_max = (b.detach().float().abs().amax() if b is not None else torch.zeros((), device=w.device)).reshape(1)
+        if len(_TSA_RANGE_TERMS) >= 64:
+            _TSA_RANGE_TERMS.pop(next(iter(_TSA_RANGE_TERMS)))
+        hit = _TSA_RANGE_TERMS[key] = ((w, b), row_l1, bias_max)
+    if not (isinstance(words, torch.Tensor) and words.is_cuda and words.dtype == torch.int32 and words.numel() == 8
+            and words.is_contiguous()):
+        raise OccAmdError("tsa_value_scale: words must be 8 contiguous int32 device words")
+    return _range_scale_from_amax(words, hit[1], hit[2], 'tsa_value_range')[:1]
+
+
+def linear_q16rows(a, weight, bias, scale, groups, act=None, residual=None, ln=None):
+    """The plain bf16x3 Linear a @ weight^T + bias with a q16 epilogue (csrc/linear_bf16x3.hip): the M rows of `a` are
+    `groups` maps of S = M / groups rows; -> int16 (groups, S + (S & 1), 256) q16 pixel pairs, bit for bit what
+    sca_rows_encode_q16(linear(a, weight, bias).view(groups, S, 256), scale) returns, without the fp32 round trip.  scale: the
+    1-element float32 device tensor s (tsa_value_scale), None = 1.  Covers N == 256, K % 16 == 0, the bf16x3 precision mode and
+    no activation / residual / LayerNorm: OccAmdUnsupported otherwise (nothing is launched)."""
+    if act is not None or residual is not None or ln is not None:
+        raise OccAmdUnsupported("linear_q16rows: the q16 epilogue takes no activation, residual or LayerNorm")
+    if LINEAR_PRECISION != "bf16x3":
+        raise OccAmdUnsupported("linear_q16rows: bf16x3 precision mode only")
+    a_, M, K, lda = _rows2d("a", a)
+    _need_cuda_f32("weight", weight)
+    if weight.dim() != 2 or weight.shape[1] != K or not weight.is_contiguous():
+        raise OccAmdError("linear_q16rows: weight must be a contiguous (N, K) matrix")
+    N = weight.shape[0]
+    if N != 256 or K % 16:
+        raise OccAmdUnsupported(f"linear_q16rows: no kernel for N={N} K={K} (need N == 256, K % 16 == 0)")
+    if bias is not None:
+        _need_cuda_f32("bias", bias)
+        if bias.numel() != N:
+            raise OccAmdError("linear_q16rows: bias must have N entries")
+    groups = int(groups)
+    if groups <= 0 or M % groups:
+        raise OccAmdError(f"linear_q16rows: {M} rows do not split into {groups} maps")
+    if scale is not None and not (isinstance(scale, torch.Tensor) and scale.is_cuda and scale.dtype == torch.float32
+                                  and scale.numel() == 1 and scale.device == a.device):
+        raise OccAmdError("linear_q16rows: scale must be a 1-element float32 tensor on a's device")
+    S = M // groups
+    wp = linear_pack_weight_bf16x3(weight)
+    out = torch.empty((groups, S + (S & 1), N), dtype=torch.int16, device=a.device)
+    if S & 1:                                    # the pad pixel of every map: never sampled, kept defined (sca_rows_encode_q16)
+        out.view(groups, (S + 1) // 2, N // 32, 2, 32)[:, -1, :, 1, :].zero_()
+    if _TIMING is not None and (_TIMING_ONLY is None or 'linear' in _TIMING_ONLY):
+        _TIMING.setdefault('linear_flops', []).append(2.0 * M * N * K)
+    with torch.cuda.device(a.device), _timed('linear'):
+        rc = _lib.lib().occ_linear_bf16x3_q16rows(ptr(a_), i64(lda), i32(K), ptr(wp), ptr(bias), ptr(scale), ptr(out),
+                                                  i32(M), i32(N), i32(groups), stream_ptr(a.device))
+    _lib.check(rc, "linear_q16rows")
+    return out
 
 
 def value_proj_bf16(a_list, weight, group_bias, out, rows_per_group, out_group_rows, out_row0, out_scale=None):
@@ -1113,6 +1265,8 @@ def linear(a, weight, bias=None, a2=None, a2_add=None, act=None, residual=None, 
                 ptr(bias), i32(1 if act == 'relu' else 0), ptr(residual), i64(ldres), ptr(g), ptr(b),
                 f32(float(eps)), ptr(out), i64(N), i32(M), i32(N), stream_ptr(a.device))
     _lib.check(rc, "linear")
+    if g is not None:
+        _attach_ln_bound(out, g, b)
     return out
 
 
@@ -1228,6 +1382,7 @@ def linear_ln_chain(a, residual, w1, b1, ln, w2, b2, act2=None):
             ptr(a_), i64(lda), ptr(r_), i64(ldres), ptr(wp), ptr(bias), ptr(g), ptr(b), f32(eps), ptr(y), i64(256),
             ptr(z), i64(n2), i32(n2), i32(1 if act2 == 'relu' else 0), i32(M), stream_ptr(a.device))
     _lib.check(rc, "linear_ln_chain")
+    _attach_ln_bound(y, g, b)
     return y, z
 
 
@@ -1292,6 +1447,7 @@ def encoder_ffn_chain(a, residual, wo, bo, ln1, w1, b1, w2, b2, ln2, tail=None, 
             ptr(be2), f32(eps2), ptr(y), i64(ldy), ptr(q_term), i64(ldq), ptr(zq), i64(ldzq), i32(nq), ptr(zv),
             i64(ldzv), i32(M), stream_ptr(a.device))
     _lib.check(rc, "encoder_ffn_chain")
+    _attach_ln_bound(y, g2, be2)
     return y, zq, zv
 
 

@@ -14,6 +14,9 @@ per head and queue entry; the two queue results are averaged, projected and adde
 * fused training path (OCC_TSA_TRAIN_FUSED=1, default off): the same gather as an autograd node
   (ext.TSAFusedFunction, csrc/tsa_fused_backward.hip) on column slices of the one query GEMM; without
   history (bs = 1) the value is projected once and the node aliases it.
+* q16 value rows (OCC_TSA_VALUES=q16, default off; fused inference path only): the projected BEV maps are stored as
+  the block-floating-point rows of the SCA gather and read by `occ_tsa_fused_forward_q16v` (csrc/tsa_fused.hip);
+  the value projection writes them itself where it is a stand-alone Linear (`ext.linear_q16rows`), `_q16_rows`.
 """
 import math
 import os
@@ -141,6 +144,7 @@ class TemporalSelfAttention(BaseModule):
             value = torch.stack([query, query], 1).reshape(bs * 2, num_query, c)
             shared = False
         n_off = self.sampling_offsets.out_features
+        v = None                # the fp32 value rows, where a chain kernel already projected them
         if pre is not None and shared:
             lin, v = pre
         else:
@@ -150,29 +154,53 @@ class TemporalSelfAttention(BaseModule):
                 # no history: cat([q, q + pos]) @ W^T + b = q @ (Wa + Wb)^T + (pos @ Wb^T + b); the
                 # position term is constant while weights and positional encoding are (inference)
                 w_sum, pos_term = self._folded_query_weights(w, b, query_pos)
+                lin = None
                 if ext.LINEAR_CHAIN and ext.LINEAR_PRECISION == "bf16x3" and bs == 1:
                     try:        # both Linears of the same rows in one launch (program C of csrc/linear_chain_x3.hip)
                         lin, v = ext.linear_pair_chain(query.contiguous(), w_sum, pos_term, self.value_proj.weight,
                                                        self.value_proj.bias)
                     except OccAmdUnsupported:
                         lin = None
-                    if lin is not None:
-                        v = v.view(v.shape[0], num_query, self.num_heads, -1)
-                        return ext.tsa_fused_forward(v, lin[..., :n_off], lin[..., n_off:],
-                                                     reference_points.float().contiguous(), bev_h, bev_w,
-                                                     self.num_heads, self.num_points, shared_queue=shared,
-                                                     order=bev_order)
-                lin = ext.linear(query.contiguous(), w_sum, None, residual=pos_term)
+                if lin is None:
+                    lin = ext.linear(query.contiguous(), w_sum, None, residual=pos_term)
             else:
                 lin = ext.linear(value_first.contiguous(), w, b, a2=query.contiguous(),
                                  a2_add=None if query_pos is None else query_pos.contiguous())
-            vsrc = (value_first if shared else value).contiguous()
-            v = ext.linear(vsrc, self.value_proj.weight, self.value_proj.bias)
+        vsrc = query if shared else value
+        rows = None
+        if ext.TSA_VALUES == "q16":
+            try:
+                rows, scale = self._q16_rows(vsrc, v)
+            except OccAmdUnsupported:       # a value projection the q16 epilogue does not cover: today's fp32 rows
+                rows = None
+        if rows is not None:
+            return ext.tsa_fused_forward(rows, lin[..., :n_off], lin[..., n_off:],
+                                         reference_points.float().contiguous(), bev_h, bev_w,
+                                         self.num_heads, self.num_points, shared_queue=shared,
+                                         order=bev_order, value_scale=scale)
+        if v is None:
+            v = ext.linear(vsrc.contiguous(), self.value_proj.weight, self.value_proj.bias)
         v = v.view(v.shape[0], num_query, self.num_heads, -1)
         return ext.tsa_fused_forward(v, lin[..., :n_off], lin[..., n_off:],
                                      reference_points.float().contiguous(), bev_h, bev_w,
                                      self.num_heads, self.num_points, shared_queue=shared,
                                      order=bev_order)
+
+    def _q16_rows(self, source, v):
+        """OCC_TSA_VALUES=q16 (inference): the value rows of the fused gather as q16 pixel pairs -> (int16 (maps, S_pad, C), scale).
+        source (maps, num_query, C): the rows value_proj is applied to (the current BEV, or stack(prev_bev, bev)); v: their fp32
+        projection where a chain kernel already made it (encoded in one extra pass), else None (the projection writes q16
+        itself).  The range scale comes from the bound the producer of `source` attached (a LayerNorm output:
+        ext.layernorm_bound_words) or, for any other tensor, from one amax pass — kept on the tensor for the following layers,
+        which project the same stack."""
+        words = ext.absmax_of(source)
+        if words is None:
+            words = ext.attach_absmax(source, ext.absmax_words_f32(source))._occ_absmax
+        scale = ext.tsa_value_scale(self.value_proj, words)
+        maps, _, c = source.shape
+        if v is not None:
+            return ext.sca_rows_encode_q16(v.reshape(maps, -1, c), scale), scale
+        return ext.linear_q16rows(source.contiguous(), self.value_proj.weight, self.value_proj.bias, scale, maps), scale
 
     def chain_tail(self, query_pos):
         """Operands with which the PREVIOUS layer's chain kernel computes this layer's query Linears and value
