@@ -18,6 +18,8 @@
 // CH/2 contiguous floats of ONE voxel and its B fragment CH/2 contiguous floats of the packed weight.
 // Zero padding of the convolution = zero-filled halo slots.  Epilogue: y = relu(acc*scale + shift)
 // with the eval-mode BatchNorm folded into (scale, shift) per output channel, 128-byte rows per voxel.
+#include <type_traits>
+
 #include "heads_x3.h"
 
 namespace occ {
@@ -57,6 +59,156 @@ __device__ __forceinline__ ConvTile conv_tile_of_block(int tiles_x, int tiles_y)
   return {bid / tiles_y, ty_i * TY, tx_i * TX};
 }
 
+// ---- the pieces the four kernels share, as TEXT ----------------------------------------------------------------------
+// conv3d_mfma_kernel, conv3d_bf16x3_kernel, conv3d_bf16x3_c8_kernel and conv3d_heads_x3_kernel are one design (one ConvGeom,
+// one halo in LDS, one row-tile -> accumulator map), and conv3d_heads_x3_kernel must stage and contract exactly as
+// conv3d_bf16x3_kernel<.., 0> does (the fused decoder is tested against the two launches it replaces).  They expand the
+// blocks below, so they agree by construction.  Macros on the kernel's locals and not __device__ functions: as
+// __forceinline__ templates each of these pieces changed the registers or the unrolling of 20 to 36 of this file's 40
+// kernels (EXPERIMENTS.md sections 8h, 8u); the preprocessor changes nothing.
+//
+// Every piece expects in scope
+//   Z, CH, G, HX, HY, NACC      the kernel's geometry: template arguments, ConvGeom<Z, CH, TY, TX> and its constants
+//   tid, lane, wave             thread index, tid & 63, tid >> 6
+// and the staging pieces
+//   inb, y0, x0, Y, X, Cin      the batch entry's input, the tile's first pillar, the map's size, the input channels
+//   ldsb, PSB, VSB              (bf16 kernels) the halo as char*, pillar / voxel-slot strides in bytes
+//   lds, PS, VS                 (f32 kernel) the halo as float*, the strides in floats
+//
+// OCC_C3D_ZERO_ZHALO            bf16 kernels: zero the z = -1 and z = Z slots of every halo pillar (they stay zero for all
+//                               phases).  Declares nothing outside its loop.
+// OCC_C3D_ACC_ABASE(PSTR, VSTR, KOFF)
+//                               declares at the point of expansion, for the rest of the kernel: acc[NACC] (zeroed), vi =
+//                               lane & 31, kh = lane >> 5 and abase[NACC], the LDS offset of tap (0,0,0) = halo corner
+//                               (-1,-1,-1) of the lane's voxel in each of the wave's row tiles, in units of PSTR / VSTR.
+//                               KOFF: the lane half's term, pasted behind the sum (`+ kh * H2` floats, `+ kh * 16` bytes,
+//                               nothing where the lane halves are taps and not channels).
+// OCC_C3D_REQ_L0(C0)            LAYOUT 0, in[b][y][x][z][Cin]: request the thread's 16-byte items of CH channels of the halo.
+//                               Declares PARTS, ITEMS, ITERS and float4 v[ITERS] (zeros outside the map).  C0: the item's
+//                               first channel in terms of the piece's own `part` (`p * CH + part * 4`, or `part * 4` in
+//                               the single-phase kernel), pasted behind the address sum.
+// OCC_C3D_REQ_L1(CI)            LAYOUT 1, in[b][y][x][Cin][Z] (the lifter view): the same, an item = 4 heights of one
+//                               channel.  Declares Z4, ITEMS, ITERS, v[ITERS].  CI: the item's channel in terms of the
+//                               piece's own `ci` (`p * CH + ci`, or `ci`).
+// OCC_C3D_PUT_L0_X3(LO) / OCC_C3D_PUT_L1_X3(LO)
+//                               behind the matching request, in the same block: split v[] into hi / lo bf16 and store it;
+//                               LO = byte distance of the lo plane inside a voxel slot (2 * CH).
+// OCC_C3D_PUT_L0_F32 / OCC_C3D_PUT_L1_F32
+//                               the same for the f32 halo: v[] as it is.
+//                               Requests and stores stay two loops: as one loop hipcc waits for every load before it issues
+//                               the next.  Expand a request and its store inside a block of their own.
+// OCC_C3D_WRING_REQ3(TAP)       the weight ring's preamble (conv_taps27): request taps 0-2 into w[0..2].  Expects w, wr, wv;
+//                               TAP: the tap of ring step `t`, clamped by the kernel where its weight can have fewer than
+//                               three taps' worth left.
+// OCC_C3D_BN_RELU_STORE         epilogue of the three convolution kernels: y = relu(acc * scale + shift), one 128-byte row
+//                               per voxel.  Expects acc, vi, kh, b, scale, shift, out, out_sb, out_sy, out_sx, relu; declares
+//                               sc, sh, outb: expand it last.
+#define OCC_C3D_ZERO_ZHALO                                                                                     \
+  for (int i = tid; i < HY * HX * 2 * (VSB / 16); i += 256) {                                                  \
+    const int pil = i / (2 * (VSB / 16)), rem = i % (2 * (VSB / 16));                                          \
+    const int part = rem % (VSB / 16);                                                                         \
+    *reinterpret_cast<uint4*>(ldsb + pil * PSB + (rem >= VSB / 16 ? (Z + 1) * VSB : 0) + part * 16) =          \
+        make_uint4(0u, 0u, 0u, 0u);                                                                            \
+  }
+#define OCC_C3D_ACC_ABASE(PSTR, VSTR, KOFF)                                                                    \
+  f32x16 acc[NACC];                                                                                            \
+  _Pragma("unroll") for (int a = 0; a < NACC; ++a)                                                             \
+    _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;                                            \
+  const int vi = lane & 31, kh = lane >> 5;                                                                    \
+  int abase[NACC];                                                                                             \
+  _Pragma("unroll") for (int a = 0; a < NACC; ++a) {                                                           \
+    const int rt = wave * NACC + a;                                                                            \
+    const int ty = rt / G::TXG, txg = rt % G::TXG;                                                             \
+    const int px = txg * G::PX + vi / Z, z = vi % Z;                                                           \
+    abase[a] = (ty * HX + px) * PSTR + z * VSTR KOFF;                                                          \
+  }
+#define OCC_C3D_REQ_L0(C0)                                                                                     \
+  constexpr int PARTS = CH / 4, ITEMS = HY * HX * Z * PARTS, ITERS = (ITEMS + 255) / 256;                      \
+  float4 v[ITERS];                                                                                             \
+  _Pragma("unroll") for (int it = 0; it < ITERS; ++it) {                                                       \
+    const int idx = tid + it * 256;                                                                            \
+    const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);                              \
+    const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;                                                  \
+    v[it] = make_float4(0.f, 0.f, 0.f, 0.f);                                                                   \
+    if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)                                                 \
+      v[it] = *reinterpret_cast<const float4*>(inb + (((long)gy * X + gx) * Z + z) * Cin + C0);                \
+  }
+#define OCC_C3D_REQ_L1(CI)                                                                                     \
+  constexpr int Z4 = Z / 4, ITEMS = HY * HX * CH * Z4, ITERS = (ITEMS + 255) / 256;                            \
+  float4 v[ITERS];                                                                                             \
+  _Pragma("unroll") for (int it = 0; it < ITERS; ++it) {                                                       \
+    const int idx = tid + it * 256;                                                                            \
+    const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);                                      \
+    const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;                                                  \
+    v[it] = make_float4(0.f, 0.f, 0.f, 0.f);                                                                   \
+    if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)                                                 \
+      v[it] = *reinterpret_cast<const float4*>(inb + ((long)gy * X + gx) * Z * Cin + (long)(CI) * Z + z4 * 4); \
+  }
+#define OCC_C3D_PUT_L0_X3(LO)                                                                                  \
+  _Pragma("unroll") for (int it = 0; it < ITERS; ++it) {                                                       \
+    const int idx = tid + it * 256;                                                                            \
+    const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);                              \
+    if (idx < ITEMS) {                                                                                         \
+      unsigned h01, h23, l01, l23;                                                                             \
+      bf16_split2(v[it].x, v[it].y, h01, l01);                                                                 \
+      bf16_split2(v[it].z, v[it].w, h23, l23);                                                                 \
+      char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;                                                   \
+      *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);                                                     \
+      *reinterpret_cast<uint2*>(d + LO) = make_uint2(l01, l23);                                                \
+    }                                                                                                          \
+  }
+#define OCC_C3D_PUT_L1_X3(LO)                                                                                  \
+  _Pragma("unroll") for (int it = 0; it < ITERS; ++it) {                                                       \
+    const int idx = tid + it * 256;                                                                            \
+    const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);                                      \
+    if (idx < ITEMS) {                                                                                         \
+      const float f[4] = {v[it].x, v[it].y, v[it].z, v[it].w};                                                 \
+      char* d = ldsb + pil * PSB + (z4 * 4 + 1) * VSB + ci * 2;                                                \
+      _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                          \
+        unsigned short hi, lo;                                                                                 \
+        bf16_split(f[q], hi, lo);                                                                              \
+        *reinterpret_cast<unsigned short*>(d + q * VSB) = hi;                                                  \
+        *reinterpret_cast<unsigned short*>(d + q * VSB + LO) = lo;                                             \
+      }                                                                                                        \
+    }                                                                                                          \
+  }
+#define OCC_C3D_PUT_L0_F32                                                                                     \
+  _Pragma("unroll") for (int it = 0; it < ITERS; ++it) {                                                       \
+    const int idx = tid + it * 256;                                                                            \
+    const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);                              \
+    if (idx < ITEMS) *reinterpret_cast<float4*>(lds + pil * PS + (z + 1) * VS + part * 4) = v[it];             \
+  }
+#define OCC_C3D_PUT_L1_F32                                                                                     \
+  _Pragma("unroll") for (int it = 0; it < ITERS; ++it) {                                                       \
+    const int idx = tid + it * 256;                                                                            \
+    const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);                                      \
+    if (idx < ITEMS) {                                                                                         \
+      float* d = lds + pil * PS + (z4 * 4 + 1) * VS + ci;                                                      \
+      d[0] = v[it].x; d[VS] = v[it].y; d[2 * VS] = v[it].z; d[3 * VS] = v[it].w;                               \
+    }                                                                                                          \
+  }
+#define OCC_C3D_WRING_REQ3(TAP)                                                                                \
+  _Pragma("unroll") for (int t = 0; t < 3; ++t) {                                                              \
+    const int tn = TAP;                                                                                        \
+    w[t][0] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, tn * 2048, 0);                                     \
+    w[t][1] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, tn * 2048 + 1024, 0);                              \
+  }
+#define OCC_C3D_BN_RELU_STORE                                                                                  \
+  const float sc = scale[vi], sh = shift[vi];                                                                  \
+  float* outb = out + (long)b * out_sb;                                                                        \
+  _Pragma("unroll") for (int a = 0; a < NACC; ++a) {                                                           \
+    const int rt = wave * NACC + a;                                                                            \
+    const int ty = rt / G::TXG, txg = rt % G::TXG;                                                             \
+    const int gy = y0 + ty;                                                                                    \
+    _Pragma("unroll") for (int r = 0; r < 16; ++r) {                                                           \
+      const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;                                                         \
+      const int gx = x0 + txg * G::PX + row / Z, z = row % Z;                                                  \
+      float v = fmaf(acc[a][r], sc, sh);                                                                       \
+      if (relu) v = fmaxf(v, 0.f);                                                                             \
+      if (gy < Y && gx < X) outb[gy * out_sy + gx * out_sx + z * 32 + vi] = v;                                 \
+    }                                                                                                          \
+  }
+
 // LAYOUT 0: in[b][y][x][z][Cin]          (channels innermost: output layout of this kernel)
 // LAYOUT 1: in[b][y][x][Cin][Z]          (lifter view of the BEV embedding: c = ci*Z + z)
 template <int Z, int CH, int TY, int TX, int LAYOUT>
@@ -78,68 +230,18 @@ __global__ __launch_bounds__(256) void conv3d_mfma_kernel(
     lds[pil * PS + (rem >= VS ? (Z + 1) * VS : 0) + rem % VS] = 0.f;
   }
 
-  f32x16 acc[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
-
-  const int vi = lane & 31, kh = lane >> 5;
-  int abase[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int px = txg * G::PX + vi / Z, z = vi % Z;
-    abase[a] = (ty * HX + px) * PS + z * VS + kh * H2;  // tap (0,0,0) = halo corner (-1,-1,-1)
-  }
+  OCC_C3D_ACC_ABASE(PS, VS, + kh * H2)
 
   const int nph = Cin / CH;
   for (int p = 0; p < nph; ++p) {
     if (p) __syncthreads();  // every wave is done reading the previous phase's halo
     // ---- stage CH channels of the halo ------------------------------------------------------
     if (LAYOUT == 0) {
-      constexpr int PARTS = CH / 4, ITEMS = HY * HX * Z * PARTS, ITERS = (ITEMS + 255) / 256;
-      float4 v[ITERS];
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-        const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-          v[it] = *reinterpret_cast<const float4*>(inb + (((long)gy * X + gx) * Z + z) * Cin +
-                                                   p * CH + part * 4);
-      }
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-        if (idx < ITEMS)
-          *reinterpret_cast<float4*>(lds + pil * PS + (z + 1) * VS + part * 4) = v[it];
-      }
+      OCC_C3D_REQ_L0(p * CH + part * 4)
+      OCC_C3D_PUT_L0_F32
     } else {
-      constexpr int Z4 = Z / 4, ITEMS = HY * HX * CH * Z4, ITERS = (ITEMS + 255) / 256;
-      float4 v[ITERS];
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);
-        const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-          v[it] = *reinterpret_cast<const float4*>(inb + ((long)gy * X + gx) * Z * Cin +
-                                                   (long)(p * CH + ci) * Z + z4 * 4);
-      }
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);
-        if (idx < ITEMS) {
-          float* d = lds + pil * PS + (z4 * 4 + 1) * VS + ci;
-          d[0] = v[it].x; d[VS] = v[it].y; d[2 * VS] = v[it].z; d[3 * VS] = v[it].w;
-        }
-      }
+      OCC_C3D_REQ_L1(p * CH + ci)
+      OCC_C3D_PUT_L1_F32
     }
     __syncthreads();
 
@@ -173,22 +275,7 @@ __global__ __launch_bounds__(256) void conv3d_mfma_kernel(
   }
 
   // ---- epilogue: BN(eval) + ReLU, one 128-byte row per voxel ---------------------------------------
-  const float sc = scale[vi], sh = shift[vi];
-  float* outb = out + (long)b * out_sb;
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int gy = y0 + ty;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-      const int gx = x0 + txg * G::PX + row / Z, z = row % Z;
-      float v = fmaf(acc[a][r], sc, sh);
-      if (relu) v = fmaxf(v, 0.f);
-      if (gy < Y && gx < X) outb[gy * out_sy + gx * out_sx + z * 32 + vi] = v;
-    }
-  }
+  OCC_C3D_BN_RELU_STORE
 }
 
 // (Cout=32, Cin, 3, 3, 3) torch weight -> packed[p][t][kh][co][CH/2], channel = p*CH + kh*CH/2 + s,
@@ -318,98 +405,25 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(
   const float* inb = in + (long)b * Y * X * Z * Cin;
 
   // z-halo slots (z = -1 and z = Z) of every halo pillar stay zero for all phases
-  for (int i = tid; i < HY * HX * 2 * (VSB / 16); i += 256) {
-    const int pil = i / (2 * (VSB / 16)), rem = i % (2 * (VSB / 16));
-    const int part = rem % (VSB / 16);
-    *reinterpret_cast<uint4*>(ldsb + pil * PSB + (rem >= VSB / 16 ? (Z + 1) * VSB : 0) + part * 16) =
-        make_uint4(0u, 0u, 0u, 0u);
-  }
+  OCC_C3D_ZERO_ZHALO
 
-  f32x16 acc[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
-
-  const int vi = lane & 31, kh = lane >> 5;
-  int abase[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int px = txg * G::PX + vi / Z, z = vi % Z;
-    abase[a] = (ty * HX + px) * PSB + z * VSB + kh * 16;       // tap (0,0,0) = halo corner (-1,-1,-1), hi plane
-  }
+  OCC_C3D_ACC_ABASE(PSB, VSB, + kh * 16)
 
   const int nph = Cin / CH;
   // weight ring (conv_taps27): the first three taps are requested before anything else
   occ_u32x4 w[4][2];
   const __amdgpu_buffer_rsrc_t wr = uniform_rsrc(wp, (unsigned)nph * 27u * 2048u);
   const int wv = lane * 16, Tlast = nph * 27 - 1;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    const int tn = t < Tlast ? t : Tlast;
-    w[t][0] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, tn * 2048, 0);
-    w[t][1] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, tn * 2048 + 1024, 0);
-  }
+  OCC_C3D_WRING_REQ3(t < Tlast ? t : Tlast)
   for (int p = 0; p < nph; ++p) {
     if (p) block_lds_sync();  // every wave is done reading the previous phase's halo
     // ---- stage 16 channels of the halo, split into hi / lo bf16 -------------------------------------
     if (LAYOUT == 0) {
-      constexpr int PARTS = CH / 4, ITEMS = HY * HX * Z * PARTS, ITERS = (ITEMS + 255) / 256;
-      float4 v[ITERS];
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-        const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-          v[it] = *reinterpret_cast<const float4*>(inb + (((long)gy * X + gx) * Z + z) * Cin +
-                                                   p * CH + part * 4);
-      }
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-        if (idx < ITEMS) {
-          unsigned h01, h23, l01, l23;
-          bf16_split2(v[it].x, v[it].y, h01, l01);
-          bf16_split2(v[it].z, v[it].w, h23, l23);
-          char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;
-          *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
-          *reinterpret_cast<uint2*>(d + 32) = make_uint2(l01, l23);
-        }
-      }
+      OCC_C3D_REQ_L0(p * CH + part * 4)
+      OCC_C3D_PUT_L0_X3(32)
     } else {
-      constexpr int Z4 = Z / 4, ITEMS = HY * HX * CH * Z4, ITERS = (ITEMS + 255) / 256;
-      float4 v[ITERS];
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);
-        const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-          v[it] = *reinterpret_cast<const float4*>(inb + ((long)gy * X + gx) * Z * Cin +
-                                                   (long)(p * CH + ci) * Z + z4 * 4);
-      }
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);
-        if (idx < ITEMS) {
-          const float f[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-          char* d = ldsb + pil * PSB + (z4 * 4 + 1) * VSB + ci * 2;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            unsigned short hi, lo;
-            bf16_split(f[q], hi, lo);
-            *reinterpret_cast<unsigned short*>(d + q * VSB) = hi;
-            *reinterpret_cast<unsigned short*>(d + q * VSB + 32) = lo;
-          }
-        }
-      }
+      OCC_C3D_REQ_L1(p * CH + ci)
+      OCC_C3D_PUT_L1_X3(32)
     }
     block_lds_sync();
 
@@ -418,22 +432,7 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_kernel(
   }
 
   // ---- epilogue: BN(eval) + ReLU, one 128-byte row per voxel ---------------------------------------
-  const float sc = scale[vi], sh = shift[vi];
-  float* outb = out + (long)b * out_sb;
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int gy = y0 + ty;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-      const int gx = x0 + txg * G::PX + row / Z, z = row % Z;
-      float v = fmaf(acc[a][r], sc, sh);
-      if (relu) v = fmaxf(v, 0.f);
-      if (gy < Y && gx < X) outb[gy * out_sy + gx * out_sx + z * 32 + vi] = v;
-    }
-  }
+  OCC_C3D_BN_RELU_STORE
 }
 
 // ---- Cin = 8 on the bf16 matrix cores: TWO TAPS per MFMA step ---------------------------------------------------------
@@ -479,91 +478,21 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_c8_kernel(
   occ_u32x4 w[4][2];
   const __amdgpu_buffer_rsrc_t wr = uniform_rsrc(wp, 14u * 2048u);
   const int wv = lane * 16;
-#pragma unroll
-  for (int s = 0; s < 3; ++s) {
-    w[s][0] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, s * 2048, 0);
-    w[s][1] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, s * 2048 + 1024, 0);
-  }
+  OCC_C3D_WRING_REQ3(t)
 
-  for (int i = tid; i < HY * HX * 2 * (VSB / 16); i += 256) {          // z-halo slots stay zero
-    const int pil = i / (2 * (VSB / 16)), rem = i % (2 * (VSB / 16));
-    const int part = rem % (VSB / 16);
-    *reinterpret_cast<uint4*>(ldsb + pil * PSB + (rem >= VSB / 16 ? (Z + 1) * VSB : 0) + part * 16) =
-        make_uint4(0u, 0u, 0u, 0u);
-  }
+  OCC_C3D_ZERO_ZHALO                             // z-halo slots stay zero
   // ---- stage the 8 channels of the halo, split into hi / lo bf16 (one phase) --------------------------------------
   // (all requests first, then the conversions: as one loop hipcc waits for every load before it issues the next)
   if (LAYOUT == 0) {
-    constexpr int PARTS = CH / 4, ITEMS = HY * HX * Z * PARTS, ITERS = (ITEMS + 255) / 256;
-    float4 v[ITERS];
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-      const int idx = tid + it * 256;
-      const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-      const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-      v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-        v[it] = *reinterpret_cast<const float4*>(inb + (((long)gy * X + gx) * Z + z) * Cin + part * 4);
-    }
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-      const int idx = tid + it * 256;
-      const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-      if (idx < ITEMS) {
-        const float4 u = v[it];
-        unsigned h01, h23, l01, l23;
-        bf16_split2(u.x, u.y, h01, l01);
-        bf16_split2(u.z, u.w, h23, l23);
-        char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;
-        *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
-        *reinterpret_cast<uint2*>(d + 16) = make_uint2(l01, l23);
-      }
-    }
+    OCC_C3D_REQ_L0(part * 4)
+    OCC_C3D_PUT_L0_X3(16)
   } else {
-    constexpr int Z4 = Z / 4, ITEMS = HY * HX * CH * Z4, ITERS = (ITEMS + 255) / 256;
-    float4 v[ITERS];
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-      const int idx = tid + it * 256;
-      const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);
-      const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-      v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-        v[it] = *reinterpret_cast<const float4*>(inb + ((long)gy * X + gx) * Z * Cin + (long)ci * Z + z4 * 4);
-    }
-#pragma unroll
-    for (int it = 0; it < ITERS; ++it) {
-      const int idx = tid + it * 256;
-      const int z4 = idx % Z4, ci = (idx / Z4) % CH, pil = idx / (Z4 * CH);
-      if (idx < ITEMS) {
-        const float f[4] = {v[it].x, v[it].y, v[it].z, v[it].w};
-        char* d = ldsb + pil * PSB + (z4 * 4 + 1) * VSB + ci * 2;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          unsigned short hi, lo;
-          bf16_split(f[q], hi, lo);
-          *reinterpret_cast<unsigned short*>(d + q * VSB) = hi;
-          *reinterpret_cast<unsigned short*>(d + q * VSB + 16) = lo;
-        }
-      }
-    }
+    OCC_C3D_REQ_L1(ci)
+    OCC_C3D_PUT_L1_X3(16)
   }
   block_lds_sync();
 
-  f32x16 acc[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
-  const int vi = lane & 31, kh = lane >> 5;
-  int abase[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int px = txg * G::PX + vi / Z, z = vi % Z;
-    abase[a] = (ty * HX + px) * PSB + z * VSB;                 // tap (0,0,0) = halo corner (-1,-1,-1), hi plane
-  }
+  OCC_C3D_ACC_ABASE(PSB, VSB, )                  // no lane-half term: the halves are taps (OCC_C8_FRAG)
   // ---- 14 steps (tap pairs) x NACC accumulators x 3 MFMAs (small terms first, term-major), pinned like conv_taps27 -------
   constexpr auto toff_of = [](int t) { return ((((t / 3) % 3) * HX + t % 3) * PSB + (t / 9) * VSB); };
   int fo[NACC];                                  // this lane half's tap offset is a run-time select of two constants
@@ -604,116 +533,41 @@ __global__ __launch_bounds__(256) void conv3d_bf16x3_c8_kernel(
 #undef OCC_C8_FRAG
 
   // ---- epilogue: BN(eval) + ReLU, one 128-byte row per voxel ---------------------------------------
-  const float sc = scale[vi], sh = shift[vi];
-  float* outb = out + (long)b * out_sb;
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int gy = y0 + ty;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      const int row = (r & 3) + 8 * (r >> 2) + 4 * kh;
-      const int gx = x0 + txg * G::PX + row / Z, z = row % Z;
-      float v = fmaf(acc[a][r], sc, sh);
-      if (relu) v = fmaxf(v, 0.f);
-      if (gy < Y && gx < X) outb[gy * out_sy + gx * out_sx + z * 32 + vi] = v;
-    }
-  }
+  OCC_C3D_BN_RELU_STORE
 }
 
-template <int Z, int TY, int TX>
-static int launch_conv_x3_c8(const float* in, const void* wp, const float* scale, const float* shift, float* out, int B,
-                             int Y, int X, long out_sb, long out_sy, long out_sx, int relu, int layout, hipStream_t st) {
-  using G = ConvGeom<Z, 8, TY, TX>;
-  const int tiles_x = (X + TX - 1) / TX, tiles_y = (Y + TY - 1) / TY;
-  const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
-  const dim3 grid((unsigned)((long)B * tiles_x * tiles_y));
-  const uint4* w4 = reinterpret_cast<const uint4*>(wp);
-  hipError_t e;
-  if (layout == 0) {
-    auto k = conv3d_bf16x3_c8_kernel<Z, TY, TX, 0>;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, in, w4, scale, shift, out, Y, X, out_sb, out_sy, out_sx, relu,
-                         tiles_x, tiles_y);
-  } else {
-    auto k = conv3d_bf16x3_c8_kernel<Z, TY, TX, 1>;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, in, w4, scale, shift, out, Y, X, out_sb, out_sy, out_sx, relu,
-                         tiles_x, tiles_y);
-  }
-  if (e != hipSuccess) {
-    set_error("conv3d_bn_relu_bf16x3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    return OCC_E_LAUNCH;
-  }
-  OCC_CHECK_LAUNCH("conv3d_bn_relu_bf16x3");
-  return OCC_OK;
+// ---- host side: one tile table, one Z switch, one launch ------------------------------------------------------------------
+// Z -> pillars per block (TY x TX) of every kernel of this file: 16 -> 2 x 8, 32 -> 2 x 4 (8 row tiles, 2 accumulators per
+// wave), 8 and 4 -> 2 x 16 (8 / 4 row tiles).
+template <int Z>
+struct ConvBlock {
+  static constexpr int TY = 2, TX = Z == 32 ? 4 : Z == 16 ? 8 : 16;
+};
+template <int Z, int CH>
+constexpr size_t kConvLdsBytes = (size_t)ConvGeom<Z, CH, ConvBlock<Z>::TY, ConvBlock<Z>::TX>::LDS_FLOATS * sizeof(float);
+
+// The Z switch: f(std::integral_constant<int, Z>) for the run-time Z if it is one of Zs, the heights the caller has
+// kernels for.  (f is instantiated in the list's order, which is the order of the kernels in the code object.)
+template <int... Zs, class F>
+static int conv_for_z(int Z, F&& f) {
+  int rc = OCC_E_UNSUPPORTED;
+  (void)(... || (Z == Zs && ((rc = f(std::integral_constant<int, Zs>{})), true)));
+  return rc;
 }
 
-template <int Z, int TY, int TX>
-static int launch_conv_x3(const float* in, const void* wp, const float* scale, const float* shift,
-                          float* out, int B, int Y, int X, int Cin, long out_sb, long out_sy,
-                          long out_sx, int relu, int layout, hipStream_t st) {
-  using G = ConvGeom<Z, 16, TY, TX>;
+// One block of 256 threads per TY x TX pillars and batch entry, `lds` bytes of halo; `args` = the kernel's arguments in
+// front of (tiles_x, tiles_y).  `op` names the operation in the error text.
+template <class K, class... Args>
+static int conv_launch(K kernel, size_t lds, const char* op, int B, int Y, int X, int TY, int TX, hipStream_t st,
+                       Args... args) {
   const int tiles_x = (X + TX - 1) / TX, tiles_y = (Y + TY - 1) / TY;
-  const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
-  const dim3 grid((unsigned)((long)B * tiles_x * tiles_y));
-  const uint4* w4 = reinterpret_cast<const uint4*>(wp);
-  hipError_t e;
-  if (layout == 0) {
-    auto k = conv3d_bf16x3_kernel<Z, TY, TX, 0>;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, in, w4, scale, shift, out, Y, X, Cin, out_sb,
-                         out_sy, out_sx, relu, tiles_x, tiles_y);
-  } else {
-    auto k = conv3d_bf16x3_kernel<Z, TY, TX, 1>;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, in, w4, scale, shift, out, Y, X, Cin, out_sb,
-                         out_sy, out_sx, relu, tiles_x, tiles_y);
-  }
+  hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) {
-    set_error("conv3d_bn_relu_bf16x3: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
+    set_error("%s: hipFuncSetAttribute failed: %s", op, hipGetErrorString(e));
     return OCC_E_LAUNCH;
   }
-  OCC_CHECK_LAUNCH("conv3d_bn_relu_bf16x3");
-  return OCC_OK;
-}
-
-template <int Z, int CH, int TY, int TX>
-static int launch_conv(const float* in, const float* wp, const float* scale, const float* shift,
-                       float* out, int B, int Y, int X, int Cin, long out_sb, long out_sy,
-                       long out_sx, int relu, int layout, hipStream_t st) {
-  using G = ConvGeom<Z, CH, TY, TX>;
-  const int tiles_x = (X + TX - 1) / TX, tiles_y = (Y + TY - 1) / TY;
-  const size_t lds = (size_t)G::LDS_FLOATS * sizeof(float);
-  const dim3 grid((unsigned)((long)B * tiles_x * tiles_y));
-  hipError_t e;
-  if (layout == 0) {
-    auto k = conv3d_mfma_kernel<Z, CH, TY, TX, 0>;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, in, wp, scale, shift, out, Y, X, Cin, out_sb,
-                         out_sy, out_sx, relu, tiles_x, tiles_y);
-  } else {
-    auto k = conv3d_mfma_kernel<Z, CH, TY, TX, 1>;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e == hipSuccess)
-      hipLaunchKernelGGL(k, grid, dim3(256), lds, st, in, wp, scale, shift, out, Y, X, Cin, out_sb,
-                         out_sy, out_sx, relu, tiles_x, tiles_y);
-  }
-  if (e != hipSuccess) {
-    set_error("conv3d_bn_relu: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-    return OCC_E_LAUNCH;
-  }
-  OCC_CHECK_LAUNCH("conv3d_bn_relu");
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(256), lds, st, args..., tiles_x, tiles_y);
+  OCC_CHECK_LAUNCH(op);
   return OCC_OK;
 }
 
@@ -756,62 +610,18 @@ __global__ __launch_bounds__(256) void conv3d_heads_x3_kernel(
   const int b = tile.b, y0 = tile.y0, x0 = tile.x0;
   const float* inb = in + (long)b * Y * X * Z * Cin;
 
-  for (int i = tid; i < HY * HX * 2 * (VSB / 16); i += 256) {          // z-halo slots stay zero
-    const int pil = i / (2 * (VSB / 16)), rem = i % (2 * (VSB / 16));
-    const int part = rem % (VSB / 16);
-    *reinterpret_cast<uint4*>(ldsb + pil * PSB + (rem >= VSB / 16 ? (Z + 1) * VSB : 0) + part * 16) =
-        make_uint4(0u, 0u, 0u, 0u);
-  }
-  f32x16 acc[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[a][r] = 0.f;
-  const int vi = lane & 31, kh = lane >> 5;
-  int abase[NACC];
-#pragma unroll
-  for (int a = 0; a < NACC; ++a) {
-    const int rt = wave * NACC + a;
-    const int ty = rt / G::TXG, txg = rt % G::TXG;
-    const int px = txg * G::PX + vi / Z, z = vi % Z;
-    abase[a] = (ty * HX + px) * PSB + z * VSB + kh * 16;
-  }
+  OCC_C3D_ZERO_ZHALO
+  OCC_C3D_ACC_ABASE(PSB, VSB, + kh * 16)
   occ_u32x4 w[4][2];                          // weight ring (conv_taps27)
   const __amdgpu_buffer_rsrc_t wr = uniform_rsrc(wp, (unsigned)(Cin / CH) * 27u * 2048u);
   const int wv = lane * 16, Tlast = (Cin / CH) * 27 - 1;
-#pragma unroll
-  for (int t = 0; t < 3; ++t) {
-    w[t][0] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, t * 2048, 0);
-    w[t][1] = __builtin_amdgcn_raw_buffer_load_b128(wr, wv, t * 2048 + 1024, 0);
-  }
+  OCC_C3D_WRING_REQ3(t)
 #pragma unroll
   for (int p = 0; p < Cin / CH; ++p) {
     if (p) block_lds_sync();
     {
-      constexpr int PARTS = CH / 4, ITEMS = HY * HX * Z * PARTS, ITERS = (ITEMS + 255) / 256;
-      float4 v[ITERS];
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-        const int gy = y0 + pil / HX - 1, gx = x0 + pil % HX - 1;
-        v[it] = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (idx < ITEMS && gy >= 0 && gy < Y && gx >= 0 && gx < X)
-          v[it] = *reinterpret_cast<const float4*>(inb + (((long)gy * X + gx) * Z + z) * Cin + p * CH + part * 4);
-      }
-#pragma unroll
-      for (int it = 0; it < ITERS; ++it) {
-        const int idx = tid + it * 256;
-        const int part = idx % PARTS, z = (idx / PARTS) % Z, pil = idx / (PARTS * Z);
-        if (idx < ITEMS) {
-          unsigned h01, h23, l01, l23;
-          bf16_split2(v[it].x, v[it].y, h01, l01);
-          bf16_split2(v[it].z, v[it].w, h23, l23);
-          char* d = ldsb + pil * PSB + (z + 1) * VSB + part * 8;
-          *reinterpret_cast<uint2*>(d) = make_uint2(h01, h23);
-          *reinterpret_cast<uint2*>(d + 32) = make_uint2(l01, l23);
-        }
-      }
+      OCC_C3D_REQ_L0(p * CH + part * 4)
+      OCC_C3D_PUT_L0_X3(32)
     }
     block_lds_sync();
     conv_taps27<NACC, true, HX, PSB, VSB, 32>(acc, ldsb, abase, w, wr, wv, p * 27, Tlast);
@@ -926,22 +736,15 @@ extern "C" int occ_conv3d_bn_relu_f32(const float* in, const float* w_packed, co
     return OCC_E_UNSUPPORTED;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define OCC_CONV_CASE(ZZ, CC, TTY, TTX)                                                            \
-  if (Z == ZZ && CH == CC)                                                                         \
-    return launch_conv<ZZ, CC, TTY, TTX>(in, w_packed, scale, shift, out, B, Y, X, Cin,            \
-                                         (long)out_stride_b, (long)out_stride_y,                   \
-                                         (long)out_stride_x, relu, in_layout, st);
-  OCC_CONV_CASE(16, 16, 2, 8)
-  OCC_CONV_CASE(16, 8, 2, 8)
-  OCC_CONV_CASE(32, 16, 2, 4)
-  OCC_CONV_CASE(32, 8, 2, 4)
-  OCC_CONV_CASE(8, 16, 2, 16)
-  OCC_CONV_CASE(8, 8, 2, 16)
-  OCC_CONV_CASE(4, 16, 2, 16)
-  OCC_CONV_CASE(4, 8, 2, 16)
-#undef OCC_CONV_CASE
-  set_error("conv3d_bn_relu: no MFMA kernel for Z=%d CH=%d", Z, CH);
-  return OCC_E_UNSUPPORTED;
+  auto run = [&](auto z, auto ch) {
+    constexpr int ZZ = decltype(z)::value, CC = decltype(ch)::value, TY = ConvBlock<ZZ>::TY, TX = ConvBlock<ZZ>::TX;
+    auto k = in_layout == 0 ? conv3d_mfma_kernel<ZZ, CC, TY, TX, 0> : conv3d_mfma_kernel<ZZ, CC, TY, TX, 1>;
+    return conv_launch(k, kConvLdsBytes<ZZ, CC>, "conv3d_bn_relu", B, Y, X, TY, TX, st, in, w_packed, scale, shift, out, Y, X,
+                       Cin, (long)out_stride_b, (long)out_stride_y, (long)out_stride_x, relu);
+  };
+  return conv_for_z<16, 32, 8, 4>(Z, [&](auto z) {
+    return CH == 16 ? run(z, std::integral_constant<int, 16>{}) : run(z, std::integral_constant<int, 8>{});
+  });
 }
 
 extern "C" int occ_conv3d_pack_weight_bf16x3(const float* weight, void* packed, int Cin, int Cout,
@@ -983,29 +786,20 @@ extern "C" int occ_conv3d_bn_relu_bf16x3_f32(const float* in, const void* w_pack
     return OCC_E_UNSUPPORTED;
   }
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (Cin == 8) {
-#define OCC_CONV_C8(ZZ, TTY, TTX)                                                                  \
-    if (Z == ZZ)                                                                                   \
-      return launch_conv_x3_c8<ZZ, TTY, TTX>(in, w_packed, scale, shift, out, B, Y, X, (long)out_stride_b, \
-                                             (long)out_stride_y, (long)out_stride_x, relu, in_layout, st);
-    OCC_CONV_C8(32, 2, 4)
-    OCC_CONV_C8(16, 2, 8)
-    OCC_CONV_C8(8, 2, 16)
-    OCC_CONV_C8(4, 2, 16)
-#undef OCC_CONV_C8
-    return OCC_E_UNSUPPORTED;
-  }
-#define OCC_CONV_CASE(ZZ, TTY, TTX)                                                                \
-  if (Z == ZZ)                                                                                     \
-    return launch_conv_x3<ZZ, TTY, TTX>(in, w_packed, scale, shift, out, B, Y, X, Cin,             \
-                                        (long)out_stride_b, (long)out_stride_y,                    \
-                                        (long)out_stride_x, relu, in_layout, st);
-  OCC_CONV_CASE(16, 2, 8)
-  OCC_CONV_CASE(32, 2, 4)
-  OCC_CONV_CASE(8, 2, 16)
-  OCC_CONV_CASE(4, 2, 16)
-#undef OCC_CONV_CASE
-  return OCC_E_UNSUPPORTED;
+  const uint4* w4 = reinterpret_cast<const uint4*>(w_packed);
+  const long sb = (long)out_stride_b, sy = (long)out_stride_y, sx = (long)out_stride_x;
+  const char* op = "conv3d_bn_relu_bf16x3";
+  if (Cin == 8)              // two taps per MFMA step; the kernel takes no Cin
+    return conv_for_z<32, 16, 8, 4>(Z, [&](auto z) {
+      constexpr int ZZ = decltype(z)::value, TY = ConvBlock<ZZ>::TY, TX = ConvBlock<ZZ>::TX;
+      auto k = in_layout == 0 ? conv3d_bf16x3_c8_kernel<ZZ, TY, TX, 0> : conv3d_bf16x3_c8_kernel<ZZ, TY, TX, 1>;
+      return conv_launch(k, kConvLdsBytes<ZZ, 8>, op, B, Y, X, TY, TX, st, in, w4, scale, shift, out, Y, X, sb, sy, sx, relu);
+    });
+  return conv_for_z<16, 32, 8, 4>(Z, [&](auto z) {
+    constexpr int ZZ = decltype(z)::value, TY = ConvBlock<ZZ>::TY, TX = ConvBlock<ZZ>::TX;
+    auto k = in_layout == 0 ? conv3d_bf16x3_kernel<ZZ, TY, TX, 0> : conv3d_bf16x3_kernel<ZZ, TY, TX, 1>;
+    return conv_launch(k, kConvLdsBytes<ZZ, 16>, op, B, Y, X, TY, TX, st, in, w4, scale, shift, out, Y, X, Cin, sb, sy, sx, relu);
+  });
 }
 
 extern "C" int occ_conv3d_heads_pack(const float* w1_occ, const float* b1_occ, const float* w2_occ, const float* b2_occ,
@@ -1042,28 +836,14 @@ extern "C" int occ_conv3d_heads_decode_bf16x3_f32(const float* in, const void* w
     set_error("conv3d_heads_decode: no fused kernel for Z=%d Cin=%d num_classes=%d", Z, Cin, num_classes);
     return OCC_E_UNSUPPORTED;
   }
-  // Z = 16: 2 x 8 pillars per block (two pillars per 32-voxel row tile); Z = 32 (BASELINE configs[4]): 2 x 4 pillars,
-  // one pillar per row tile — the same 8 row tiles / 2 accumulators per wave, 66 KB of halo
-  auto launch = [&](auto k, int TY, int TX, size_t lds) -> int {
-    const int tiles_x = (X + TX - 1) / TX, tiles_y = (Y + TY - 1) / TY;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) {
-      set_error("conv3d_heads_decode: hipFuncSetAttribute failed: %s", hipGetErrorString(e));
-      return OCC_E_LAUNCH;
-    }
-    hipLaunchKernelGGL(k, dim3((unsigned)((long)B * tiles_x * tiles_y)), dim3(256), lds, reinterpret_cast<hipStream_t>(stream),
+  // Z = 16: two pillars per 32-voxel row tile; Z = 32 (BASELINE configs[4]): one pillar per row tile — the same 8 row
+  // tiles / 2 accumulators per wave, 66 KB of halo.  The class count is a compile-time constant for the reference's 17.
+  return conv_for_z<16, 32>(Z, [&](auto z) {
+    constexpr int ZZ = decltype(z)::value, TY = ConvBlock<ZZ>::TY, TX = ConvBlock<ZZ>::TX;
+    auto k = num_classes == 17 ? conv3d_heads_x3_kernel<ZZ, TY, TX, 17> : conv3d_heads_x3_kernel<ZZ, TY, TX, 0>;
+    return conv_launch(k, kConvLdsBytes<ZZ, 16>, "conv3d_heads_decode", B, Y, X, TY, TX, reinterpret_cast<hipStream_t>(stream),
                        in, reinterpret_cast<const uint4*>(w_packed), scale, shift,
                        reinterpret_cast<const uint4*>(heads_packed), occ_out, flow_out,
-                       reinterpret_cast<long long*>(occ_cls_out), Y, X, num_classes, tiles_x, tiles_y);
-    OCC_CHECK_LAUNCH("conv3d_heads_decode");
-    return OCC_OK;
-  };
-  if (Z == 16) {
-    if (num_classes == 17)
-      return launch(conv3d_heads_x3_kernel<16, 2, 8, 17>, 2, 8, (size_t)ConvGeom<16, 16, 2, 8>::LDS_FLOATS * sizeof(float));
-    return launch(conv3d_heads_x3_kernel<16, 2, 8, 0>, 2, 8, (size_t)ConvGeom<16, 16, 2, 8>::LDS_FLOATS * sizeof(float));
-  }
-  if (num_classes == 17)
-    return launch(conv3d_heads_x3_kernel<32, 2, 4, 17>, 2, 4, (size_t)ConvGeom<32, 16, 2, 4>::LDS_FLOATS * sizeof(float));
-  return launch(conv3d_heads_x3_kernel<32, 2, 4, 0>, 2, 4, (size_t)ConvGeom<32, 16, 2, 4>::LDS_FLOATS * sizeof(float));
+                       reinterpret_cast<long long*>(occ_cls_out), Y, X, num_classes);
+  });
 }

@@ -635,6 +635,9 @@ def conv3d_channel_block(cin):
 
 
 CONV3D_PRECISION = os.environ.get("OCC_CONV3D_PRECISION", "bf16x3")   # 'bf16x3' (default) or 'f32'
+# int16 elements of the packed bf16x3 weight for Cin = 8 (Cout = 32): that kernel contracts two taps per MFMA step, so the
+# 27 taps are 14 steps (the 28th tap is zero weights) x (hi, lo) planes x 2 lane halves x 32 output channels x 8 channels
+CONV3D_C8_PACKED_INT16 = 14 * 2 * 2 * 32 * 8
 
 
 def conv3d_pack_weight(weight, precision=None):
@@ -646,8 +649,7 @@ def conv3d_pack_weight(weight, precision=None):
     cout, cin = weight.shape[:2]
     precision = precision or CONV3D_PRECISION
     if precision == 'bf16x3' and (cin % 16 == 0 or (cin == 8 and cout == 32)):
-        # Cin = 8: two taps per MFMA step, 14 steps (the 28th tap is zero weights) -> 14 * 2 * 2 * 32 * 8 bf16
-        n16 = 14 * 2 * 2 * 32 * 8 if cin == 8 else weight.numel() * 2
+        n16 = CONV3D_C8_PACKED_INT16 if cin == 8 else weight.numel() * 2
         packed = torch.empty(n16, dtype=torch.int16, device=weight.device)
         with torch.cuda.device(weight.device):
             rc = _lib.lib().occ_conv3d_pack_weight_bf16x3(ptr(weight), ptr(packed), i32(cin), i32(cout),
@@ -676,7 +678,7 @@ def conv3d_bn_relu(x, w_packed, scale, shift, Z, Y, X, cin, cout, in_layout, out
     if not (w_packed.is_cuda and w_packed.is_contiguous() and (x3 or w_packed.dtype == torch.float32)):
         raise OccAmdError("conv3d_bn_relu: w_packed must come from conv3d_pack_weight")
     B = x.shape[0]
-    n_w = (14 * 2 * 2 * 32 * 8 if cin == 8 else cout * cin * 27 * 2) if x3 else cout * cin * 27
+    n_w = (CONV3D_C8_PACKED_INT16 if cin == 8 else cout * cin * 27 * 2) if x3 else cout * cin * 27
     if x.numel() != B * Y * X * Z * cin or w_packed.numel() != n_w \
             or scale.numel() != cout or shift.numel() != cout:
         raise OccAmdError("conv3d_bn_relu: inconsistent shapes")

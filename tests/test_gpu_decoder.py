@@ -31,6 +31,8 @@ CONV_CASES = [
     ("hires_z32_c32", 1, 32, 4, 7, 32),
     ("z8", 1, 8, 6, 19, 32),
     ("one_pillar", 1, 16, 1, 1, 16),
+    ("z8_c8", 1, 8, 3, 18, 8),                 # the Z = 8 instances of the 8-channel kernels (bf16x3 two-tap and f32)
+    ("z16_c24", 1, 16, 3, 9, 24),              # three phases of the f32 kernel's 8-channel geometry (no bf16x3 kernel)
 ]
 
 
@@ -143,9 +145,17 @@ def test_unsupported_shapes_raise_unsupported():
                       torch.randn(64).cuda(), torch.randn(2, 64).cuda(), torch.randn(2).cuda())
 
 
-@pytest.mark.parametrize("B,Y,X,Z", [(1, 9, 21, 16), (2, 7, 10, 16), (1, 1, 1, 16), (1, 16, 40, 16),
-                                     (1, 5, 9, 32), (2, 3, 4, 32), (1, 1, 1, 32)])
-def test_fused_conv_heads_decode_equals_two_launches(B, Y, X, Z):
+FUSED_CASES = [
+    # B, Y, X, Z, ncls   (17: the kernel's compile-time class count; any other count takes its run-time instances)
+    (1, 9, 21, 16, 17), (2, 7, 10, 16, 17), (1, 1, 1, 16, 17), (1, 16, 40, 16, 17),
+    (1, 5, 9, 32, 17), (2, 3, 4, 32, 17), (1, 1, 1, 32, 17),
+    (1, 3, 9, 16, 5), (1, 2, 5, 32, 5),
+]
+
+
+@pytest.mark.parametrize("B,Y,X,Z,ncls", FUSED_CASES,
+                         ids=["-".join(map(str, c[:4])) + ("" if c[4] == 17 else f"-ncls{c[4]}") for c in FUSED_CASES])
+def test_fused_conv_heads_decode_equals_two_launches(B, Y, X, Z, ncls):
     """occ_conv3d_heads_decode_bf16x3_f32 (second convolution + BN + ReLU + both heads + decode in one kernel; the
     convolution's output never reaches HBM) vs the two launches it replaces — conv3d_bn_relu(out_xy_major) then
     occ_heads(decode=True) — and vs the float64 oracle chain.  The fused kernel contracts the heads' first layer in a
@@ -153,7 +163,7 @@ def test_fused_conv_heads_decode_equals_two_launches(B, Y, X, Z):
     bit for bit (first index on ties).  Ragged tiles (Y, X not multiples of the 2 x 8 block tile), batch 2."""
     from occnet_amd import ext
     g = torch.Generator().manual_seed(61)
-    C, ncls = 32, 17                      # Z = 32: BASELINE configs[4] (2 x 4 pillars per block, one pillar per row tile)
+    C = 32                                # Z = 32: BASELINE configs[4] (2 x 4 pillars per block, one pillar per row tile)
     x = torch.randn(B, Y, X, Z, C, generator=g)
     w = torch.randn(C, C, 3, 3, 3, generator=g) * (2.0 / (C * 27)) ** 0.5
     bn = _bn(C, g)
