@@ -35,10 +35,10 @@
 // layout, so a corner is one 128-byte row per group; the channel sums are 3-step DPP/shuffle
 // reductions inside the 8-lane group.  Other D: one thread per (item, channel), mmcv's own shape,
 // with the channel sums reduced through LDS.
-#include <cstdlib>
-#include <string>
+#include <cstring>
 #include "gather_pieces.h"
 #include "msda_bwd_bins.h"
+#include "msda_bwd_pieces.h"
 
 namespace occ {
 
@@ -171,9 +171,7 @@ __global__ __launch_bounds__(256) void msda_bwd_d32_kernel(
 }
 
 // ---- counting sort of the bilinear row items into 32-pixel bins + owner-computes replay (file header) ------
-constexpr int kBinPix = 32;
-
-struct BwdItem { int qpl; float w0, w1; };            // (query << 5 | pixel in bin), left / right corner weight
+// (kBinPix, BwdItem and what the kernels of a pass share: msda_bwd_pieces.h)
 
 // counter[gbin] += 1 for every lane with `valid`, aggregated inside the wave: lanes that target the same bin are
 // served by ONE atomic of their leader (up to 4 rounds = 4 distinct bins, the rest individually).  The coarse FPN
@@ -227,32 +225,18 @@ __global__ __launch_bounds__(256) void msda_bwd_bin_kernel(
   const int q = (int)(qp / P), p = (int)(qp - (long)q * P);
   const long item = (b * Lq + q) * M + m;             // (b, q, m)
   const long si = (item * L + l) * P + p;
-  int binoff = 0, H = 0, W = 0;
-  for (int i = 0; i <= l; ++i) {
-    H = (int)shapes[2 * i]; W = (int)shapes[2 * i + 1];
-    if (i < l) binoff += (H * W + kBinPix - 1) / kBinPix;
-  }
+  OCC_BWD_LEVEL
   const unsigned char fl = nzflag[item];
   const float2 xy = *reinterpret_cast<const float2*>(loc + si * 2);
   const float a = attn[si];
   const BilinearTerms t = bilinear_terms(xy.x, xy.y, H, W, lane_flag(in_grid) & lane_flag(fl != 0));
-  const int ok = t.adm;
-  const int h_low = t.h_low, w_low = t.w_low;
-  const float lh = t.lh, lw = t.lw, hh = t.hh, hw = t.hw;
-  const int l_ok = lane_flag(w_low >= 0), r_ok = lane_flag(w_low + 1 <= W - 1);
-  const int both = l_ok & r_ok;
+  OCC_BWD_ROW_EDGES
   const int gbase = (int)((b * M + m) * (long)bins_per_bm) + binoff;
 #pragma unroll
   for (int r = 0; r < 2; ++r) {                       // top row, bottom row (wave-uniform control flow)
-    const int hy = h_low + r;
-    const int valid = ok & lane_flag(hy >= 0) & lane_flag(hy <= H - 1);
-    const float wy = (r ? lh : hh) * a;
-    const float wl = l_ok ? wy * hw : 0.f, wr = r_ok ? wy * lw : 0.f;
-    // left pixel (or the right one when the left is outside the map) decides the bin
-    const int pl = hy * W + (l_ok ? w_low : w_low + 1);
-    const int bin = valid ? pl / kBinPix : 0, in = pl - bin * kBinPix;
-    const int split = valid & both & lane_flag(in == kBinPix - 1);   // the pair straddles a bin edge: two single items
-    const float i0 = l_ok ? wl : wr, i1 = (both & (split ^ 1)) ? wr : 0.f;
+    int valid, bin, in, split;
+    float i0, i1, wr;
+    OCC_BWD_ROW_ITEM(r, valid, bin, in, split, i0, i1, wr)
     const int slot = bwd_agg_add<FILL>(counter, valid != 0, gbase + bin, lane);
     if (FILL && valid) items[slot] = BwdItem{(q << 5) | in, i0, i1};
     if (split) {                                      // 1 in 32: plain atomics
@@ -290,11 +274,7 @@ __global__ __launch_bounds__(kBinBlockThreads) void msda_bwd_bin_block_kernel(
   const int l = (int)(rest % L); rest /= L;
   const int m = (int)(rest % M);
   const long b = rest / M;
-  int binoff = 0, H = 0, W = 0;
-  for (int i = 0; i <= l; ++i) {
-    H = (int)shapes[2 * i]; W = (int)shapes[2 * i + 1];
-    if (i < l) binoff += (H * W + kBinPix - 1) / kBinPix;
-  }
+  OCC_BWD_LEVEL
   const int nb = (H * W + kBinPix - 1) / kBinPix;
   int* hist = bin_lds;
   int* gbase_of = bin_lds + nb;
@@ -328,30 +308,13 @@ __global__ __launch_bounds__(kBinBlockThreads) void msda_bwd_bin_block_kernel(
     live = lane_flag(in_grid) & lane_flag(fl != 0);
   }
   const BilinearTerms t = bilinear_terms(xy.x, xy.y, H, W, live);
-  const int ok = t.adm;
-  const int h_low = t.h_low, w_low = t.w_low;
-  const float lh = t.lh, lw = t.lw, hh = t.hh, hw = t.hw;
-  const int l_ok = lane_flag(w_low >= 0), r_ok = lane_flag(w_low + 1 <= W - 1);
-  const int both = l_ok & r_ok;
-
-  // same row items as msda_bwd_bin_kernel: per bilinear row one item at the left pixel's bin (two single items when
-  // the pair straddles a bin edge)
+  OCC_BWD_ROW_EDGES
   int valid[2], split[2];                              // 0 / 1 lane flags (common.h: lane_flag)
   int bin[2], in[2], slot[2], slot2[2];
-  float i0[2], i1[2], wr_[2];
+  float i0[2], i1[2], wr[2];
 #pragma unroll
   for (int r = 0; r < 2; ++r) {
-    const int hy = h_low + r;
-    valid[r] = ok & lane_flag(hy >= 0) & lane_flag(hy <= H - 1);
-    const float wy = (r ? lh : hh) * a;
-    const float wl = l_ok ? wy * hw : 0.f, wr = r_ok ? wy * lw : 0.f;
-    const int pl = hy * W + (l_ok ? w_low : w_low + 1);
-    bin[r] = valid[r] ? pl / kBinPix : 0;
-    in[r] = pl - bin[r] * kBinPix;
-    split[r] = valid[r] & both & lane_flag(in[r] == kBinPix - 1);
-    i0[r] = l_ok ? wl : wr;
-    i1[r] = (both & (split[r] ^ 1)) ? wr : 0.f;
-    wr_[r] = wr;
+    OCC_BWD_ROW_ITEM(r, valid[r], bin[r], in[r], split[r], i0[r], i1[r], wr[r])
     slot[r] = slot2[r] = 0;
     if (valid[r]) slot[r] = atomicAdd(&hist[bin[r]], 1);            // LDS
     if (split[r]) slot2[r] = atomicAdd(&hist[bin[r] + 1], 1);
@@ -370,7 +333,7 @@ __global__ __launch_bounds__(kBinBlockThreads) void msda_bwd_bin_block_kernel(
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       if (valid[r]) items[gbase_of[bin[r]] + slot[r]] = BwdItem{(q << 5) | in[r], i0[r], i1[r]};
-      if (split[r]) items[gbase_of[bin[r] + 1] + slot2[r]] = BwdItem{(q << 5) | 0, wr_[r], 0.f};
+      if (split[r]) items[gbase_of[bin[r] + 1] + slot2[r]] = BwdItem{(q << 5) | 0, wr[r], 0.f};
     }
   }
 }
@@ -467,66 +430,17 @@ __global__ __launch_bounds__(256) void msda_bwd_replay_kernel(
   constexpr int D = 32;
   __shared__ float acc_s[8][(kBinPix + 1) * D];        // per half-wave; +1 pixel: the w1 lane of pixel 31
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, ch = lane & 31;
-  if ((int)blockIdx.x >= work_count[0]) return;        // the grid is an upper bound of the work list
-  const int4 wk = work[blockIdx.x];
-  const long bin_g = wk.x;
-  const int beg = wk.y, end = wk.z;
+  OCC_BWD_WORK_ENTRY
   const bool shared_bin = wk.w != 0;                   // other blocks add into the same 32 pixels
   const int hw = wave * 2 + half;
   float* acc = acc_s[hw];
 #pragma unroll
   for (int i = 0; i <= kBinPix; ++i) acc[i * D + ch] = 0.f;
-  const long bm = bin_g / bins_per_bm;
-  int bl = (int)(bin_g - bm * bins_per_bm);
-  const int m = (int)(bm % M);
-  const long b = bm / M;
-  int l = 0, HW = 0;
-  for (; l < L; ++l) {
-    HW = (int)shapes[2 * l] * (int)shapes[2 * l + 1];
-    const int nb = (HW + kBinPix - 1) / kBinPix;
-    if (bl < nb) break;
-    bl -= nb;
-  }
-  if (l >= L) return;                                  // slack bins of the upper bound (never filled)
-  const float* go = grad_out + ((b / bdiv) * Lq * (long)M + m) * D + ch;        // + q * M * D (bdiv: msda_bwd_bins.h)
-  // 8 items per half-wave per step, software-pipelined over three steps: the item records of step i+2 and the
-  // output-gradient rows of step i+1 are in flight while step i is added into LDS (two dependent global loads per
-  // item made every step cost both latencies: ~1.5 us per 64 items and block)
-  int qA[8], qB[8], qC[8];
-  float w0A[8], w1A[8], w0B[8], w1B[8], w0C[8], w1C[8], gA[8], gB[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int i0 = beg + hw + 8 * u, i1 = i0 + 64;
-    const BwdItem a = items[i0 < end ? i0 : beg];
-    const BwdItem c = items[i1 < end ? i1 : beg];
-    qA[u] = i0 < end ? a.qpl : -1; w0A[u] = a.w0; w1A[u] = a.w1;
-    qB[u] = i1 < end ? c.qpl : -1; w0B[u] = c.w0; w1B[u] = c.w1;
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u) gA[u] = go[(long)(qA[u] < 0 ? 0 : qA[u] >> 5) * M * D];
-  for (int base = beg; base < end; base += 64) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {                      // item records two steps ahead
-      const int idx = base + 128 + hw + 8 * u;
-      const BwdItem it = items[idx < end ? idx : beg];
-      qC[u] = idx < end ? it.qpl : -1; w0C[u] = it.w0; w1C[u] = it.w1;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) gB[u] = go[(long)(qB[u] < 0 ? 0 : qB[u] >> 5) * M * D];   // rows one step ahead
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (qA[u] >= 0) {
-        const int pl = qA[u] & 31;
-        acc[pl * D + ch] += gA[u] * w0A[u];
-        acc[(pl + 1) * D + ch] += gA[u] * w1A[u];      // w1 == 0 for single items (pixel 32 is a dummy row)
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      qA[u] = qB[u]; w0A[u] = w0B[u]; w1A[u] = w1B[u]; gA[u] = gB[u];
-      qB[u] = qC[u]; w0B[u] = w0C[u]; w1B[u] = w1C[u];
-    }
-  }
+  OCC_BWD_BIN_REF
+  if (l >= L) return;                                   // slack bins of the upper bound (never filled)
+  const float* go = bwd_go_row(grad_out, b, bdiv, Lq, M, m, ch);
+  OCC_BWD_REPLAY_ITEMS(acc[pl * D + ch] += g * w0;
+                       acc[(pl + 1) * D + ch] += g * w1;)
   __syncthreads();
   // the 8 partial sums -> grad_value
   const int p0 = bl * kBinPix, np = min(kBinPix, HW - p0);
@@ -539,7 +453,7 @@ __global__ __launch_bounds__(256) void msda_bwd_replay_kernel(
       const float4 u = *reinterpret_cast<const float4*>(acc_s[k] + px * D + c4 * 4);
       sum.x += u.x; sum.y += u.y; sum.z += u.z; sum.w += u.w;
     }
-    float* dstf = grad_value + ((b * S + st + p0 + px) * M + m) * D + c4 * 4;
+    float* dstf = bwd_gv_row(grad_value, b * S + st + p0 + px, M, m) + c4 * 4;
     if (shared_bin) {                                  // a split bin: a few dozen blocks per bin at most
       unsafeAtomicAdd(dstf + 0, sum.x);
       unsafeAtomicAdd(dstf + 1, sum.y);
@@ -587,7 +501,7 @@ __global__ __launch_bounds__(256) void msda_bwd_det_zero_kernel(const int* __res
   for (int i = threadIdx.x; i < kDetSlotWords; i += 256) tiles[(long)slot * kDetSlotWords + i] = 0ull;
 }
 
-// Round 6: the loop of the default replay (item records two steps, gradient rows one step ahead) with 64-bit fixed-point sums:
+// Round 6: the loop of the default replay (OCC_BWD_REPLAY_ITEMS, msda_bwd_pieces.h) with 64-bit fixed-point sums:
 // ONE tile per block in LDS, accumulated with LDS integer atomics (ds_add_u64: fire and forget, any number of half-waves on
 // one pixel), and hot bins SPLIT like the default mode's — the pieces of split bin `slot` add their tiles into the slot's
 // scratch with 64-bit global atomics (integer addition commutes: no order reaches the result) and the piece that arrives
@@ -605,78 +519,32 @@ __global__ __launch_bounds__(256) void msda_bwd_replay_det_kernel(
   __shared__ int bad_px[kBinPix + 1];
   __shared__ int last_piece;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, half = lane >> 5, ch = lane & 31;
-  if ((int)blockIdx.x >= work_count[0]) return;
-  const int4 wk = work[blockIdx.x];
-  const long bin_g = wk.x;
-  const int beg = wk.y, end = wk.z;
+  OCC_BWD_WORK_ENTRY
   const int slot = wk.w - 1;                           // >= 0: one piece of a split bin
   const int hw = wave * 2 + half;
   for (int i = tid; i < (kBinPix + 1) * D; i += 256) acc_d[i] = 0ull;
   if (tid <= kBinPix) bad_px[tid] = 0;
   __syncthreads();
-  const long bm = bin_g / bins_per_bm;
-  int bl = (int)(bin_g - bm * bins_per_bm);
-  const int m = (int)(bm % M);
-  const long b = bm / M;
-  int l = 0, HW = 0;
-  for (; l < L; ++l) {
-    HW = (int)shapes[2 * l] * (int)shapes[2 * l + 1];
-    const int nb = (HW + kBinPix - 1) / kBinPix;
-    if (bl < nb) break;
-    bl -= nb;
-  }
-  if (l >= L) return;
+  OCC_BWD_BIN_REF
+  if (l >= L) return;   
   const float mx = __uint_as_float((unsigned)work_count[1]);           // max |grad_output| of the launch
   int e = 0;
   if (mx > 0.f) (void)frexpf(mx, &e);                                  // mx < 2^e
   const int sh = 40 - e;                                               // products scaled by 2^sh: |.| < 2^40, exact in fp32
   const double inv = ldexp(1.0, e - 40);
-  const float* go = grad_out + ((b / bdiv) * Lq * (long)M + m) * D + ch;        // + q * M * D (bdiv: msda_bwd_bins.h)
-  int qA[8], qB[8], qC[8];
-  float w0A[8], w1A[8], w0B[8], w1B[8], w0C[8], w1C[8], gA[8], gB[8];
-#pragma unroll
-  for (int u = 0; u < 8; ++u) {
-    const int i0 = beg + hw + 8 * u, i1 = i0 + 64;
-    const BwdItem a = items[i0 < end ? i0 : beg];
-    const BwdItem c = items[i1 < end ? i1 : beg];
-    qA[u] = i0 < end ? a.qpl : -1; w0A[u] = a.w0; w1A[u] = a.w1;
-    qB[u] = i1 < end ? c.qpl : -1; w0B[u] = c.w0; w1B[u] = c.w1;
-  }
-#pragma unroll
-  for (int u = 0; u < 8; ++u) gA[u] = go[(long)(qA[u] < 0 ? 0 : qA[u] >> 5) * M * D];
-  for (int base = beg; base < end; base += 64) {
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {                      // item records two steps ahead
-      const int idx = base + 128 + hw + 8 * u;
-      const BwdItem it = items[idx < end ? idx : beg];
-      qC[u] = idx < end ? it.qpl : -1; w0C[u] = it.w0; w1C[u] = it.w1;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) gB[u] = go[(long)(qB[u] < 0 ? 0 : qB[u] >> 5) * M * D];   // rows one step ahead
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      if (qA[u] >= 0) {
-        const int pl = qA[u] & 31;
-        const float c0 = gA[u] * w0A[u], c1 = gA[u] * w1A[u];
-        if (!(fabsf(c0) < 3.0e38f)) bad_px[pl] = 1;
-        else atomicAdd(&acc_d[pl * D + ch], (unsigned long long)__float2ll_rn(ldexpf(c0, sh)));
-        if (!(fabsf(c1) < 3.0e38f)) bad_px[pl + 1] = 1;
-        else atomicAdd(&acc_d[(pl + 1) * D + ch], (unsigned long long)__float2ll_rn(ldexpf(c1, sh)));
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      qA[u] = qB[u]; w0A[u] = w0B[u]; w1A[u] = w1B[u]; gA[u] = gB[u];
-      qB[u] = qC[u]; w0B[u] = w0C[u]; w1B[u] = w1C[u];
-    }
-  }
+  const float* go = bwd_go_row(grad_out, b, bdiv, Lq, M, m, ch);
+  OCC_BWD_REPLAY_ITEMS(const float c0 = g * w0, c1 = g * w1;
+                       if (!(fabsf(c0) < 3.0e38f)) bad_px[pl] = 1;
+                       else atomicAdd(&acc_d[pl * D + ch], (unsigned long long)__float2ll_rn(ldexpf(c0, sh)));
+                       if (!(fabsf(c1) < 3.0e38f)) bad_px[pl + 1] = 1;
+                       else atomicAdd(&acc_d[(pl + 1) * D + ch], (unsigned long long)__float2ll_rn(ldexpf(c1, sh)));)
   __syncthreads();
   const int p0 = bl * kBinPix, np = min(kBinPix, HW - p0);
   const long st = lstart[l];
   if (slot < 0) {                                      // the bin's only writer
     for (int i = tid; i < np * D; i += 256) {
       const int px = i >> 5, c = i & 31;
-      float* dst = grad_value + ((b * S + st + p0 + px) * M + m) * D + c;
+      float* dst = bwd_gv_row(grad_value, b * S + st + p0 + px, M, m) + c;
       if (bad_px[px]) *dst = __builtin_nanf("");
       else *dst += (float)((double)(long long)acc_d[px * D + c] * inv);
     }
@@ -698,7 +566,7 @@ __global__ __launch_bounds__(256) void msda_bwd_replay_det_kernel(
     const int px = i >> 5, c = i & 31;
     const unsigned long long bad = atomicAdd(&tile[kBinPix * D + px], 0ull);
     const long long sum = (long long)atomicAdd(&tile[i], 0ull);
-    float* dst = grad_value + ((b * S + st + p0 + px) * M + m) * D + c;
+    float* dst = bwd_gv_row(grad_value, b * S + st + p0 + px, M, m) + c;
     if (bad) *dst = __builtin_nanf("");
     else *dst += (float)((double)sum * inv);
   }
@@ -783,27 +651,60 @@ BwdWsLayout bwd_ws_layout(int B, int S, int M, int L, int Lq, int P) {
   w.n_bins = (long)B * M * w.bins_per_bm;
   w.n_samples = n_items * L * P;
   w.max_items = 4 * w.n_samples;                                      // 2 rows x (1 or 2 items)
-  w.off_cnt = ((size_t)n_items + 255) & ~(size_t)255;
-  w.off_cur = w.off_cnt + (((size_t)(w.n_bins + 1) * 4 + 255) & ~(size_t)255);
-  w.off_work = w.off_cur + (((size_t)(w.n_bins + 1) * 4 + 255) & ~(size_t)255);
+  const auto align256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  w.off_cnt = align256((size_t)n_items);
+  w.off_cur = w.off_cnt + align256((size_t)(w.n_bins + 1) * 4);
+  w.off_work = w.off_cur + align256((size_t)(w.n_bins + 1) * 4);
   w.work_cap = w.n_bins + w.max_items / kReplayCap + 1;               // >= sum_bins ceil(count / kReplayCap)
-  w.off_items = w.off_work + (((size_t)(w.work_cap + 1) * 16 + 255) & ~(size_t)255);   // [0] = entry count
+  w.off_items = w.off_work + align256((size_t)(w.work_cap + 1) * 16);   // [0] = entry count
   // deterministic mode: a split bin holds more than kReplayCap items, so there are at most max_items / kReplayCap of them;
   // per slot an arrival counter + piece count and a tile of kDetSlotWords 64-bit sums
   w.max_split = w.max_items / kReplayCap + 1;
-  w.off_meta = (w.off_items + (size_t)w.max_items * sizeof(BwdItem) + 255) & ~(size_t)255;
-  w.off_tiles = (w.off_meta + (size_t)w.max_split * 8 + 255) & ~(size_t)255;
-  w.off_aux = (w.off_tiles + (size_t)w.max_split * kDetSlotWords * 8 + 255) & ~(size_t)255;      // 3 ints per 1 024-bin scan block
+  w.off_meta = align256(w.off_items + (size_t)w.max_items * sizeof(BwdItem));
+  w.off_tiles = align256(w.off_meta + (size_t)w.max_split * 8);
+  w.off_aux = align256(w.off_tiles + (size_t)w.max_split * kDetSlotWords * 8);      // 3 ints per 1 024-bin scan block
   w.bytes = w.off_aux + 3 * 1024 * sizeof(int);
   w.ok = w.n_bins <= 1024L * 1024 && Lq < (1 << 26) && w.n_bins < (1L << 30) && w.max_items < (1L << 31) && w.work_cap < (1L << 31);
   return w;
 }
 
-bool bwd_block_bins_fit(int B, int S, int M, int L, int Lq, int P) {
-  const long blocks_per_bml = ((long)Lq * P + kBinBlockThreads - 1) / kBinBlockThreads;
-  const size_t lds_b = (size_t)(S / kBinPix + 2) * 2 * sizeof(int);
-  return lds_b <= 48 * 1024 && (long)B * M * L * blocks_per_bml < (1L << 31);
+// the launch of a block-aggregated binning pass: one block per 1024 (query, point) samples of a (batch, head, level), an LDS
+// histogram of >= 2 x the bins of the largest level; fits: within the LDS limit and the grid bound
+struct BinBlockGeom { long blocks_per_bml, grid; size_t lds_b; bool fits; };
+static BinBlockGeom bwd_block_bins_geom(int B, int S, int M, int L, int Lq, int P) {
+  BinBlockGeom g;
+  g.blocks_per_bml = ((long)Lq * P + kBinBlockThreads - 1) / kBinBlockThreads;
+  g.grid = (long)B * M * L * g.blocks_per_bml;
+  g.lds_b = (size_t)(S / kBinPix + 2) * 2 * sizeof(int);
+  g.fits = g.lds_b <= 48 * 1024 && g.grid < (1L << 31);
+  return g;
 }
+
+bool bwd_block_bins_fit(int B, int S, int M, int L, int Lq, int P) { return bwd_block_bins_geom(B, S, M, L, Lq, P).fits; }
+
+// One binning pass.  FILL == false: count the items into `counter` = counts; FILL == true: write them at `counter` = cursor.
+// Block-aggregated kernels (from the SCA source when `sca`), or the wave-aggregated ones when !block_bins.
+template <bool FILL>
+static void bwd_launch_bin_pass(const BwdWsLayout& w, const BinBlockGeom& g, bool block_bins, const ScaBinSource* sca,
+                                const int64_t* shapes, const float* loc, const float* attn, const unsigned char* flags,
+                                int* counter, BwdItem* items, int M, int L, int Lq, int P, hipStream_t st) {
+  if (block_bins) {
+    const ScaBinSource src = sca != nullptr ? *sca : ScaBinSource{nullptr, nullptr, nullptr, nullptr, 1, 1, 1};
+    const auto kernel = sca != nullptr ? msda_bwd_bin_block_kernel<FILL, true> : msda_bwd_bin_block_kernel<FILL, false>;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)g.grid), dim3(kBinBlockThreads), g.lds_b, st, shapes, loc, attn, flags, counter,
+                       items, M, L, Lq, P, w.bins_per_bm, (int)g.blocks_per_bml, src);
+  } else {
+    hipLaunchKernelGGL(msda_bwd_bin_kernel<FILL>, dim3((unsigned)((w.n_samples + 255) / 256)), dim3(256), 0, st, shapes, loc, attn,
+                       flags, counter, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
+  }
+}
+
+// OCC_MSDA_BWD_BIN=wave / OCC_MSDA_BWD_ATOMICS (set to anything): read per call, like bwd_deterministic (msda_bwd_bins.h)
+static bool bwd_wave_bins() {
+  const char* e = getenv("OCC_MSDA_BWD_BIN");
+  return e != nullptr && strcmp(e, "wave") == 0;
+}
+static bool bwd_value_atomics() { return getenv("OCC_MSDA_BWD_ATOMICS") != nullptr; }
 
 int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const int64_t* spatial_shapes,
                     const int64_t* level_start_index, const float* sampling_loc, const float* attn_weight,
@@ -815,32 +716,14 @@ int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const in
   BwdItem* items = reinterpret_cast<BwdItem*>(ws + w.off_items);
   int* work_count = reinterpret_cast<int*>(ws + w.off_work);
   int4* work = reinterpret_cast<int4*>(ws + w.off_work + 16);
-  const ScaBinSource src = sca != nullptr ? *sca : ScaBinSource{nullptr, nullptr, nullptr, nullptr, 1, 1, 1};
-  const int bdiv = sca != nullptr ? src.NC : loc_batch_div;
-  const dim3 grid_s((unsigned)((w.n_samples + 255) / 256));
+  const int bdiv = sca != nullptr ? sca->NC : loc_batch_div;
   // binning passes: block-aggregated (default) or the wave-aggregated kernels (OCC_MSDA_BWD_BIN=wave, or a
   // level with more bins than the LDS histogram holds); the SCA items exist in the block-aggregated form only (the
   // caller checked bwd_block_bins_fit)
-  static const bool wave_bins = getenv("OCC_MSDA_BWD_BIN") != nullptr &&
-                                std::string(getenv("OCC_MSDA_BWD_BIN")) == "wave";
-  const long qp_n = (long)Lq * P;
-  const long blocks_per_bml = (qp_n + kBinBlockThreads - 1) / kBinBlockThreads;
-  const long grid_b = (long)B * M * L * blocks_per_bml;
-  const size_t lds_b = (size_t)(S / kBinPix + 2) * 2 * sizeof(int);        // >= 2 * bins of the largest level
-  const bool block_bins = sca != nullptr || (!wave_bins && lds_b <= 48 * 1024 && grid_b < (1L << 31));
-  if (block_bins) {
-    if (sca != nullptr)
-      hipLaunchKernelGGL((msda_bwd_bin_block_kernel<false, true>), dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
-                         st, spatial_shapes, sampling_loc, attn_weight, flags, counts, items, M, L, Lq, P,
-                         w.bins_per_bm, (int)blocks_per_bml, src);
-    else
-      hipLaunchKernelGGL(msda_bwd_bin_block_kernel<false>, dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
-                         st, spatial_shapes, sampling_loc, attn_weight, flags, counts, items, M, L, Lq, P,
-                         w.bins_per_bm, (int)blocks_per_bml, src);
-  } else {
-    hipLaunchKernelGGL(msda_bwd_bin_kernel<false>, grid_s, dim3(256), 0, st, spatial_shapes, sampling_loc,
-                       attn_weight, flags, counts, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
-  }
+  const BinBlockGeom geom = bwd_block_bins_geom(B, S, M, L, Lq, P);
+  const bool block_bins = sca != nullptr || (!bwd_wave_bins() && geom.fits);
+  bwd_launch_bin_pass<false>(w, geom, block_bins, sca, spatial_shapes, sampling_loc, attn_weight, flags, counts, items, M, L,
+                             Lq, P, st);
   int* split_meta = reinterpret_cast<int*>(ws + w.off_meta);
   unsigned long long* tiles = reinterpret_cast<unsigned long long*>(ws + w.off_tiles);
   const int scan_blocks = (int)((w.n_bins + 1023) / 1024);
@@ -851,19 +734,8 @@ int bwd_bins_replay(const BwdWsLayout& w, char* ws, bool deterministic, const in
                      work_count);
   hipLaunchKernelGGL(msda_bwd_scan_kernel, dim3((unsigned)scan_blocks), dim3(1024), 0, st, counts, cursor, (int)w.n_bins, work,
                      scan_aux, kReplayCap, deterministic ? split_meta : nullptr);
-  if (block_bins) {
-    if (sca != nullptr)
-      hipLaunchKernelGGL((msda_bwd_bin_block_kernel<true, true>), dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
-                         st, spatial_shapes, sampling_loc, attn_weight, flags, cursor, items, M, L, Lq, P,
-                         w.bins_per_bm, (int)blocks_per_bml, src);
-    else
-      hipLaunchKernelGGL(msda_bwd_bin_block_kernel<true>, dim3((unsigned)grid_b), dim3(kBinBlockThreads), lds_b,
-                         st, spatial_shapes, sampling_loc, attn_weight, flags, cursor, items, M, L, Lq, P,
-                         w.bins_per_bm, (int)blocks_per_bml, src);
-  } else {
-    hipLaunchKernelGGL(msda_bwd_bin_kernel<true>, grid_s, dim3(256), 0, st, spatial_shapes, sampling_loc,
-                       attn_weight, flags, cursor, items, M, L, Lq, P, w.bins_per_bm, w.n_samples);
-  }
+  bwd_launch_bin_pass<true>(w, geom, block_bins, sca, spatial_shapes, sampling_loc, attn_weight, flags, cursor, items, M, L,
+                            Lq, P, st);
   if (deterministic) {
     const hipError_t ed = hipMemsetAsync(work_count + 1, 0, sizeof(int), st);
     if (ed != hipSuccess) {
@@ -923,11 +795,11 @@ extern "C" int occ_ms_deform_attn_backward_ws_f32(
   if (D == 32) {
     const long threads = n_items * 8;
     const dim3 grid1((unsigned)((threads + 255) / 256));
-    // atomic-free grad_value (file header): per-sample gradients + flags, count, scan, fill, replay
-    static const bool use_atomics = getenv("OCC_MSDA_BWD_ATOMICS") != nullptr;
-    // read per call (tests switch it inside one process): bit-reproducible grad_value, see msda_bwd_replay_det_kernel
-    const char* det_env = getenv("OCC_MSDA_BWD_DETERMINISTIC");
-    const bool deterministic = det_env != nullptr && det_env[0] == '1';
+    // atomic-free grad_value (file header): per-sample gradients + flags, count, scan, fill, replay.  The switches are
+    // read per call (tests flip them inside one process); deterministic: bit-reproducible grad_value, see
+    // msda_bwd_replay_det_kernel
+    const bool use_atomics = bwd_value_atomics();
+    const bool deterministic = bwd_deterministic();
     const BwdWsLayout w = bwd_ws_layout(B, S, M, L, Lq, P);
     char* ws = nullptr;
     bool own = false;
@@ -945,20 +817,18 @@ extern "C" int occ_ms_deform_attn_backward_ws_f32(
       }
     }
     if (e == hipSuccess) e = hipMemsetAsync(ws, 0, w.off_cur, st);      // flags + counts
+    int rc = OCC_OK;
     if (e == hipSuccess) {
       unsigned char* flags = reinterpret_cast<unsigned char*>(ws);
       hipLaunchKernelGGL(msda_bwd_d32_kernel<false>, grid1, dim3(256), 0, st, value, spatial_shapes,
                          level_start_index, sampling_loc, attn_weight, grad_output, grad_value,
                          grad_sampling_loc, grad_attn_weight, flags, S, M, L, Lq, P, n_items);
-      const int rc = bwd_bins_replay(w, ws, deterministic, spatial_shapes, level_start_index, sampling_loc, attn_weight,
-                                     nullptr, grad_output, n_items * 32, grad_value, B, S, M, L, Lq, P, st);
-      if (rc != OCC_OK) {
-        if (own) (void)hipFreeAsync(ws, st);
-        return rc;
-      }
-      if (own) (void)hipFreeAsync(ws, st);
-    } else {
-      if (own && ws) (void)hipFreeAsync(ws, st);
+      rc = bwd_bins_replay(w, ws, deterministic, spatial_shapes, level_start_index, sampling_loc, attn_weight,
+                           nullptr, grad_output, n_items * 32, grad_value, B, S, M, L, Lq, P, st);
+    }
+    if (own) (void)hipFreeAsync(ws, st);      // stream-ordered: behind the replay (or the failed set-up)
+    if (rc != OCC_OK) return rc;
+    if (e != hipSuccess) {
       (void)hipGetLastError();
       if (deterministic) {
         set_error("ms_deform_attn_backward: OCC_MSDA_BWD_DETERMINISTIC=1 needs the binned path (%.2f GB of scratch, "
@@ -979,12 +849,9 @@ extern "C" int occ_ms_deform_attn_backward_ws_f32(
                          grad_sampling_loc, grad_attn_weight, nullptr, S, M, L, Lq, P, n_items);
     }
   } else {
-    {
-      const char* det_env = getenv("OCC_MSDA_BWD_DETERMINISTIC");
-      if (det_env != nullptr && det_env[0] == '1') {     // the generic kernel sums with float atomics: say so, do not pretend
-        set_error("ms_deform_attn_backward: OCC_MSDA_BWD_DETERMINISTIC=1 exists for D = 32 only (D = %d)", D);
-        return OCC_E_UNSUPPORTED;
-      }
+    if (bwd_deterministic()) {       // the generic kernel sums with float atomics: say so, do not pretend
+      set_error("ms_deform_attn_backward: OCC_MSDA_BWD_DETERMINISTIC=1 exists for D = 32 only (D = %d)", D);
+      return OCC_E_UNSUPPORTED;
     }
     const int per_block = 256 / D > 0 ? 256 / D : 1;
     const int threads = per_block * D;

@@ -1,9 +1,17 @@
 // The binned, atomic-free grad_value machinery of msda_backward.hip (count -> scan -> fill -> replay, see its file header),
 // shared with the fused SCA backward (sca_fused_backward.hip).
 #pragma once
+#include <cstdlib>
 #include "common.h"
 
 namespace occ {
+
+// OCC_MSDA_BWD_DETERMINISTIC=1: the order-independent fixed-point replay (bit-identical grad_value from run to run).  Read per
+// call (tests switch it inside one process) by the msda, fused SCA and fused TSA backward.
+inline bool bwd_deterministic() {
+  const char* e = getenv("OCC_MSDA_BWD_DETERMINISTIC");
+  return e != nullptr && e[0] == '1';
+}
 
 struct BwdWsLayout { size_t off_cnt, off_cur, off_work, off_items, off_meta, off_tiles, off_aux, bytes; long n_bins, n_samples, max_items, work_cap, max_split; int bins_per_bm; bool ok; };
 // scratch of the binned path for B value batch entries of S pixels, M heads, L levels, Lq queries of P points each

@@ -175,8 +175,7 @@ extern "C" int occ_tsa_fused_backward_f32(const float* value, int64_t value_bt_s
   OCC_CHECK_ARG(workspace_bytes >= (int64_t)w.bytes && (reinterpret_cast<uintptr_t>(workspace) & 255) == 0,
                 "tsa_fused_backward: workspace too small (%ld < %ld bytes) or not 256-byte aligned", (long)workspace_bytes,
                 (long)w.bytes);
-  const char* det_env = getenv("OCC_MSDA_BWD_DETERMINISTIC");      // read per call, as the msda backward does
-  const bool deterministic = det_env != nullptr && det_env[0] == '1';
+  const bool deterministic = bwd_deterministic();                  // read per call, as the msda backward does
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   char* ws = reinterpret_cast<char*>(workspace);
   float* ws_loc = reinterpret_cast<float*>(ws + w.off_loc);

@@ -1,5 +1,8 @@
 """-m gpu: HIP `ms_deform_attn_backward` (through the C ABI and the autograd Function) vs the oracle
 (torch.autograd through the restated mmcv CPU function, float64)."""
+import functools
+
+import numpy as np
 import pytest
 import torch
 
@@ -31,26 +34,118 @@ def _interior(loc, shapes):
     return loc
 
 
-@pytest.mark.parametrize("name,B,shapes,M,D,Lq,P", CASES, ids=[c[0] for c in CASES])
-def test_backward_matches_autograd_oracle(name, B, shapes, M, D, Lq, P):
-    from occnet_amd import ext
+@functools.lru_cache(maxsize=None)
+def _case(name, B, shapes, M, D, Lq, P):
+    """Inputs, output gradient and float64 autograd gradients of one case: computed once, shared, never written to."""
+    shapes = [list(s) for s in shapes]
     value, shapes_t, start, loc, attn = _inputs(B, shapes, M, D, Lq, P, seed=5, adversarial=False)
     loc = _interior(loc, shapes)
     g = torch.Generator().manual_seed(6)
     grad_out = torch.randn(B, Lq, M * D, generator=g)
-    gv_ref, gl_ref, ga_ref = omsda.msda_backward_autograd(
-        value.double(), shapes_t, loc.double(), attn.double(), grad_out.double())
-    gv = torch.zeros_like(value).cuda()
-    gl = torch.zeros_like(loc).cuda()
-    ga = torch.zeros_like(attn).cuda()
+    refs = omsda.msda_backward_autograd(value.double(), shapes_t, loc.double(), attn.double(), grad_out.double())
+    return (value, shapes_t, start, loc, attn, grad_out), refs
+
+
+def _case_of(name):
+    name, B, shapes, M, D, Lq, P = next(c for c in CASES if c[0] == name)
+    return _case(name, B, tuple(tuple(s) for s in shapes), M, D, Lq, P)
+
+
+def _run_backward(inputs):
+    from occnet_amd import ext
+    value, shapes_t, start, loc, attn, grad_out = inputs
+    gv, gl, ga = (torch.zeros_like(t).cuda() for t in (value, loc, attn))
     ext.ms_deform_attn_backward(value.cuda(), shapes_t.cuda(), start.cuda(), loc.cuda(), attn.cuda(),
                                 grad_out.cuda(), gv, gl, ga, im2col_step=64)
     torch.cuda.synchronize()
-    for nm, got, ref in (("grad_value", gv, gv_ref), ("grad_loc", gl, gl_ref), ("grad_attn", ga, ga_ref)):
+    return gv, gl, ga
+
+
+def _assert_within_bound(name, got, refs):
+    for nm, g, ref in zip(("grad_value", "grad_loc", "grad_attn"), got, refs):
         scale = max(1.0, float(ref.abs().max()))
-        d = float((got.cpu().double() - ref).abs().max()) / scale
+        d = float((g.cpu().double() - ref).abs().max()) / scale
         print(f"{name} {nm}: max rel diff = {d:.3e} (scale {scale:.2f})")
         assert d < 1e-4, (name, nm, d)
+
+
+@pytest.mark.parametrize("name,B,shapes,M,D,Lq,P", CASES, ids=[c[0] for c in CASES])
+def test_backward_matches_autograd_oracle(name, B, shapes, M, D, Lq, P):
+    inputs, refs = _case_of(name)
+    _assert_within_bound(name, _run_backward(inputs), refs)
+
+
+# The smallest shape at which everything in the binned pipeline's shared pieces can go wrong (msda_bwd_pieces.h): the 15-pixel
+# level is ONE bin that collects ~600 * 8 * 2 row items per head, more than kReplayCap = 2048, so it is split; 240 pixels are
+# 7.5 bins, so the last bin is ragged; pixels 31 and 32 of the 20-wide map share a row, so pairs straddle a bin edge.
+PIECES_CASE = ("bin_pieces", 1, ((12, 20), (3, 5)), 2, 32, 600, 8)
+REPLAY_CAP, BIN_PIX = 2048, 32
+
+
+def _row_item_counts(loc, shapes):
+    """The row items as the binning kernels build them (one per admitted sample and bilinear row inside the map, at the bin
+    of its left pixel, or of the right one when the left is outside): (largest number of items in one (head, level, bin),
+    number of pairs that straddle a bin edge, items in the ragged last bin of level 0)."""
+    most = straddle = ragged = 0
+    M = loc.shape[2]
+    for l, (H, W) in enumerate(shapes):
+        xy = loc[:, :, :, l].numpy().astype(np.float32)                         # (B, Lq, M, P, 2)
+        w_im, h_im = xy[..., 0] * np.float32(W) - np.float32(0.5), xy[..., 1] * np.float32(H) - np.float32(0.5)
+        adm = (h_im > -1) & (w_im > -1) & (h_im < H) & (w_im < W)
+        h_low, w_low = np.floor(h_im).astype(np.int64), np.floor(w_im).astype(np.int64)
+        l_ok, r_ok = w_low >= 0, w_low + 1 <= W - 1
+        head = np.broadcast_to(np.arange(M)[None, None, :, None], adm.shape)
+        nb = (H * W + BIN_PIX - 1) // BIN_PIX
+        per_bin = np.zeros(M * nb, dtype=np.int64)
+        for r in (0, 1):
+            hy = h_low + r
+            valid = adm & (hy >= 0) & (hy <= H - 1)
+            pl = hy * W + np.where(l_ok, w_low, w_low + 1)
+            split = valid & l_ok & r_ok & (pl % BIN_PIX == BIN_PIX - 1)
+            per_bin += np.bincount((head * nb + pl // BIN_PIX)[valid], minlength=M * nb)
+            per_bin += np.bincount((head * nb + pl // BIN_PIX + 1)[split], minlength=M * nb)
+            straddle += int(split.sum())
+        most = max(most, int(per_bin.max()))
+        if l == 0:
+            ragged = int(per_bin.reshape(M, nb)[:, -1].sum())
+    return most, straddle, ragged
+
+
+def test_wave_binning_equals_block_binning(monkeypatch):
+    """The wave-aggregated binning kernels (OCC_MSDA_BWD_BIN=wave; also the fallback for a level whose histogram does not fit
+    the block-aggregated form) build their row items from the same piece as the default block-aggregated ones.  Fixed-point
+    accumulation is order-independent, so under OCC_MSDA_BWD_DETERMINISTIC=1 the two forms agree BIT FOR BIT exactly when they
+    emit the same item multiset; without it the wave form stays within the file's bound of the float64 oracle."""
+    inputs, refs = _case(*PIECES_CASE)
+    shapes = [list(s) for s in PIECES_CASE[2]]
+    most, straddle, ragged = _row_item_counts(inputs[3], shapes)
+    print(f"row items: {most} in the fullest bin (cap {REPLAY_CAP}), {straddle} straddling pairs, {ragged} in the ragged bins")
+    assert sum(h * w for h, w in shapes[:1]) % BIN_PIX != 0 and ragged > 0      # a ragged last bin that is used
+    assert most > REPLAY_CAP and straddle > 0                                    # a split bin, straddling pairs
+    monkeypatch.delenv("OCC_MSDA_BWD_ATOMICS", raising=False)
+    monkeypatch.delenv("OCC_MSDA_BWD_BIN", raising=False)
+    monkeypatch.setenv("OCC_MSDA_BWD_DETERMINISTIC", "1")
+    block = _run_backward(inputs)
+    monkeypatch.setenv("OCC_MSDA_BWD_BIN", "wave")
+    wave = _run_backward(inputs)
+    for nm, a, b in zip(("grad_value", "grad_loc", "grad_attn"), wave, block):
+        print(f"{nm}: wave vs block binning, elements that differ: {int((a != b).sum())}")
+        assert torch.equal(a, b), nm
+    _assert_within_bound("bin_pieces (block, deterministic)", block, refs)
+    monkeypatch.delenv("OCC_MSDA_BWD_DETERMINISTIC")
+    _assert_within_bound("bin_pieces (wave, default replay)", _run_backward(inputs), refs)
+
+
+@pytest.mark.parametrize("name", ["sca_like", "ragged_items"])
+def test_float_atomic_fallback_matches_autograd_oracle(name, monkeypatch):
+    """OCC_MSDA_BWD_ATOMICS=1: msda_bwd_d32_kernel<true>, the kernel a call falls back to when the scratch of the binned path
+    cannot be had.  (Its per-sample arithmetic is a loop of its own, not the default kernel's with atomics added - the default
+    takes four samples per step with unconditional loads and 1 - lh, this one skips a sample outside the map - so grad_loc /
+    grad_attn are held to the oracle, not to the default path's bits.)"""
+    inputs, refs = _case_of(name)
+    monkeypatch.delenv("OCC_MSDA_BWD_DETERMINISTIC", raising=False)
+    monkeypatch.setenv("OCC_MSDA_BWD_ATOMICS", "1")
+    _assert_within_bound(f"{name} (float atomics)", _run_backward(inputs), refs)
 
 
 def test_out_of_range_samples_have_zero_gradient():
