@@ -19,8 +19,8 @@ What the sweep ran and found on an MI355X (every mask under the reference bound 
       autocast chain's is 0.002 - 0.06) and gamma without W got no gradient: 8 of 15 masks (6 of 14) per case.  Fixed in
       ConvBNActFunction.backward.  Also found: ResNet ignored norm_cfg's requires_grad=False.  Fixed.
   SCAFusedFunction: 7 masks (value, offs, logits), 3 with offs / logits as slices of one leaf; bits.  Nothing found.
-  MultiScaleDeformableAttnFunction_fp32 / _fp16: 7 masks each (fp16 under autocast; it has no parity test of its own, its
-      bound is the fp32 node's plus one fp16 rounding, 2^-11); bits.  Nothing found.
+  MultiScaleDeformableAttnFunction_fp32 / _fp16: 7 masks each (fp16 under autocast; its bound here is the fp32 node's plus one fp16
+      rounding, 2^-11; its parity test is tests/test_gpu_msda_edges.py: .half() of the fp32 node bit for bit); bits.  Nothing found.
   Conv3dX3Function: 3 masks, both input layouts, x also as a view of a wider leaf; bits.  Nothing found.
   LinearX3Function: 7 masks with a bias, 3 without, with and without ReLU; bits.  Nothing found.
   LinearWgradFunction: 7 masks with a bias, 3 without (the output and dx are library GEMMs no parity test bounds: the fp32
