@@ -455,6 +455,10 @@ int occ_encoder_ffn_chain_bf16x3_f32(const float* a, int64_t lda, const float* r
 int occ_linear_pair_chain_bf16x3_f32(const float* a, int64_t lda, const void* w_chain, const float* bias_chain,
                                      const float* q_term, int64_t ldq_term, float* zq, int64_t ldzq, int nq,
                                      float* zv, int64_t ldzv, int M, void* stream);
+/* The tile split of the three chain programs, a pure host function: M rows on `slots` resident blocks (the launchers
+ * pass 2 x the CU count) -> blocks [0, nfull) own 64-row tiles, blocks [nfull, ntiles) 32-row tiles of the rows behind
+ * them.  32-row tiles appear only when the last round of 64-row tiles would fill at most half of the slots. */
+int occ_linear_chain_tile_split(int M, int slots, int* nfull, int* ntiles);
 
 /* Training path of SpatialCrossAttention, query side (csrc/sca_prep.hip; reference spatial_cross_attention.py:338-373
  * applied to the per-camera rebatched rows): from proj (B, Q, >= 3*M*L*P) = [sampling_offsets | attention_weights]

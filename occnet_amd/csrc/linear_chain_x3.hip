@@ -603,6 +603,21 @@ extern "C" int occ_linear_chain_pack_bf16x3(const float* weight, void* packed, i
   return OCC_OK;
 }
 
+// Tile split of the chain kernels (kernel comment above linear_chain_x3_kernel), a pure host function: M rows on `slots`
+// resident blocks -> blocks [0, nfull) own 64-row tiles, the rows behind them are cut into 32-row tiles; ntiles is the
+// grid.  The last, partial round of 64-row tiles becomes 32-row tiles when it would fill at most half of the slots.
+extern "C" int occ_linear_chain_tile_split(int M, int slots, int* nfull, int* ntiles) {
+  using namespace occ;
+  OCC_CHECK_ARG(nfull && ntiles, "linear_chain_tile_split: null pointer argument");
+  OCC_CHECK_ARG(M > 0 && slots > 0, "linear_chain_tile_split: bad dimension (M=%d slots=%d)", M, slots);
+  const int n64 = (int)(((long)M + kChRows - 1) / kChRows);
+  const int rem = n64 % slots;
+  *nfull = (n64 > slots && rem > 0 && 2 * rem <= slots) ? n64 - rem : n64;
+  const long rows_left = (long)M - (long)*nfull * kChRows;          // rows behind the 64-row tiles
+  *ntiles = *nfull + (rows_left > 0 ? (int)((rows_left + 31) / 32) : 0);
+  return OCC_OK;
+}
+
 namespace {
 template <int PROG>
 int chain_launch(const occ::ChainArgs& args_in, hipStream_t st, const char* what) {
@@ -621,19 +636,17 @@ int chain_launch(const occ::ChainArgs& args_in, hipStream_t st, const char* what
         return OCC_E_UNSUPPORTED;
       }
   }
-  // tile split (kernel comment): the last, partial round of 64-row tiles becomes 32-row tiles when it would fill less
-  // than half of the resident slots.  OCC_CHAIN_HALF_TILES=0 keeps 64-row tiles throughout (development).
+  // tile split: occ_linear_chain_tile_split on two resident blocks per CU.  OCC_CHAIN_HALF_TILES=0 keeps 64-row tiles
+  // throughout (development).
   static const int slots = [] {
     int dev = 0, n = 256;
     if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
     return 2 * n;
   }();
   static const bool half_tiles = env_default_on("OCC_CHAIN_HALF_TILES");
-  const int n64 = (args.M + kChRows - 1) / kChRows;
-  const int rem = n64 % slots;
-  args.nfull = (half_tiles && n64 > slots && rem > 0 && 2 * rem <= slots) ? n64 - rem : n64;
-  const long rows_left = (long)args.M - (long)args.nfull * kChRows;          // rows behind the 64-row tiles
-  const int ntiles = args.nfull + (rows_left > 0 ? (int)((rows_left + 31) / 32) : 0);
+  int ntiles = (args.M + kChRows - 1) / kChRows;
+  args.nfull = ntiles;
+  if (half_tiles) (void)occ_linear_chain_tile_split(args.M, slots, &args.nfull, &ntiles);
   void (*kern)(const ChainArgs) = linear_chain_x3_kernel<PROG, 0>;
   if (PROG == 0 && abl == 1) kern = linear_chain_x3_kernel<0, 1>;
   if (PROG == 0 && abl == 2) kern = linear_chain_x3_kernel<0, 2>;

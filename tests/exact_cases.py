@@ -16,9 +16,14 @@ hi + lo), the others are bf16-exact (|int| <= 8, low plane zero), so the dropped
 Each flavour fails exactly when the low-part product of ITS wide operand is missing.  The precondition of these cases is
 taken on |hi| + |lo| of the wide operand (the planes the kernel really multiplies).
 
-Out of scope (their transcendentals, divisions or square roots are not exact): the LayerNorm and Softplus epilogues, the
-linear_*_chain kernels, occ_heads, the BatchNorm statistics kernels and the heads-loss kernels.  The gather kernels
-already have float64 tests in every mode; bias_relu_maxpool_nhwc and bias_act_nhwc_ are already compared bit for bit."""
+The linear_*_chain kernels are covered stage by stage: linear_pair_chain as it stands, the tails of linear_ln_chain and
+encoder_ffn_chain and the latter's FFN behind a LayerNorm whose gamma is zero (its output is then the row beta, exactly).
+A LayerNorm itself is not exact: the chains' LayerNorms and the ln= epilogue of linear are checked on exact integer
+inputs under an error bound counted from the kernel source (tests/ln_bound.py).
+
+Out of scope (their transcendentals, divisions or square roots are not exact): the Softplus epilogue, occ_heads, the
+BatchNorm statistics kernels and the heads-loss kernels.  The gather kernels already have float64 tests in every mode;
+bias_relu_maxpool_nhwc and bias_act_nhwc_ are already compared bit for bit."""
 import functools
 
 import torch
@@ -26,7 +31,8 @@ import torch
 F = torch.nn.functional
 LIMIT = float(2 ** 24)
 
-MUTANTS = ("trunc", "half_away", "drop_k", "edge_pad", "skip_mid_round", "drop_low", "stride_off", "up_off", "trunc_in")
+MUTANTS = ("trunc", "half_away", "drop_k", "edge_pad", "skip_mid_round", "drop_low", "stride_off", "up_off", "trunc_in",
+           "term_last_group", "term_on_zv", "bias_pass0", "tile_copy", "no_relu", "no_x2")
 
 
 # ---- number formats --------------------------------------------------------------------------------------------------
@@ -701,6 +707,183 @@ def linear_wgrad_cases():
             for wide in LINEAR_WGRAD_FLAVOURS]
 
 
+# ---- linear_pair_chain, and the exact stages of linear_ln_chain / encoder_ffn_chain -------------------------------------------
+# Program C (linear_pair_chain) has no LayerNorm and is exact as it stands.  Programs A and B are exact behind a LayerNorm
+# whose gamma is zero: fmaf(d * rstd, 0, beta) = beta for any finite row, so the LayerNorm'd tile is the row beta, whatever
+# the (arbitrary, finite) operands in front of it.  That row is the operand of the next stage: the tail of A, the tail of
+# B (gamma2 = 0) and B's FFN (gamma1 = 0, up to the second LayerNorm: its input pre2 is an exact integer, its output is
+# checked under the derived bound of tests/ln_bound.py).  The references of the gamma = 0 cases are one row, broadcast.
+
+CHAIN_M_SMALL = (1, 63, 65)            # one ragged tile, and one row into the second
+CHAIN_M_FULL = 8229                    # 128 full 64-row tiles + a ragged one: blockIdx >> 3 takes all 16 k-step rotations
+CHAIN_NQ = (64, 128, 192, 256)
+CHAIN_N2 = (32, 96, 224, 288, 768, 1280)          # n2 % 64 == 32 (half-wave store masks), one .. five passes
+CHAIN_PAIR_FLAVOURS = ("a", "w")
+CHAIN_TAIL_FLAVOURS = ("beta", "w")
+WIDE10 = 1023                          # weights against the 256 DISTINCT bf16-exact beta values (-128 .. 127)
+CHAIN_MUTANTS = ("term_last_group", "term_on_zv", "bias_pass0", "tile_copy")
+
+
+def chain_m_half(cus=256):
+    """Rows that reach the 32-row tiles of the chain kernels on a device of `cus` CUs (two resident blocks each):
+    2 * cus full tiles, then 129 half tiles, the last with one row: all 16 rotations on 32-row tiles."""
+    return 64 * 2 * cus + 32 * 128 + 1
+
+
+def _distinct(g, wide):
+    """256 distinct integers: 12-bit ones (wide), or a permutation of -128 .. 127 (all bf16-exact)."""
+    if wide:
+        return (torch.randperm(2 * WIDE12 + 1, generator=g)[:256] - WIDE12).double()
+    return (torch.randperm(256, generator=g) - 128).double()
+
+
+def _noise(g, *shape):
+    """Arbitrary finite fp32 operands of the stages in front of a gamma = 0 LayerNorm."""
+    return torch.randint(-50, 51, tuple(shape), generator=g).float()
+
+
+def _pair_core(x, c, mut, x_name):
+    """[x . Wq^T (+ term) | x . Wv^T + bv] for x (R, 256), R = 1 (broadcast) or M -> (zq | zv, abs-sum)."""
+    wide, nq, term = c["wide"], c["wq"].shape[0], c["term"]
+    xw = _wide(x, mut) if wide == x_name else x
+    wq, wv = c["wq"], c["wv"]
+    if wide == "w":
+        wq, wv = _wide(wq, mut), _wide(wv, mut)
+    else:
+        wv = _drop_k(wv, mut)
+    zq, zv = xw @ wq.t(), xw @ wv.t() + c["bv"]
+    sx = split_abs(x)
+    aq, av = sx @ split_abs(c["wq"]).t(), sx @ split_abs(c["wv"]).t() + c["bv"].abs()
+    if term is not None:
+        t = term
+        if mut == "term_last_group":                 # MUTANT: the last 64-column group of zq misses its term
+            t = term.clone()
+            t[:, nq - 64:] = 0.0
+        zq, aq = zq + t, aq + term.abs()
+        if mut == "term_on_zv":                      # MUTANT: the term is added to the value columns as well
+            zv = zv.expand(term.shape[0], 256).clone()
+            zv[:, :nq] += term
+    M = c["M"]
+    return torch.cat([zq.expand(M, nq), zv.expand(M, 256)], 1), torch.cat([aq.expand(M, nq), av.expand(M, 256)], 1)
+
+
+def _pair_fn(c, mut=None):
+    z, ab = _pair_core(c["a"], c, mut, "a")
+    _f32(z)
+    return Ref(z, z, z, [("pair", ab)], False)
+
+
+def pair_chain_case(M, nq, term, wide):
+    """Program C.  Expected output: [zq | zv] (M, nq + 256)."""
+    g = _gen("pair_chain", M, nq, term, wide)
+    wamp = WIDE12 if wide == "w" else NARROW
+    inp = dict(a=ints(g, (M, 256), WIDE12 if wide == "a" else NARROW), wq=ints(g, (nq, 256), wamp),
+               wv=ints(g, (256, 256), wamp), bv=ints(g, (256,), 1000), term=ints(g, (M, nq), 100000) if term else None,
+               wide=wide, M=M)
+    return Case(("pair_chain", M, nq, int(term), wide), inp, _pair_fn)
+
+
+def _tail_b_fn(c, mut=None):
+    z, ab = _pair_core(c["beta"][None], c, mut, "beta")
+    _f32(z)
+    return Ref(z, z, z, [("tail", ab)], False, extra=dict(y=c["beta"][None].expand(c["M"], 256)))
+
+
+def tail_b_case(M, nq, term, wide):
+    """Program B with gamma2 = 0: y = beta2 in every row, [zq | zv] = [beta2 . Wq^T + term | beta2 . Wv^T + bv].  The
+    stages in front (output_proj, LayerNorm 1, FFN) run on arbitrary finite operands."""
+    g = _gen("tail_b", M, nq, term, wide)
+    wamp = WIDE10 if wide == "w" else NARROW
+    inp = dict(beta=_distinct(g, wide == "beta"), wq=ints(g, (nq, 256), wamp), wv=ints(g, (256, 256), wamp),
+               bv=ints(g, (256,), 1000), term=ints(g, (M, nq), 100000) if term else None, wide=wide, M=M,
+               a=_noise(g, M, 256), res=_noise(g, M, 256), wo=ints(g, (256, 256), 2).float(), bo=_noise(g, 256),
+               g1=torch.randint(1, 4, (256,), generator=g).float(), be1=_noise(g, 256) / 16,
+               w1=ints(g, (512, 256), 2).float(), b1=_noise(g, 512), w2=ints(g, (256, 512), 2).float(), b2=_noise(g, 256))
+    return Case(("tail_b", M, nq, int(term), wide), inp, _tail_b_fn)
+
+
+def _tail_a_fn(c, mut=None, relu=False):
+    wide, n2 = c["wide"], c["w2"].shape[0]
+    beta = c["beta"][None]
+    bw = _wide(beta, mut) if wide == "beta" else beta
+    w2 = _wide(c["w2"], mut) if wide == "w" else _drop_k(c["w2"], mut)
+    b2 = c["b2"]
+    if mut == "bias_pass0":                          # MUTANT: the passes behind the first take the first pass's biases
+        b2 = b2.clone()
+        b2[256:] = torch.cat([c["b2"][:256]] * 5)[:n2 - 256]
+    pre = bw @ w2.t() + b2
+    ab = split_abs(beta) @ split_abs(c["w2"]).t() + c["b2"].abs()
+    value = pre.relu() if relu else pre
+    if mut == "tile_copy":                           # MUTANT: the last stored 32-column tile is a copy of the one before it
+        value = value.clone()
+        value[:, n2 - 32:] = value[:, n2 - 64:n2 - 32]
+    _f32(value)
+    M = c["M"]
+    return Ref(pre, value, value.expand(M, n2), [("tail", ab)], relu, extra=dict(y=beta.expand(M, 256)))
+
+
+def tail_a_case(M, n2, wide):
+    """Program A with gamma = 0: y = beta in every row, z = act2(beta . W2^T + b2)."""
+    g = _gen("tail_a", M, n2, wide)
+    inp = dict(beta=_distinct(g, wide == "beta"), w2=ints(g, (n2, 256), WIDE10 if wide == "w" else NARROW),
+               b2=ints(g, (n2,), 1000), wide=wide, M=M, a=_noise(g, M, 256), res=_noise(g, M, 256),
+               w1=ints(g, (256, 256), 2).float(), b1=_noise(g, 256))
+    return Case(("tail_a", M, n2, wide), inp, _tail_a_fn)
+
+
+FFN_B1_SHIFT = 300           # b1 = +-1000 + 300: 40 % negative pre-activations, and a third of h = relu(.) needs its low plane
+
+
+def _ffn_fn(c, mut=None):
+    """x2 = beta1;  h = relu(x2 . W1^T + b1);  pre2 = h . W2^T + b2 + x2: the exact input of the second LayerNorm."""
+    x2 = c["beta1"][None]
+    hpre = x2 @ c["w1"].t() + c["b1"]
+    h_true = hpre.relu()
+    h = hpre if mut == "no_relu" else h_true          # MUTANT no_relu: the hidden activation keeps its negative values
+    h = _wide(h, mut)
+    w2 = c["w2"]
+    if mut == "drop_k":                              # MUTANT: the first live contraction element of output column 0 is dropped
+        w2 = w2.clone()
+        w2[0, int(((h_true[0] > 0) & (w2[0] != 0)).nonzero()[0])] = 0.0
+    pre2 = h @ w2.t() + c["b2"]
+    if mut != "no_x2":                               # MUTANT no_x2: the FFN's residual is missing
+        pre2 = pre2 + x2
+    a1 = x2.abs() @ c["w1"].abs().t() + c["b1"].abs()
+    a2 = split_abs(h_true) @ c["w2"].abs().t() + c["b2"].abs() + x2.abs()
+    _f32(pre2)
+    return Ref(hpre, pre2, pre2.expand(c["M"], 256), [("ffn1", a1), ("ffn2", a2)], True, extra=dict(h=h_true))
+
+
+def ffn_case(M):
+    """Program B with gamma1 = 0 and no tail, exact up to the second LayerNorm.  W2 is +-2: |pre2| stays below 2^16, so
+    the deviations from the row mean (multiples of 2^-8) are fp32 values too."""
+    g = _gen("ffn_b", M)
+    inp = dict(beta1=ints(g, (256,), NARROW), w1=ints(g, (512, 256), NARROW), b1=ints(g, (512,), 1000) + FFN_B1_SHIFT,
+               w2=ints(g, (256, 512), 2), b2=ints(g, (256,), 1000), M=M,
+               g2=(torch.rand(256, generator=g) + 0.5) * (torch.randint(0, 2, (256,), generator=g) * 2 - 1).float(),
+               be2=torch.randn(256, generator=g), a=_noise(g, M, 256), res=_noise(g, M, 256),
+               wo=ints(g, (256, 256), 2).float(), bo=_noise(g, 256))
+    return Case(("ffn_b", M), inp, _ffn_fn)
+
+
+@functools.lru_cache(maxsize=None)
+def chain_host_cases():
+    """(case, reference keywords) the host tests build: every flavour / width / term combination at the small M, and one
+    case per program at the two tall M (the operands of a row do not depend on M; the references of the gamma = 0
+    programs are one row)."""
+    tall = (CHAIN_M_FULL, chain_m_half())
+    out = []
+    for M in (1, 65):
+        out += [(pair_chain_case(M, nq, t, w), {}) for nq in CHAIN_NQ for t in (False, True) for w in CHAIN_PAIR_FLAVOURS]
+        out += [(tail_b_case(M, nq, t, w), {}) for nq in CHAIN_NQ for t in (False, True) for w in CHAIN_TAIL_FLAVOURS]
+        out += [(tail_a_case(M, n2, w), dict(relu=r)) for n2 in CHAIN_N2 for w in CHAIN_TAIL_FLAVOURS for r in (False, True)]
+        out.append((ffn_case(M), {}))
+    out += [(pair_chain_case(M, 192, True, "a"), {}) for M in tall]
+    out += [(tail_b_case(M, 192, True, "beta"), {}) for M in tall]
+    out += [(tail_a_case(M, 288, "beta"), dict(relu=True)) for M in tall]
+    return out
+
+
 # ---- conv1x1_wgrad_nhwc, conv3x3_wgrad_nhwc, bias_act_bwd_nhwc --------------------------------------------------------------
 
 CONV_WGRAD_CHANNELS = [(32, 32), (128, 64), (64, 256)]          # (Cin, Cout)
@@ -798,6 +981,18 @@ def mutant_table():
         (linear_wgrad_case(1, 100, 48, "dy"), {}, ("drop_low",)),
         (linear_wgrad_case(1, 100, 48, "x"), {}, ("drop_low",)),
         (linear_wgrad_case(257, 100, 48, "x"), {}, ("drop_low", "drop_k")),
+        (pair_chain_case(1, 64, True, "a"), {}, ("drop_low", "drop_k", "term_last_group", "term_on_zv")),
+        (pair_chain_case(1, 64, True, "w"), {}, ("drop_low",)),
+        (tail_b_case(1, 64, True, "beta"), {}, ("drop_low", "drop_k", "term_last_group", "term_on_zv")),
+        (tail_b_case(1, 64, True, "w"), {}, ("drop_low",)),
+        (tail_a_case(1, 32, "beta"), dict(relu=False), ("drop_low", "drop_k")),
+        (tail_a_case(1, 32, "w"), dict(relu=False), ("drop_low",)),
+        (tail_a_case(1, 96, "beta"), dict(relu=True), ("tile_copy",)),          # n2 % 64 == 32 with a tile in front of the last
+        (tail_a_case(1, 288, "beta"), dict(relu=False), ("bias_pass0",)),       # the smallest n2 with a second pass
+        # encoder_ffn_chain's FFN: pre2, the input of the second LayerNorm, is what these change.  The kernel's output is
+        # LayerNorm(pre2), so on the device drop_low and drop_k, like no_relu and no_x2 (the hidden ReLU or the FFN's
+        # residual missing), are killed through the derived bound on y, not bit-wise: tests/test_ln_bound_host.py
+        (ffn_case(1), {}, ("drop_low", "drop_k", "no_relu", "no_x2")),
         (conv_wgrad_case(1, 1, 32, 32, 1, 1, 1), dict(bf16=True), rounding),
         (conv_wgrad_case(1, 2, 32, 32, 2, 9, 13), dict(bf16=True), rounding + ("drop_k", "stride_off")),
         (conv_wgrad_case(3, 1, 32, 32, 1, 1, 1), dict(bf16=True), rounding + ("edge_pad",)),
@@ -822,6 +1017,7 @@ def fp32_cases():
     out += [(c, {}) for c in conv3d_autograd_cases() + linear_cases() + value_proj_cases() + linear_wgrad_cases()]
     out += [(c, dict(bf16=False)) for k in (1, 3) for c in conv_wgrad_cases(k)]
     out += [(c, dict(relu=r)) for c in bias_act_bwd_cases() for r in (True, False)]
+    out += chain_host_cases()
     return out
 
 
@@ -837,4 +1033,11 @@ def wide_operands():
         out.append((c, c.inp["w"] if c.inp["wide"] == "w" else a))
     out += [(c, c.inp["w"]) for c in value_proj_cases()]
     out += [(c, c.inp[c.inp["wide"]]) for c in linear_wgrad_cases()]
+    for c, kw in chain_host_cases():
+        if c.key[0] == "ffn_b":
+            out.append((c, c.ref().extra["h"]))          # the hidden activation: the kernel splits it itself
+        elif kw.get("relu", False) is False:             # (the ReLU twin of a tail case has the same operands)
+            w = c.inp["wide"]
+            out.append((c, torch.cat([c.inp["wq"], c.inp["wv"]]) if w == "w" and "wq" in c.inp else
+                        c.inp["w2"] if w == "w" else c.inp[w]))
     return out

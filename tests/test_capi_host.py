@@ -241,3 +241,85 @@ def test_round6_training_nodes_validate_without_gpu():
     assert np.array_equal(got, h)
     keep = (h[:4096] >= np.uint32(int(0.1 * 4294967296.0))).mean()
     assert abs(keep - 0.9) < 0.03
+
+
+CHAIN_SLOTS = (2, 16, 208, 512, 608)
+
+
+def _chain_split(M, slots):
+    nfull, ntiles = ctypes.c_int(-1), ctypes.c_int(-1)
+    assert _lib.lib().occ_linear_chain_tile_split(M, slots, ctypes.byref(nfull), ctypes.byref(ntiles)) == 0
+    return nfull.value, ntiles.value
+
+
+@pytest.mark.parametrize("slots", CHAIN_SLOTS)
+def test_linear_chain_tile_split_covers_every_row_once(slots):
+    """occ_linear_chain_tile_split, the pure function behind the launch of the three chain programs: blocks [0, nfull) own
+    64-row tiles, blocks [nfull, ntiles) 32-row tiles of the rows behind them (the kernel's own block -> row formula)."""
+    # every boundary: around each multiple of 32 and 64 rows up to three rounds of tiles, and around the rounds themselves
+    edges = set(range(1, 200))
+    for r in range(0, 3 * slots + 3):
+        edges.update(64 * r + d for d in (-33, -32, -31, -1, 0, 1, 31, 32, 33))
+    for n64 in (slots, slots + 1, slots + slots // 2, slots + slots // 2 + 1, 2 * slots, 2 * slots + 1, 3 * slots - 1):
+        edges.update(64 * n64 + d for d in (-64, -63, -1, 0, 1, 63, 64))
+    halves = 0
+    for M in sorted(m for m in edges if m > 0):
+        nfull, ntiles = _chain_split(M, slots)
+        n64 = (M + 63) // 64
+        rem = n64 % slots
+        half = n64 > slots and 0 < 2 * rem <= slots
+        assert nfull == (n64 - rem if half else n64), (M, slots)
+        # the tiles as the kernel walks them
+        tiles = [(64 * b, 64) for b in range(nfull)] + [(64 * nfull + 32 * (b - nfull), 32) for b in range(nfull, ntiles)]
+        assert tiles[0][0] == 0 and all(t[0] + t[1] == u[0] for t, u in zip(tiles, tiles[1:])), (M, slots)      # no gap, no overlap
+        assert tiles[-1][0] < M <= tiles[-1][0] + tiles[-1][1], (M, slots)          # the last tile holds the last row, none is empty
+        assert (ntiles > nfull) == half, (M, slots)                                  # half tiles exactly under the rule
+        assert ntiles == nfull + ((M - 64 * nfull + 31) // 32 if half else 0), (M, slots)
+        if half:
+            assert nfull % slots == 0 and ntiles - nfull <= slots, (M, slots)        # whole rounds in front, one round of half tiles
+        halves += half
+    assert halves > 0
+    lib = _lib.lib()
+    n = ctypes.c_int(0)
+    assert lib.occ_linear_chain_tile_split(0, slots, ctypes.byref(n), ctypes.byref(n)) == -1
+    assert lib.occ_linear_chain_tile_split(64, 0, ctypes.byref(n), ctypes.byref(n)) == -1
+    assert lib.occ_linear_chain_tile_split(64, slots, None, ctypes.byref(n)) == -1
+
+
+def test_linear_chain_tile_split_of_the_tested_row_counts():
+    """The M of tests/exact_cases.py on the 512 slots of 256 CUs: 8229 rows are 129 full tiles (blockIdx >> 3 = 0 .. 16: all
+    16 rotations), chain_m_half() rows are 512 full tiles and 129 half tiles, the last with one row."""
+    from tests import exact_cases as ec
+    assert _chain_split(ec.CHAIN_M_FULL, 512) == (129, 129)
+    assert {(b >> 3) & 15 for b in range(129)} == set(range(16))
+    for cus in (256, 304, 104):
+        M = ec.chain_m_half(cus)
+        assert _chain_split(M, 2 * cus) == (2 * cus, 2 * cus + 129)
+        assert {(b >> 3) & 15 for b in range(2 * cus, 2 * cus + 129)} == set(range(16))
+        assert M - 64 * 2 * cus - 32 * 128 == 1
+
+
+def test_linear_chain_refuses_rows_beyond_the_4gb_of_a_buffer_resource():
+    """(M + 64) * ld * 4 >= 2^32 for any of the six leading dimensions is OccAmdUnsupported, before any launch."""
+    lib = _lib.lib()
+    null = ctypes.c_void_p(0)
+    buf = (ctypes.c_float * 64)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    i64, f = ctypes.c_int64, ctypes.c_float(1e-5)
+    big_m = 2 ** 22 - 64                              # (M + 64) * 256 * 4 == 2^32
+    big_ld = 2 ** 20                                   # (1024 + 64) * 2^20 * 4 > 2^32
+
+    def pair(M, lda=256, ldq=192, ldzq=192, ldzv=256):
+        return lib.occ_linear_pair_chain_bf16x3_f32(p, i64(lda), p, p, p, i64(ldq), p, i64(ldzq), 192, p, i64(ldzv), M, null)
+
+    def prog_a(M, lda=256, ldres=256, ldy=256, ldz=768):
+        return lib.occ_linear_ln_chain_bf16x3_f32(p, i64(lda), p, i64(ldres), p, p, p, p, f, p, i64(ldy), p, i64(ldz), 768, 0,
+                                                  M, null)
+
+    def prog_b(M, ldy=256, ldzv=256):
+        return lib.occ_encoder_ffn_chain_bf16x3_f32(p, i64(256), p, i64(256), p, p, p, p, f, p, p, f, p, i64(ldy), p, i64(192),
+                                                    p, i64(192), 192, p, i64(ldzv), M, null)
+    for rc in (pair(big_m), prog_a(big_m), prog_b(big_m), pair(1024, lda=big_ld), pair(1024, ldq=big_ld), pair(1024, ldzq=big_ld),
+               pair(1024, ldzv=big_ld), prog_a(1024, ldres=big_ld), prog_a(1024, ldy=big_ld), prog_a(1024, ldz=big_ld),
+               prog_b(1024, ldy=big_ld), prog_b(1024, ldzv=big_ld)):
+        assert rc == -3 and b'4 GB' in lib.occ_last_error()

@@ -53,6 +53,17 @@ def test_rounding_profile(case, kw):
             assert i2 >= 0.01 and t2 >= 0.01 and 0.25 <= n2 <= 0.75, (name, i2, t2, n2)
 
 
+CHAIN_RELU = [(c, kw) for c, kw in ec.chain_host_cases() if c.ref(**kw).relu]
+
+
+@pytest.mark.parametrize("case,kw", CHAIN_RELU, ids=_ids(CHAIN_RELU))
+def test_chain_relu_sees_negative_preactivations(case, kw):
+    """The ReLU of linear_ln_chain's tail and of encoder_ffn_chain's hidden layer (fp32 outputs: no rounding to profile)."""
+    negative = ec.rounding_profile(case.ref(**kw).pre)[2]
+    print(f"{case!r}: negative {negative:.3f}")
+    assert 0.25 <= negative <= 0.75, negative
+
+
 @pytest.mark.parametrize("case,wide", WIDE, ids=[repr(c) for c, _ in WIDE])
 def test_wide_operand_needs_its_low_plane(case, wide):
     share = float((~ec.is_bf16(wide)).double().mean())

@@ -15,9 +15,14 @@ pooling) to bf16; a projection shortcut is contracted in the accumulator of the 
 linear applies the ReLU before the residual.  The bf16x3 kernels (linear, value_proj, linear_wgrad, conv3d and its
 gradients) run once per flavour: one operand wide (needs its low plane), the others bf16-exact.
 
-Out of scope: the LayerNorm and Softplus epilogues, the linear_*_chain kernels and occ_heads (transcendentals and
-divisions are not exact), the BatchNorm statistics and heads-loss kernels, and the gather kernels (float64 tests in every
-mode already).  bias_relu_maxpool_nhwc and bias_act_nhwc_ are compared bit for bit in tests/test_gpu_backbone.py.  Both
+The linear chains (csrc/linear_chain_x3.hip): linear_pair_chain is exact as it stands; the tails of linear_ln_chain and
+encoder_ffn_chain run behind a LayerNorm with gamma = 0, whose output is the row beta exactly, and are exact from there.
+A LayerNorm itself is not exact: those of the chains (encoder_ffn_chain's second one on the exact integer output of its
+FFN) and the ln= epilogue of linear get exact integer inputs, at rows with |mean| >> std and with variance near eps,
+and must stay inside an error bound counted from the kernel source, never fitted to a result (tests/ln_bound.py).
+
+Out of scope: the Softplus epilogue and occ_heads (transcendentals and divisions are not exact), the BatchNorm
+statistics and heads-loss kernels, and the gather kernels (float64 tests in every mode already).  bias_relu_maxpool_nhwc and bias_act_nhwc_ are compared bit for bit in tests/test_gpu_backbone.py.  Both
 Linear kernels need K1 % 16 == 0 and K2 % 16 == 0 (anything else is OccAmdUnsupported, tests/test_gpu_linear.py), so the
 odd K here is 48 = 32 + 16."""
 import pytest
@@ -319,3 +324,135 @@ def test_bias_act_bwd_bias_gradient_is_the_exact_column_sum(N, C, H, W):
         got_g, got_b = ext.bias_act_bwd_nhwc(gy, y if relu else None, relu=relu)
         ec.assert_bit_equal(got_g, ref.extra["g"], f"{case!r} relu={relu} g")
         ec.assert_bit_equal(got_b, ref.out, f"{case!r} relu={relu} bias gradient")
+
+
+# ---- the linear chains (csrc/linear_chain_x3.hip): exact stages ---------------------------------------------------------------
+
+@pytest.fixture
+def x3(monkeypatch):
+    """The chain programs exist in the bf16x3 precision mode only (the environment could set the other one)."""
+    from occnet_amd import ext
+    monkeypatch.setattr(ext, "LINEAR_PRECISION", "bf16x3")
+    return ext
+
+
+def _chain_tall():
+    """The tall M: all 16 k-step rotations on 64-row tiles and, from the device's CU count, on 32-row tiles."""
+    return ec.CHAIN_M_FULL, ec.chain_m_half(torch.cuda.get_device_properties(0).multi_processor_count)
+
+
+def _chain_runs(flavours):
+    """(M, flavour): both flavours at the small M; the tall M walk the tiles, which does not depend on the flavour: one
+    each."""
+    return [(M, w) for M in ec.CHAIN_M_SMALL for w in flavours] + list(zip(_chain_tall(), flavours))
+
+
+def _ln0(beta):
+    """A LayerNorm with gamma = 0: its output is the row beta."""
+    return torch.zeros(256, device="cuda"), _f(beta), 1e-5
+
+
+def _rows_equal(y, beta, what):
+    """Every row of y is the row beta, bit for bit (the columns are distinct integers: a permuted store shows)."""
+    assert tuple(y.shape) == (y.shape[0], 256)
+    bad = (y != _f(beta)[None]).nonzero()
+    assert bad.numel() == 0, f"{what}: {bad.shape[0]} elements of y differ from beta, first at {tuple(int(i) for i in bad[0])}"
+
+
+@pytest.mark.parametrize("term", [False, True])
+@pytest.mark.parametrize("nq", ec.CHAIN_NQ)
+def test_linear_pair_chain(nq, term, x3):
+    for M, wide in _chain_runs(ec.CHAIN_PAIR_FLAVOURS):
+        case = ec.pair_chain_case(M, nq, term, wide)
+        c = case.inp
+        zq, zv = x3.linear_pair_chain(_f(c["a"]), _f(c["wq"]), _f(c["term"]), _f(c["wv"]), _f(c["bv"]))
+        assert zq.shape == (M, nq) and zv.shape == (M, 256)
+        ec.assert_bit_equal(torch.cat([zq, zv], 1), case.ref().out, f"{case!r}")
+
+
+@pytest.mark.parametrize("wide", ec.CHAIN_TAIL_FLAVOURS)
+@pytest.mark.parametrize("n2", ec.CHAIN_N2)
+def test_linear_ln_chain_tail(n2, wide, x3):
+    """Program A behind gamma = 0: y is beta in every row and z = act2(beta . W2^T + b2), ReLU on and off."""
+    for M, relu in [(M, r) for M in ec.CHAIN_M_SMALL for r in (False, True)] + list(zip(_chain_tall(), (True, False))):
+        case = ec.tail_a_case(M, n2, wide)
+        c = case.inp
+        y, z = x3.linear_ln_chain(c["a"].cuda(), c["res"].cuda(), c["w1"].cuda(), c["b1"].cuda(), _ln0(c["beta"]),
+                                  _f(c["w2"]), _f(c["b2"]), act2="relu" if relu else None)
+        _rows_equal(y, c["beta"], f"{case!r}")
+        ec.assert_bit_equal(z, case.ref(relu=relu).out, f"{case!r} relu={relu}")
+
+
+@pytest.mark.parametrize("term", [False, True])
+@pytest.mark.parametrize("nq", ec.CHAIN_NQ)
+def test_encoder_ffn_chain_tail(nq, term, x3):
+    """Program B behind gamma2 = 0: y (which parks x2 until x3 overwrites it) is beta2 in every row, and the tail is
+    [beta2 . Wq^T + term | beta2 . Wv^T + bv]."""
+    for M, wide in _chain_runs(ec.CHAIN_TAIL_FLAVOURS):
+        case = ec.tail_b_case(M, nq, term, wide)
+        c = case.inp
+        d = {k: c[k].cuda() for k in ("a", "res", "wo", "bo", "g1", "be1", "w1", "b1", "w2", "b2")}
+        y, zq, zv = x3.encoder_ffn_chain(d["a"], d["res"], d["wo"], d["bo"], (d["g1"], d["be1"], 1e-5), d["w1"], d["b1"],
+                                         d["w2"], d["b2"], _ln0(c["beta"]),
+                                         tail=(_f(c["wq"]), _f(c["term"]), _f(c["wv"]), _f(c["bv"])))
+        _rows_equal(y, c["beta"], f"{case!r}")
+        assert zq.shape == (M, nq) and zv.shape == (M, 256)
+        ec.assert_bit_equal(torch.cat([zq, zv], 1), case.ref().out, f"{case!r}")
+
+
+# ---- LayerNorm on exact integer inputs, under the bound counted from the kernel sources (tests/ln_bound.py) -------------------
+
+LN_M = (65, 8229)
+
+
+def _check_ln(got, ref, c, mean_roundings, what, constant=None):
+    from tests import ln_bound as lb
+    ratio = lb.worst_ratio(got, ref, ref.bound(c, mean_roundings))
+    print(f"{what}: c = {c}, worst err / bound = {ratio:.3f}")
+    assert ratio <= 1.0, f"{what}: err / bound = {ratio:.4g} with c = {c}"
+    if constant is not None:                           # a constant row is beta, exactly
+        rows = got.detach().cpu()[constant]
+        assert torch.equal(rows, ref.beta.float()[None].expand_as(rows)), f"{what}: a constant row is not beta"
+
+
+@pytest.mark.parametrize("M", LN_M)
+def test_linear_ln_chain_layernorm(M, x3):
+    """y of linear_ln_chain on the four row kinds.  |y - ref| <= 24 U |t| + U |y|: the count is in tests/ln_bound.py."""
+    from tests import ln_bound as lb
+    c = lb.ln_case(M, 256)
+    ref = lb.LnRef(c["x"], c["gamma"], c["beta"])
+    w2 = torch.zeros(32, 256, device="cuda")
+    y, _ = x3.linear_ln_chain(_f(c["a"]), _f(c["res"]), _f(c["wo"]), _f(c["bo"]), (c["gamma"].cuda(), c["beta"].cuda(), 1e-5),
+                              w2, None)
+    _check_ln(y, ref, lb.C_CHAIN, 0, f"linear_ln_chain M={M}", c["kind"] == lb.CONSTANT)
+
+
+@pytest.mark.parametrize("M", LN_M)
+def test_encoder_ffn_chain_layernorm(M, x3):
+    """gamma1 = 0 makes x2 the row beta1 and pre2 = relu(x2 . W1^T + b1) . W2^T + b2 + x2 an exact integer
+    (tests/exact_cases.ffn_case); y = LayerNorm2(pre2) under the bound of ch_layernorm.  A missing ReLU, a missing x2, a
+    lost low plane of h or a dropped k element miss it by factors of 1e4 and more (tests/test_ln_bound_host.py)."""
+    from tests import ln_bound as lb
+    case = ec.ffn_case(M)
+    c = case.inp
+    ref = lb.LnRef(case.ref().value, c["g2"], c["be2"])
+    y, zq, zv = x3.encoder_ffn_chain(c["a"].cuda(), c["res"].cuda(), c["wo"].cuda(), c["bo"].cuda(), _ln0(c["beta1"]),
+                                     _f(c["w1"]), _f(c["b1"]), _f(c["w2"]), _f(c["b2"]), (c["g2"].cuda(), c["be2"].cuda(), 1e-5))
+    assert zq is None and zv is None and y.shape == (M, 256)
+    _check_ln(y, ref, lb.C_CHAIN, 0, f"encoder_ffn_chain M={M}")
+
+
+@pytest.mark.parametrize("precision", ["f32", "bf16x3"])
+@pytest.mark.parametrize("N", [256, 128, 100])
+def test_linear_layernorm_epilogue(N, precision):
+    """linear(..., residual=, ln=) on the four row kinds: c = 12, and for N = 100 (1 / N and the mean are not exact) c = 14
+    with the two terms of the inexact mean (tests/ln_bound.py)."""
+    from occnet_amd import ext
+    from tests import ln_bound as lb
+    cc, mr = lb.linear_c(N)
+    for M in LN_M:
+        c = lb.ln_case(M, N)
+        ref = lb.LnRef(c["x"], c["gamma"], c["beta"])
+        y = ext.linear(_f(c["a"]), _f(c["wo"]), _f(c["bo"]), residual=_f(c["res"]), ln=(c["gamma"].cuda(), c["beta"].cuda(), 1e-5),
+                       precision=precision)
+        _check_ln(y, ref, cc, mr, f"linear ln= N={N} {precision} M={M}", c["kind"] == lb.CONSTANT)

@@ -520,6 +520,136 @@ def test_linear_chain_never_writes_past_the_last_row(monkeypatch):
         assert bool((full[:M] != -777.0).any())
 
 
+# ---- strided rows and caller-provided outputs: same tile walk, same summation order, so any difference from the
+# contiguous call at the same M is an addressing error --------------------------------------------------------------------
+
+SENTINEL = -777.0
+
+
+def _chain_strided_m():
+    from tests import exact_cases as ec
+    return 197, ec.chain_m_half(torch.cuda.get_device_properties(0).multi_processor_count)      # M_half: 32-row tiles too
+
+
+def _in_slice(t, width, c0):
+    """t (M, K) -> the same values as columns [c0, c0 + K) of a sentinel-filled (M, width) device buffer (a view)."""
+    buf = torch.full((t.shape[0], width), SENTINEL, device='cuda')
+    buf[:, c0:c0 + t.shape[1]] = t
+    return buf[:, c0:c0 + t.shape[1]]
+
+
+def _chain_operands(g, M, nq):
+    s = (1.0 / 256) ** 0.5
+    return {k: v.cuda() for k, v in dict(
+        a=_mk(g, M, 256), res=_mk(g, M, 256), wo=_mk(g, 256, 256, scale=s), bo=_mk(g, 256, scale=0.1),
+        g1=torch.rand(256, generator=g) + 0.5, be1=_mk(g, 256, scale=0.1), w1=_mk(g, 512, 256, scale=s),
+        b1=_mk(g, 512, scale=0.1), w2=_mk(g, 256, 512, scale=(1.0 / 512) ** 0.5), b2=_mk(g, 256, scale=0.1),
+        g2=torch.rand(256, generator=g) + 0.5, be2=_mk(g, 256, scale=0.1), wq=_mk(g, nq, 256, scale=s),
+        qt=_mk(g, M, nq), wv=_mk(g, 256, 256, scale=s), bv=_mk(g, 256, scale=0.1), w3=_mk(g, 288, 256, scale=s),
+        b3=_mk(g, 288, scale=0.1)).items()}
+
+
+@pytest.fixture
+def chain_ext(monkeypatch):
+    from occnet_amd import ext
+    monkeypatch.setattr(ext, "LINEAR_PRECISION", "bf16x3")
+    return ext
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_linear_ln_chain_strided_rows(which, chain_ext):
+    """Program A with a and residual as column slices of wider buffers (lda = 320, ldres = 384)."""
+    M = _chain_strided_m()[which]
+    c = _chain_operands(torch.Generator().manual_seed(65), M, 192)
+    ln = (c['g1'], c['be1'], 1e-5)
+    y0, z0 = chain_ext.linear_ln_chain(c['a'], c['res'], c['wo'], c['bo'], ln, c['w3'], c['b3'], act2='relu')
+    a, res = _in_slice(c['a'], 320, 32), _in_slice(c['res'], 384, 64)
+    assert a.stride(0) == 320 and res.stride(0) == 384
+    y, z = chain_ext.linear_ln_chain(a, res, c['wo'], c['bo'], ln, c['w3'], c['b3'], act2='relu')
+    assert torch.equal(y, y0) and torch.equal(z, z0)
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_linear_pair_chain_strided_rows(which, chain_ext):
+    """Program C with a (lda = 320) and q_term (ldterm = 256 > nq) as column slices of wider buffers."""
+    M = _chain_strided_m()[which]
+    nq = (128, 192)[which]
+    c = _chain_operands(torch.Generator().manual_seed(66), M, nq)
+    zq0, zv0 = chain_ext.linear_pair_chain(c['a'], c['wq'], c['qt'], c['wv'], c['bv'])
+    a, qt = _in_slice(c['a'], 320, 32), _in_slice(c['qt'], 256, 0)
+    assert qt.stride(0) == 256
+    zq, zv = chain_ext.linear_pair_chain(a, c['wq'], qt, c['wv'], c['bv'])
+    assert torch.equal(zq, zq0) and torch.equal(zv, zv0)
+
+
+@pytest.mark.parametrize("which", [0, 1])
+def test_encoder_ffn_chain_strided_rows_and_out_bands(which, chain_ext):
+    """Program B with strided a, residual and q_term, and out = (y, zq, zv) as row-and-column bands of larger buffers:
+    rows [G, G + M) of M + 2 G, ldy = 512, ldzq = 256, ldzv = 320.  Equal to the contiguous call; every element of the out
+    buffers outside the band keeps its sentinel."""
+    M = _chain_strided_m()[which]
+    nq = (128, 192)[which]
+    G = 3
+    c = _chain_operands(torch.Generator().manual_seed(67), M, nq)
+    args = lambda a, res: (a, res, c['wo'], c['bo'], (c['g1'], c['be1'], 1e-5), c['w1'], c['b1'], c['w2'], c['b2'],
+                           (c['g2'], c['be2'], 1e-5))
+    y0, zq0, zv0 = chain_ext.encoder_ffn_chain(*args(c['a'], c['res']), tail=(c['wq'], c['qt'], c['wv'], c['bv']))
+    bufs = [torch.full((M + 2 * G, w), SENTINEL, device='cuda') for w in (512, 256, 320)]
+    bands = [(128, 256), (64, nq), (32, 256)]           # (first column, columns) of y, zq, zv
+    out = tuple(b[G:G + M, c0:c0 + n] for b, (c0, n) in zip(bufs, bands))
+    assert [o.stride(0) for o in out] == [512, 256, 320]
+    a, res, qt = _in_slice(c['a'], 320, 32), _in_slice(c['res'], 384, 64), _in_slice(c['qt'], 256, 0)
+    y, zq, zv = chain_ext.encoder_ffn_chain(*args(a, res), tail=(c['wq'], qt, c['wv'], c['bv']), out=out)
+    torch.cuda.synchronize()
+    assert y.data_ptr() == out[0].data_ptr() and zq.data_ptr() == out[1].data_ptr() and zv.data_ptr() == out[2].data_ptr()
+    for got, want, buf, (c0, n), name in zip(out, (y0, zq0, zv0), bufs, bands, ("y", "zq", "zv")):
+        assert torch.equal(got, want), name
+        outside = torch.ones_like(buf, dtype=torch.bool)
+        outside[G:G + M, c0:c0 + n] = False
+        assert bool((buf[outside] == SENTINEL).all()), f"{name}: written outside its band"
+    # without a tail: y alone
+    bufs[0].fill_(SENTINEL)
+    y1, zq1, zv1 = chain_ext.encoder_ffn_chain(*args(a, res), out=(out[0], None, None))
+    y2, _, _ = chain_ext.encoder_ffn_chain(*args(c['a'], c['res']))
+    assert zq1 is None and zv1 is None and torch.equal(out[0], y2)
+    outside = torch.ones_like(bufs[0], dtype=torch.bool)
+    outside[G:G + M, 128:384] = False
+    assert bool((bufs[0][outside] == SENTINEL).all())
+
+
+def test_linear_chain_rejects_misaligned_views(chain_ext):
+    """A data pointer that is not 16-byte aligned, or a leading dimension with ld % 4 != 0, is OccAmdUnsupported for every
+    strided operand and output."""
+    from occnet_amd._lib import OccAmdUnsupported
+    M, nq = 70, 64
+    c = _chain_operands(torch.Generator().manual_seed(68), M, nq)
+    ln1, ln2 = (c['g1'], c['be1'], 1e-5), (c['g2'], c['be2'], 1e-5)
+    shifted = lambda t: _in_slice(t, t.shape[1] + 64, 1)             # first element 4 bytes behind an aligned address
+    odd_ld = lambda t: _in_slice(t, t.shape[1] + 2, 0)               # ld = K + 2
+    tail = (c['wq'], c['qt'], c['wv'], c['bv'])
+    ffn = lambda a, res, **kw: chain_ext.encoder_ffn_chain(a, res, c['wo'], c['bo'], ln1, c['w1'], c['b1'], c['w2'], c['b2'],
+                                                           ln2, **kw)
+    good = lambda n: torch.empty(M, n, device='cuda')
+    for bad in (shifted, odd_ld):
+        assert bad(c['a']).data_ptr() % 16 != 0 or bad(c['a']).stride(0) % 4 != 0
+        calls = [
+            lambda: chain_ext.linear_ln_chain(bad(c['a']), c['res'], c['wo'], c['bo'], ln1, c['w3'], c['b3']),
+            lambda: chain_ext.linear_ln_chain(c['a'], bad(c['res']), c['wo'], c['bo'], ln1, c['w3'], c['b3']),
+            lambda: chain_ext.linear_pair_chain(bad(c['a']), c['wq'], c['qt'], c['wv'], c['bv']),
+            lambda: chain_ext.linear_pair_chain(c['a'], c['wq'], bad(c['qt']), c['wv'], c['bv']),
+            lambda: ffn(bad(c['a']), c['res']),
+            lambda: ffn(c['a'], bad(c['res'])),
+            lambda: ffn(c['a'], c['res'], tail=(c['wq'], bad(c['qt']), c['wv'], c['bv'])),
+            lambda: ffn(c['a'], c['res'], tail=tail, out=(bad(good(256)), good(nq), good(256))),
+            lambda: ffn(c['a'], c['res'], tail=tail, out=(good(256), bad(good(nq)), good(256))),
+            lambda: ffn(c['a'], c['res'], tail=tail, out=(good(256), good(nq), bad(good(256)))),
+        ]
+        for i, call in enumerate(calls):
+            with pytest.raises(OccAmdUnsupported):
+                call()
+    torch.cuda.synchronize()
+
+
 def test_linear_chain_rejects_other_shapes():
     from occnet_amd import ext
     from occnet_amd._lib import OccAmdUnsupported
