@@ -667,6 +667,29 @@ int occ_stem_conv7x7_pool_u8_bf16(const uint8_t* x, const void* weight_frag, con
                                   int batch, int Hs, int Ws, int H, int W, const float* mean,
                                   const float* std, int to_rgb, void* stream);
 
+/* The reference's TRAINING input from raw frames in one pass (bevformer_base_occ.py:153-164 and use_grid_mask):
+ * PhotoMetricDistortionMultiViewImage -> NormalizeMultiviewImage -> PadMultiViewImage -> GridMask
+ * (P/datasets/pipelines/transform_3d.py:141-188, :91, :31-43; P/models/utils/grid_mask.py:84-124), float32 throughout.
+ *   x        (n_images, Hs, Ws, 3) uint8 HWC on the device, channels as loaded (BGR); any byte alignment
+ *   records  n_images x 8 DEVICE floats, one row per image, the draws of the distortion made on the host:
+ *              [0] brightness delta (0 = off)   [1] contrast alpha applied BEFORE the HSV round trip (1 = off)
+ *              [2] saturation factor (1 = off)  [3] hue shift in degrees (0 = off)
+ *              [4] contrast alpha applied AFTER the round trip (1 = off)
+ *              [5..7] perm[3] as 0.f / 1.f / 2.f: output channel c takes channel perm[c] (0 1 2 = off)
+ *   out      (n_images, 3, H, W) f32 NCHW, 16-byte aligned; every element is written, rows >= Hs and columns >= Ws are 0
+ *   mean, std: 3 HOST floats each, network channel order; to_rgb reverses the channels first; 1 / std is formed in
+ *            double and rounded to float, as occ_stem_conv7x7_pool_u8_bf16 forms it
+ *   grid_mask: NULL (not applied) or 8 HOST ints (apply, d, l, st_h, st_w, use_h, use_w, mode): GridMask with rotate = 1
+ *            and offset = False: the multiplier is 0 inside a band (1 outside), inverted when mode == 1.  With
+ *            hh = 3H/2, Y = y + (hh - H)/2 a row is in a band iff use_h, Y - st_h >= 0, (Y - st_h) / d < hh / d and
+ *            (Y - st_h) % d < l; columns alike with W, st_w, use_w.
+ * The BGR <-> HSV steps restate OpenCV's float path (s = diff / (|v| + FLT_EPSILON), h in degrees, sector table).
+ * OCC_E_INVALID before any launch: null / misaligned pointers, H < Hs, W < Ws, zero std, more than 65 535 images,
+ * d < 2, l outside [1, d-1], st_h / st_w outside [0, d).  OCC_E_UNSUPPORTED: W % 4 != 0 (one thread stores 4 pixels). */
+int occ_train_input_u8_f32(const uint8_t* x, const void* records, float* out, int n_images, int Hs, int Ws, int H,
+                           int W, const float* mean, const float* std, int to_rgb, const int32_t* grid_mask,
+                           void* stream);
+
 /* Stem tail in one pass: out = max_pool2d(relu(y + bias), kernel 3, stride 2, padding 1) on NHWC bf16
  * (outside the hand-written hot path).  y (batch, H, W, C) bf16 raw convolution output ; bias (C) f32 ;
  * out (batch, (H-1)/2+1, (W-1)/2+1, C) bf16.  Needs C % 8 == 0.

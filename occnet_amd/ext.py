@@ -2317,6 +2317,50 @@ def stem_conv7x7_pool_u8(x_u8, weight_frag, bias, mean, std, to_rgb=False, size_
     return out, (H, W)
 
 
+def train_input_u8(frames_u8, records, mean, std, to_rgb, size_divisor=32, grid_mask=None, out=None):
+    """The reference's training input in one launch: frames_u8 (NI, Hs, Ws, 3) uint8 HWC on the device, channels as
+    loaded (BGR) -> (NI, 3, H, W) float32, H x W the next multiples of `size_divisor`, the pad area 0.
+    PhotoMetricDistortionMultiViewImage with the draws in `records` ((NI, 8) float32, io.sample_photometric /
+    io.identity_photometric; a numpy array is uploaded, a device tensor is taken as it is), NormalizeMultiviewImage(mean,
+    std, to_rgb), PadMultiViewImage(size_divisor) and GridMask (reference transform_3d.py:141-188, :91, :31-43,
+    grid_mask.py:84-124).  grid_mask: None (not applied) or (d, l, st_h, st_w, use_h, use_w, mode) — the draws of
+    GridMask.sample_params and the module's use_h / use_w / mode; rotate == 1 and offset == False only.
+    out: optional (NI, 3, H, W) float32 contiguous device tensor to write into."""
+    if not (isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda):
+        raise OccAmdError("train_input_u8: frames must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+    if not (frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[-1] == 3
+            and frames_u8.is_contiguous()):
+        raise OccAmdUnsupported("train_input_u8: frames must be a contiguous (NI, Hs, Ws, 3) uint8 device tensor")
+    NI, Hs, Ws, _ = frames_u8.shape
+    if not isinstance(records, torch.Tensor):
+        import numpy as np
+        records = torch.from_numpy(np.ascontiguousarray(records, dtype=np.float32)).to(frames_u8.device)
+    _need_cuda_f32("records", records)
+    if tuple(records.shape) != (NI, 8):
+        raise OccAmdError(f"train_input_u8: records must be ({NI}, 8), got {tuple(records.shape)}")
+    d = int(size_divisor)
+    H, W = (Hs + d - 1) // d * d, (Ws + d - 1) // d * d
+    if out is None:
+        out = torch.empty((NI, 3, H, W), dtype=torch.float32, device=frames_u8.device)
+    else:
+        _need_cuda_f32("out", out)
+        if tuple(out.shape) != (NI, 3, H, W):
+            raise OccAmdError(f"train_input_u8: out must be ({NI}, 3, {H}, {W}), got {tuple(out.shape)}")
+    mean_c = (f32 * 3)(*[float(v) for v in mean])
+    std_c = (f32 * 3)(*[float(v) for v in std])
+    gm_c = None
+    if grid_mask is not None:
+        if len(grid_mask) != 7:
+            raise OccAmdError("train_input_u8: grid_mask must be (d, l, st_h, st_w, use_h, use_w, mode)")
+        gm_c = (i32 * 8)(1, *[int(v) for v in grid_mask])
+    with torch.cuda.device(frames_u8.device), _timed('train_input_u8'):
+        rc = _lib.lib().occ_train_input_u8_f32(ptr(frames_u8), ptr(records), ptr(out), i32(NI), i32(Hs), i32(Ws), i32(H),
+                                               i32(W), mean_c, std_c, i32(1 if to_rgb else 0), gm_c,
+                                               stream_ptr(frames_u8.device))
+    _lib.check(rc, "train_input_u8")
+    return out
+
+
 def bias_relu_maxpool_nhwc(y, bias):
     """max_pool2d(relu(y + bias), 3, stride 2, padding 1) in one launch on a channels_last bf16 activation
     (the ResNet stem's tail).  y (N, C, H, W) channels_last bf16 raw convolution output; bias (C) f32."""

@@ -4,6 +4,9 @@ or the nuScenes devkit.  Host-side formatting only (no model compute lives here)
 
   pad_multiview / normalize_multiview / to_batch   P/datasets/pipelines/transform_3d.py:12-101
                                                    (PadMultiViewImage size_divisor=32, NormalizeMultiviewImage)
+  sample_photometric / photometric_distort         P/datasets/pipelines/transform_3d.py:102-189
+                                                   (PhotoMetricDistortionMultiViewImage: the draws, and the host chain;
+                                                   the device chain is ext.train_input_u8)
   quaternion_rotation_matrix, transform_matrix     pyquaternion / nuscenes.utils.geometry_utils, as used at
                                                    P/datasets/nuscenes_occ.py:82-86
   camera_matrices                                  P/datasets/nuscenes_occ.py:87-120 (lidar2img = K_pad @ lidar2cam)
@@ -55,6 +58,114 @@ def normalize_multiview(imgs, mean, std, to_rgb=True):
             x = x[..., ::-1]
         out.append((x - mean) * stdinv)
     return out, dict(mean=mean.reshape(-1), std=std.reshape(-1), to_rgb=to_rgb)
+
+
+_EPS32 = np.float32(np.finfo(np.float32).eps)     # FLT_EPSILON
+
+
+def bgr2hsv_f32(img):
+    """(..., 3) float32 BGR -> HSV (h in degrees, s, v): OpenCV's float path (RGB2HSV_f) restated in float32 numpy
+    — what mmcv.bgr2hsv runs on a float32 image.  cv2 is not vendored by the reference; this is a restatement from
+    the published algorithm ("Training input from uint8 frames")."""
+    assert img.dtype == np.float32
+    b, g, r = img[..., 0], img[..., 1], img[..., 2]
+    v = np.maximum(np.maximum(b, g), r)
+    vmin = np.minimum(np.minimum(b, g), r)
+    diff = v - vmin
+    s = diff / (np.abs(v) + _EPS32)
+    k = np.float32(60) / (diff + _EPS32)
+    h = np.where(v == r, (g - b) * k, np.where(v == g, (b - r) * k + np.float32(120), (r - g) * k + np.float32(240)))
+    h = np.where(h < 0, h + np.float32(360), h)
+    return np.stack([h, s, v], -1).astype(np.float32)
+
+
+def hsv2bgr_f32(img):
+    """(..., 3) float32 HSV (h in degrees) -> BGR: OpenCV's float path (HSV2RGB_f) restated in float32 numpy."""
+    assert img.dtype == np.float32
+    h, s, v = img[..., 0], img[..., 1], img[..., 2]
+    h = h * np.float32(1.0 / 60.0)
+    while (h < 0).any():
+        h = np.where(h < 0, h + np.float32(6), h)
+    while (h >= 6).any():
+        h = np.where(h >= 6, h - np.float32(6), h)
+    fl = np.floor(h)
+    over = fl >= 6
+    sector = np.where(over, 0, fl).astype(np.int64)
+    f = np.where(over, np.float32(0), h - fl)
+    one = np.float32(1)
+    tab = np.stack([v, v * (one - s), v * (one - s * f), v * (one - s * (one - f))], -1)
+    idx = np.array([[1, 3, 0], [1, 0, 2], [3, 0, 1], [0, 2, 1], [0, 1, 3], [2, 1, 0]])
+    bgr = np.take_along_axis(tab, idx[sector], -1)
+    return np.where((s == 0)[..., None], v[..., None], bgr).astype(np.float32)
+
+
+PHOTOMETRIC_IDENTITY = np.array([0, 1, 1, 0, 1, 0, 1, 2], dtype=np.float32)
+
+
+def identity_photometric(n_images):
+    """Records that switch every stage of the distortion off."""
+    return np.tile(PHOTOMETRIC_IDENTITY, (int(n_images), 1))
+
+
+def sample_photometric(n_images, brightness_delta=32, contrast_range=(0.5, 1.5), saturation_range=(0.5, 1.5),
+                       hue_delta=18):
+    """The random draws of PhotoMetricDistortionMultiViewImage for `n_images` images, made from numpy's GLOBAL RNG in
+    the reference's order (transform_3d.py:146-186), so a run seeded like the reference distorts alike.
+    -> (n_images, 8) float32 records [delta, alpha_pre, sat, hue, alpha_post, perm0, perm1, perm2]: a stage that was
+    not drawn holds its identity (0, 1, 1, 0, 1, 0 1 2).  alpha_pre is the contrast applied before the HSV round trip
+    (the reference's mode == 1), alpha_post the one after it (mode == 0).  Values are rounded to float32: the
+    reference applies them in place to float32 arrays."""
+    rng = np.random
+    lo_c, hi_c = contrast_range
+    lo_s, hi_s = saturation_range
+    rec = identity_photometric(n_images)
+    for r in rec:
+        if rng.randint(2):
+            r[0] = rng.uniform(-brightness_delta, brightness_delta)
+        mode = rng.randint(2)
+        if mode == 1:
+            if rng.randint(2):
+                r[1] = rng.uniform(lo_c, hi_c)
+        if rng.randint(2):
+            r[2] = rng.uniform(lo_s, hi_s)
+        if rng.randint(2):
+            r[3] = rng.uniform(-hue_delta, hue_delta)
+        if mode == 0:
+            if rng.randint(2):
+                r[4] = rng.uniform(lo_c, hi_c)
+        if rng.randint(2):
+            r[5:8] = rng.permutation(3)
+    return rec
+
+
+def photometric_distort(imgs, records):
+    """PhotoMetricDistortionMultiViewImage.__call__ with the draws given: imgs = list of (H, W, 3) uint8 or float32 BGR
+    arrays, records from sample_photometric.  The reference's statements in float32 numpy, in its order; a stage
+    whose record value is the identity is skipped, as the reference skips a stage it did not draw.
+    -> list of new (H, W, 3) float32 arrays.  The host twin of ext.train_input_u8's first five steps."""
+    records = np.asarray(records, dtype=np.float32).reshape(len(imgs), 8)
+    out = []
+    for img, (delta, a_pre, sat, hue, a_post, p0, p1, p2) in zip(imgs, records):
+        img = np.array(img, dtype=np.float32)
+        if delta != 0:
+            img += delta
+        if a_pre != 1:
+            img *= a_pre
+        img = bgr2hsv_f32(img)
+        if sat != 1:
+            img[..., 1] *= sat
+        if hue != 0:
+            img[..., 0] += hue
+            img[..., 0][img[..., 0] > 360] -= 360
+            img[..., 0][img[..., 0] < 0] += 360
+        img = hsv2bgr_f32(img)
+        if a_post != 1:
+            img *= a_post
+        perm = [int(p0), int(p1), int(p2)]
+        if perm != [0, 1, 2]:
+            img = img[..., perm]
+        out.append(img)
+    return out
 
 
 def to_batch(imgs):

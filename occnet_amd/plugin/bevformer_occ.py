@@ -9,6 +9,7 @@ train_cfg / test_cfg is injected into the head's config.
 import torch
 
 from .. import cache_epoch, ext
+from ..io import identity_photometric
 from .bricks import BaseModule
 from .grid_mask import GridMask
 from .registry import DETECTORS, build_backbone, build_head, build_neck
@@ -120,8 +121,9 @@ class BEVFormerOcc(BaseModule):
             if m is not None:
                 m.init_weights()
 
-    def extract_img_feat(self, img, img_metas=None, len_queue=None):
-        """img (B, N, 3, H, W) -> list of (B, N, C, h, w) (or (B/len_queue, len_queue, N, C, h, w))."""
+    def extract_img_feat(self, img, img_metas=None, len_queue=None, grid_masked=False):
+        """img (B, N, 3, H, W) -> list of (B, N, C, h, w) (or (B/len_queue, len_queue, N, C, h, w)).
+        grid_masked: the caller has applied GridMask already (extract_feat_u8 with `aug`)."""
         if img is None:
             return None
         B = img.size(0)
@@ -134,7 +136,7 @@ class BEVFormerOcc(BaseModule):
         if plan is not None:
             img_feats = plan(img)       # BN-folded, NHWC, own bf16 kernels
         else:
-            if self.use_grid_mask:
+            if self.use_grid_mask and not grid_masked:
                 img = self.grid_mask(img)
             ac = self.backbone_autocast_dtype
             with torch.autocast(img.device.type, dtype=ac or torch.bfloat16, enabled=ac is not None):
@@ -181,12 +183,42 @@ class BEVFormerOcc(BaseModule):
     def extract_feat(self, img, img_metas=None, len_queue=None):
         return self.extract_img_feat(img, img_metas, len_queue=len_queue)
 
-    def extract_feat_u8(self, img_u8, img_norm_cfg, size_divisor=32):
+    def _train_input_u8(self, frames_u8, img_norm_cfg, size_divisor, aug):
+        """(NI, Hs, Ws, 3) uint8 frames -> the (NI, 3, H, W) float32 backbone input in one launch
+        (ext.train_input_u8): photometric distortion with the records `aug`, normalise, pad and — where
+        extract_img_feat would apply the GridMask module — the module's mask from its own draws
+        (GridMask.sample_params: same RNG consumption as the module's forward, which is then skipped).  A GridMask
+        with rotate > 1 or offset=True has no closed form in the kernel: the module is applied to the result."""
+        NI, Hs, Ws, _ = frames_u8.shape
+        d = int(size_divisor)
+        H, W = (Hs + d - 1) // d * d, (Ws + d - 1) // d * d
+        gm, module_mask = None, False
+        plan_serves = not self.training and not torch.is_grad_enabled() and self._current_plan() is not None
+        if self.use_grid_mask and not plan_serves:
+            g = self.grid_mask
+            if g.rotate == 1 and not g.offset:
+                drawn = g.sample_params(H, W)
+                if drawn is not None:
+                    gm = tuple(drawn) + (int(bool(g.use_h)), int(bool(g.use_w)), int(g.mode))
+            else:
+                module_mask = True
+        x = ext.train_input_u8(frames_u8, aug, img_norm_cfg['mean'], img_norm_cfg['std'],
+                               bool(img_norm_cfg.get('to_rgb', True)), size_divisor=d, grid_mask=gm)
+        return self.grid_mask(x) if module_mask else x
+
+    def extract_feat_u8(self, img_u8, img_norm_cfg, size_divisor=32, aug=None, len_queue=None):
         """Device-side input path: img_u8 (B, N, Hs, Ws, 3) uint8 HWC raw camera images on
         the device.  NormalizeMultiviewImage(**img_norm_cfg) + PadMultiViewImage(size_divisor) + the layout
         change of DefaultFormatBundle3D (reference transform_3d.py:31-45,82-94) run inside the stem kernel of
-        the inference plan, or as torch device ops without it.  -> (list of (B, N, C, h, w) maps, padded (H, W))."""
+        the inference plan, or as torch device ops without it.  -> (list of (B, N, C, h, w) maps, padded (H, W)).
+        aug: (B * N, 8) photometric records (io.sample_photometric / io.identity_photometric) select the training
+        input kernel instead: distortion + normalise + pad + GridMask in one launch (_train_input_u8), then the
+        backbone as extract_img_feat runs it."""
         B, N, Hs, Ws, _ = img_u8.shape
+        if aug is not None:
+            x = self._train_input_u8(img_u8.reshape(B * N, Hs, Ws, 3), img_norm_cfg, size_divisor, aug)
+            H, W = x.shape[-2:]
+            return self.extract_img_feat(x.view(B, N, 3, H, W), len_queue=len_queue, grid_masked=True), (H, W)
         mean, std = img_norm_cfg['mean'], img_norm_cfg['std']
         to_rgb = bool(img_norm_cfg.get('to_rgb', True))
         plan = None if self.training else self._current_plan()
@@ -239,18 +271,26 @@ class BEVFormerOcc(BaseModule):
             return self.forward_train(**kwargs)
         return self.forward_test(**kwargs)
 
-    def obtain_history_bev(self, imgs_queue, img_metas_list):
+    def obtain_history_bev(self, imgs_queue, img_metas_list, img_norm_cfg=None, img_aug=None):
         """BEV of the history frames, iteratively, without gradients
-        (imgs_queue (bs, len_queue, N, 3, H, W))."""
+        (imgs_queue (bs, len_queue, N, 3, H, W), or raw uint8 frames (bs, len_queue, N, Hs, Ws, 3) with
+        img_norm_cfg and optional (bs * len_queue * N, 8) photometric records img_aug, as forward_train takes them)."""
         was_training = self.training
         object.__setattr__(self, '_in_history', True)      # no content fingerprint for this eval <-> train flip
         self.eval()
         object.__setattr__(self, '_in_history', False)
         with torch.no_grad():
             prev_bev = None
-            bs, len_queue, num_cams, C, H, W = imgs_queue.shape
-            imgs_queue = imgs_queue.reshape(bs * len_queue, num_cams, C, H, W)
-            img_feats_list = self.extract_feat(img=imgs_queue, len_queue=len_queue)
+            if imgs_queue.dtype == torch.uint8:
+                bs, len_queue, num_cams, Hs, Ws, _ = imgs_queue.shape
+                if img_aug is None:
+                    img_aug = identity_photometric(bs * len_queue * num_cams)
+                img_feats_list, _ = self.extract_feat_u8(imgs_queue.reshape(bs * len_queue, num_cams, Hs, Ws, 3),
+                                                         img_norm_cfg, aug=img_aug, len_queue=len_queue)
+            else:
+                bs, len_queue, num_cams, C, H, W = imgs_queue.shape
+                imgs_queue = imgs_queue.reshape(bs * len_queue, num_cams, C, H, W)
+                img_feats_list = self.extract_feat(img=imgs_queue, len_queue=len_queue)
             for i in range(len_queue):
                 img_metas = [each[i] for each in img_metas_list]
                 if not img_metas[0]['prev_bev_exists']:
@@ -264,8 +304,19 @@ class BEVFormerOcc(BaseModule):
     def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None,
                       voxel_semantics=None, voxel_flow=None, mask_lidar=None, mask_camera=None,
                       gt_labels=None, gt_bboxes=None, img=None, proposals=None,
-                      gt_bboxes_ignore=None, img_depth=None, img_mask=None):
-        img_feats = self.extract_feat(img=img, img_metas=img_metas)
+                      gt_bboxes_ignore=None, img_depth=None, img_mask=None, img_u8=None, img_norm_cfg=None,
+                      img_aug=None):
+        """img_u8 (B, N, Hs, Ws, 3) uint8 device frames + img_norm_cfg (+ img_aug, (B * N, 8) records of
+        io.sample_photometric; identity when None) instead of `img`: the input tensor is built on the device by
+        ext.train_input_u8, GridMask included when use_grid_mask."""
+        if img_u8 is not None:
+            if img is not None:
+                raise ValueError('forward_train: pass img or img_u8, not both')
+            if img_aug is None:
+                img_aug = identity_photometric(img_u8.shape[0] * img_u8.shape[1])
+            img_feats, _ = self.extract_feat_u8(img_u8, img_norm_cfg, aug=img_aug)
+        else:
+            img_feats = self.extract_feat(img=img, img_metas=img_metas)
         losses = dict()
         losses.update(self.forward_pts_train(img_feats, gt_bboxes_3d, gt_labels_3d, voxel_semantics,
                                              voxel_flow, mask_camera, img_metas, gt_bboxes_ignore,

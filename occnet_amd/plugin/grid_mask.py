@@ -4,7 +4,9 @@ bevformer_occ.py:52-53, applied in extract_img_feat when `use_grid_mask`, :81-82
 
 Draws from numpy's global RNG in the reference's order (apply?, period d, row start, column start, angle), so
 a run seeded like the reference masks the same pixels.  The mask is built on the host (one (1.5h, 1.5w) byte
-plane per call) and applied on the device."""
+plane per call) and applied on the device.  For rotate == 1 and offset == False (what BEVFormerOcc builds) the mask
+has a closed form in four integers: sample_params draws them without building the plane, mask_from_params evaluates
+the form on the host, and ext.train_input_u8 evaluates it inside the uint8 training-input kernel."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -58,6 +60,33 @@ class GridMask(nn.Module):
         mask = self._rotate_nearest(np.uint8(mask), r).astype(np.float32)
         mask = mask[(hh - h) // 2:(hh - h) // 2 + h, (ww - w) // 2:(ww - w) // 2 + w]
         return 1 - mask if self.mode == 1 else mask
+
+    def sample_params(self, h, w):
+        """The draws of one forward() call on an (h, w) image without building the mask: None when the mask is not
+        applied, else (d, l, st_h, st_w).  Consumes numpy's global RNG exactly as forward() + make_mask() do (apply?,
+        d, st_h, st_w, the randint(rotate) angle), so either route leaves the generator in the same state.  The
+        parameters describe the whole mask only for rotate == 1 (the angle is then always 0) and offset == False: that
+        is what mask_from_params and the device route (ext.train_input_u8) evaluate."""
+        if np.random.rand() > self.prob or not self.training:
+            return None
+        d = np.random.randint(2, h)
+        self.l = min(max(int(d * self.ratio + 0.5), 1), d - 1)
+        st_h, st_w = np.random.randint(d), np.random.randint(d)
+        np.random.randint(self.rotate)
+        return int(d), int(self.l), int(st_h), int(st_w)
+
+    @staticmethod
+    def mask_from_params(h, w, d, l, st_h, st_w, use_h=True, use_w=True, mode=0):
+        """make_mask's (h, w) float32 multiplier for rotate == 1 in closed form.  With hh = int(1.5 h) and
+        Y = y + (hh - h) // 2, row y lies in a band iff use_h, Y - st_h >= 0, (Y - st_h) // d < hh // d and
+        (Y - st_h) % d < l; columns alike.  0 inside a band, 1 outside, inverted for mode == 1."""
+        def bands(n, st, use):
+            nn = int(1.5 * n)
+            t = np.arange(n) + (nn - n) // 2 - st
+            return (t >= 0) & (t // d < nn // d) & (t % d < l) if use else np.zeros(n, bool)
+        band = bands(h, st_h, use_h)[:, None] | bands(w, st_w, use_w)[None, :]
+        mask = np.where(band, np.float32(0), np.float32(1))
+        return 1 - mask if mode == 1 else mask
 
     def forward(self, x):
         if np.random.rand() > self.prob or not self.training:

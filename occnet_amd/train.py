@@ -58,17 +58,19 @@ def synthetic_targets(bev_h, bev_w, pillar_h, num_classes=18, batch=1, seed=0, d
 
 
 def train_step(model, optimizer, img, img_metas, voxel_semantics, voxel_flow, mask_camera,
-               max_norm=35.0, autocast_backbone=False):
+               max_norm=35.0, autocast_backbone=False, img_u8=None, img_norm_cfg=None, img_aug=None):
     """One optimisation step; returns the rank-local loss dict (python floats are NOT synchronised:
-    call .item() on the values only when logging)."""
+    call .item() on the values only when logging).  img_u8 / img_norm_cfg / img_aug (with img=None): raw uint8
+    frames and photometric records, handed to BEVFormerOcc.forward_train."""
     net = model.module if hasattr(model, 'module') else model
     optimizer.zero_grad(set_to_none=True)
     # the stock MIOpen backbone may run in bf16 (the hand-written hot path stays fp32): a detector attribute,
     # so that the WHOLE step goes through model(...) — i.e. through DDP.forward, which arms the reducer; a
     # forward that bypasses the wrapper leaves the gradients un-reduced (each rank would diverge silently)
     net.backbone_autocast_dtype = torch.bfloat16 if autocast_backbone else None
+    u8 = {} if img_u8 is None else dict(img_u8=img_u8, img_norm_cfg=img_norm_cfg, img_aug=img_aug)
     losses = model(return_loss=True, img_metas=img_metas, img=img, voxel_semantics=voxel_semantics,
-                   voxel_flow=voxel_flow, mask_camera=mask_camera)
+                   voxel_flow=voxel_flow, mask_camera=mask_camera, **u8)
     loss = sum(losses.values())
     loss.backward()          # DDP all-reduces the gradient buckets here (overlapped with backward)
     params = [p for p in net.parameters() if p.grad is not None]
