@@ -79,9 +79,11 @@ def _need_cuda_f32(name, t, contiguous=True):
         raise OccAmdError(f"{name} must be contiguous")
 
 
-def _need_cuda_i64(name, t):
-    if not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
+def _need_cuda_i64(name, t, device=None):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
         raise OccAmdError(f"{name} must be a contiguous int64 device tensor")
+    if device is not None and t.device != device:
+        raise OccAmdError(f"{name} must be on the device of the data ({device}), got {t.device}")
 
 
 def ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
@@ -1752,13 +1754,15 @@ class LinearX3Function(torch.autograd.Function):
 
 
 def rows_gather_sum(x, index):
-    """out[b, r] = sum_k x[b, index[r, k]] over the entries with index >= 0 (csrc/rows_index.hip).  x (B, rows_in, F)
-    float32 contiguous, index (rows_out, K) int64 on the device -> (B, rows_out, F)."""
+    """out[b, r] = sum_k x[b, index[r, k]] over the entries with 0 <= index < rows_in (csrc/rows_index.hip).  x (B, rows_in, F)
+    float32 contiguous, index (rows_out, K) int64, contiguous, on x's device -> (B, rows_out, F).  An entry outside
+    [0, rows_in) contributes nothing: -1 is the padding of the rebatch maps, and an entry >= rows_in is skipped in the same
+    way, never read.  A row index that occurs twice in a row of `index` is summed twice."""
     _need_cuda_f32("x", x)
-    if x.dim() != 3 or index.dim() != 2 or index.dtype != torch.int64 or not index.is_cuda \
-            or not index.is_contiguous():
+    if x.dim() != 3 or not isinstance(index, torch.Tensor) or index.dim() != 2:
         raise OccAmdError("rows_gather_sum: x must be (B, rows, F), index a contiguous (rows_out, K) int64 device "
                           "tensor")
+    _need_cuda_i64("rows_gather_sum: index", index, x.device)
     B, rows_in, F = x.shape
     rows_out, K = index.shape
     out = torch.empty((B, rows_out, F), dtype=torch.float32, device=x.device)
@@ -1775,6 +1779,11 @@ class RowsGatherSumFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, index, inverse_index):
+        _need_cuda_f32("x", x, contiguous=False)
+        if x.dim() != 3 or not isinstance(inverse_index, torch.Tensor) or inverse_index.dim() != 2 \
+                or inverse_index.shape[0] != x.shape[1]:
+            raise OccAmdError("RowsGatherSumFunction: inverse_index must be (rows_in, K'), one row per row of x")
+        _need_cuda_i64("RowsGatherSumFunction: inverse_index", inverse_index, x.device)
         ctx.save_for_backward(inverse_index)
         return rows_gather_sum(x.contiguous(), index)
 
@@ -1796,8 +1805,17 @@ class SCAPrepFunction(torch.autograd.Function):
     def forward(ctx, proj, row_to_query, query_to_rows, ref_rb, spatial_shapes, M, L, P):
         _need_cuda_f32("proj", proj)
         _need_cuda_f32("ref_rb", ref_rb)
+        if proj.dim() != 3 or ref_rb.device != proj.device:
+            raise OccAmdError("SCAPrepFunction: proj must be (B, Q, ld), ref_rb on its device")
+        for n, t in (("row_to_query", row_to_query), ("query_to_rows", query_to_rows), ("spatial_shapes", spatial_shapes)):
+            _need_cuda_i64("SCAPrepFunction: " + n, t, proj.device)
         B, Q, ld = proj.shape
+        if row_to_query.dim() != 2 or row_to_query.shape[1] != 1 or query_to_rows.dim() != 2 \
+                or query_to_rows.shape[0] != Q or query_to_rows.shape[1] < 1 or tuple(spatial_shapes.shape) != (L, 2):
+            raise OccAmdError("SCAPrepFunction: expected row_to_query (R, 1), query_to_rows (Q, K) and spatial_shapes (L, 2)")
         R = row_to_query.shape[0]
+        if ref_rb.dim() != 4 or ref_rb.shape[0] != B or ref_rb.shape[1] != R or ref_rb.shape[2] < 1 or ref_rb.shape[3] != 2:
+            raise OccAmdError(f"SCAPrepFunction: ref_rb must be ({B}, {R}, Z, 2), got {tuple(ref_rb.shape)}")
         Z = ref_rb.shape[2]
         loc = torch.empty((B, R, M, L, P, 2), dtype=torch.float32, device=proj.device)
         attn = torch.empty((B, R, M, L, P), dtype=torch.float32, device=proj.device)

@@ -41,7 +41,38 @@ The ln= epilogue of linear (csrc/linear_mfma.hip and csrc/linear_bf16x3.hip, the
   holds the mean of a row exactly.  It moves every deviation by delta and, as sum d = 0, the variance by exactly
   delta^2, so for such N the bound has two more terms:
       + delta * rstd * |gamma|  +  delta^2 / (2 (var + eps)) * |t|.
-  Both vanish for a power-of-two N, where the bound is the one above."""
+  Both vanish for a power-of-two N, where the bound is the one above.
+
+dropout_add_ln_fwd_kernel (csrc/ln_dropout_train.hip), N = 256 on 64 lanes x 4.  z = x keep scale + residual is an exact
+integer (tests/train_glue_ref.py), the row sum, the mean and d = z - mean are exact as above:
+    variance: (dx dx + dy dy) + (dz dz + dw dw), contracted to fmas or not: at most 3 roundings on any path;  wave_sum:
+      6 shuffle additions;  * (1 / 256): exact;  + eps: 1.   10 U, at half weight:                          5 U
+    rsqrtf:                                                                                                 4 U
+    d * rstd:                                                                                               1 U
+    fmaf(., gamma, beta): its one rounding is the U |y| term.
+    c = 10 -> C_TRAIN_LN = 11.
+  The stored rstd is off by the first two lines, 9 U: RSTD_ROUNDINGS.
+
+dropout_add_ln_bwd_kernel, per element, with zh = d rstd, w = gy gamma, c1 = mean_c(w), c2 = mean_c(w zh) in float64:
+  g_residual = rstd (w - c1 - zh c2).  The kernel's h = d * rstd: 9 U + its product 1 U = 10 U |zh|.
+    w = gy * gamma:                                                                       1 U |w|
+    c1: the terms 1 U each, (wx + wy) + (wz + ww) 2 additions, wave_sum 6:                9 U mean|w|
+    c2: a term w h is 1 + 10 + 1 (its product) = 12 U, the same 8 additions:             20 U mean|w zh|
+    h * c2: 10 + 20 + 1 (the product, unless contracted):                                31 U |zh| mean|w zh|
+    (w - c1) - h c2: two roundings, each at most U (|w| + mean|w| + |zh| mean|w zh|)
+    rstd * (.): 9 U of rstd + 1 for the product, on the same sum of magnitudes:          10 U
+  |w|: 1 + 2 + 10 = 13, mean|w|: 9 + 2 + 10 = 21, |zh| mean|w zh|: 31 + 2 + 10 = 43.  The largest covers all three:
+    |got - g_residual|  <=  C_TRAIN_GRES U rstd (|w| + mean|w| + |zh| mean|w zh|),   c = 43 -> C_TRAIN_GRES = 44.
+  dgamma = sum_rows gy zh.  A term gy * h carries the 10 U of h.  The longest addition chain on any path, at no more than
+  8197 rows (1024 blocks of 4 waves, at most 3 rows per wave):
+    dg = fmaf(gy, h, dg) per row of the wave:                                             3
+    (red[0] + red[1]) + (red[2] + red[3]) of the block:                                   2
+    ln_colsum_reduce_kernel: s0 takes 1024 / 32 = 32 terms in the unrolled loop and up to 3 in its tail:  35
+    (s0 + s1) + (s2 + s3):                                                                2
+    the 8 row groups, one after the other:                                                7
+    49 additions, each at most U of a partial sum of magnitudes, and the 10 U of h:
+    |got - dgamma|  <=  C_TRAIN_DGAMMA U sum_rows |gy zh|,                             c = 59 -> C_TRAIN_DGAMMA = 60.
+  dbeta = sum_rows gy has no bound: with |gy| <= 8 every partial sum is an integer below 2^24, the sum is exact."""
 import torch
 
 from tests import exact_cases as ec
@@ -52,6 +83,10 @@ C_CHAIN = 24
 C_LINEAR = 12
 C_LINEAR_INEXACT = 14
 MEAN_ROUNDINGS = 3
+C_TRAIN_LN = 11
+RSTD_ROUNDINGS = 9
+C_TRAIN_GRES = 44
+C_TRAIN_DGAMMA = 60
 EPS = float(torch.tensor(1e-5, dtype=torch.float32))          # the fp32 value the kernels add
 
 ORDINARY, OFFSET, NEAR_CONSTANT, CONSTANT = 0, 1, 2, 3

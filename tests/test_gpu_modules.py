@@ -28,16 +28,26 @@ def test_point_sampling_matches_oracle():
     assert torch.equal(ref_3d_g.cpu(), ref_3d)      # host-evaluated grid: bit-identical
     rc, m, vis = BEVFormerEncoder.point_sampling(enc, ref_3d_g, pcr, metas, return_vis=True)
     m, rc, vis = m.cpu(), rc.cpu(), vis.cpu()
+    # float64 from the same fp32 inputs, with the set of points whose mask the kernel's roundings cannot flip
+    # (tests/train_glue_ref.py): the mask may differ from the oracle's or from float64 at an undecidable point, nowhere else
+    from tests import train_glue_ref as tg
+    r64 = tg.point_sampling_ref(ref_3d, torch.from_numpy(np.asarray([mt['lidar2img'] for mt in metas], dtype=np.float32)),
+                                torch.from_numpy(np.asarray(metas[0]['ego2lidar'], dtype=np.float32)), pcr,
+                                metas[0]['img_shape'][0][0], metas[0]['img_shape'][0][1])
+    undecidable = int((~r64.decidable).sum())
+    assert undecidable <= tg.POINT_CAP * m.numel()
+    ratio = tg.assert_point_sampling(rc, m, vis, r64)
     mism = int((m != m_o).sum())
-    print(f"bev_mask mismatches: {mism} of {m.numel()}")
-    assert mism <= 4            # fp32 rounding may flip a point that sits exactly on an image border
+    print(f"bev_mask mismatches: {mism} of {m.numel()} ({undecidable} undecidable); ref_cam err / bound vs float64 {ratio:.3f}")
+    assert not bool(((m != m_o) & r64.decidable).any())
     # coordinates agree wherever the point is in front of the camera (elsewhere they are x/1e-5 huge)
     front = m_o | (rc_o.abs().amax(-1) < 4.0)
     rel = ((rc - rc_o).abs() / (1.0 + rc_o.abs()))[front].max()
     print(f"ref_cam max rel diff (in front): {float(rel):.3e}")
     assert float(rel) < 1e-5
     bits = sum((m_o[c].any(-1).long() << c) for c in range(m_o.shape[0]))
-    assert int((vis.long() != bits).sum()) <= 4
+    q_ok = r64.decidable.all(-1).all(0)              # queries none of whose points is undecidable
+    assert not bool(((vis.long() != bits) & q_ok).any())
     rows = [int(m_o[c, 0].any(-1).sum()) for c in range(6)]
     print("visible queries per camera:", rows, "total", sum(rows))
 

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from occnet_amd import synthetic
+from tests.train_glue_ref import keep_mask as _keep_mask          # host restatement of csrc/ln_dropout_train.hip's keep decision
 from tests.util import build_pair, small_cfg
 
 pytestmark = pytest.mark.gpu
@@ -389,19 +390,6 @@ def test_data_copy_before_eval_is_caught_by_the_content_fingerprint():
     n0.data.fill_(0.75), n1.data.fill_(1.25)                # the two tensors swap contents: same multiset of norms
     model.eval()
     assert occnet_amd.cache_epoch() > e3
-
-
-def _keep_mask(n, seed, p):
-    """numpy restatement of csrc/ln_dropout_train.hip's keep decision for elements 0 .. n-1."""
-    import numpy as np
-    i = np.arange(n, dtype=np.uint32)
-    s0, s1 = np.uint32(seed & 0xffffffff), np.uint32(seed >> 32)
-    with np.errstate(over='ignore'):
-        h = i ^ s0
-        h ^= h >> np.uint32(16); h *= np.uint32(0x85ebca6b); h ^= h >> np.uint32(13); h *= np.uint32(0xc2b2ae35); h ^= h >> np.uint32(16)
-        h += s1
-        h ^= h >> np.uint32(15); h *= np.uint32(0x2c1b3c6d); h ^= h >> np.uint32(12)
-    return h >= np.uint32(int(p * 4294967296.0))
 
 
 @pytest.mark.parametrize("p", [0.0, 0.1])
