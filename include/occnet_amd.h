@@ -839,6 +839,27 @@ int occ_bottleneck64_nhwc_bf16_variant(const void* x, const void* w1_frag, const
  * pure function, needs no GPU.  Bad arguments: OCC_E_INVALID (negative). */
 int occ_bottleneck64_tile_of_block(int block, int n_blocks, int tiles_x, int tiles_y, int order);
 
+/* The last identity bottleneck (Cin 256) of a stage whose output only feeds the next stage's first block, with that block's
+ * two pointwise readers computed on the tile before it leaves the CU (csrc/bottleneck64_next_nhwc_bf16.hip); the
+ * 256-channel map out = bottleneck64(x) is NOT written:
+ *   y        = relu( conv1x1(out, W1n) + b1n )            (batch, H, W, cmid_next) bf16
+ *   shortcut = conv1x1(out, Wds, stride 2) + bds          (batch, (H-1)/2+1, (W-1)/2+1, 4 cmid_next) bf16
+ *   x (batch, H, W, 256) bf16 ; w1_frag .. b3 as occ_bottleneck64_nhwc_bf16 with downsample == 0 ;
+ *   next_w1_frag = occ_mfma_pack_b_frag_bf16 of W1n (cmid_next, 256) ; next_b1 (cmid_next) f32 ;
+ *   next_wds_frag = occ_mfma_pack_b_frag_bf16 of Wds (4 cmid_next, 256) ; next_bds (4 cmid_next) f32.
+ * cmid_next must be 128, otherwise OCC_E_UNSUPPORTED.  Bit-identical to occ_bottleneck64_nhwc_bf16_variant 2 followed by
+ * occ_conv1x1_nhwc_bf16_variant 2 with relu = 1 and by occ_conv1x1_nhwc_bf16_variant 2 with stride = 2, for every shape.
+ * Argument checks run before any launch. */
+int occ_bottleneck64_next_nhwc_bf16(const void* x, const void* w1_frag, const float* b1, const void* w2_frag,
+                                    const float* b2, const void* w3_frag, const float* b3, const void* next_w1_frag,
+                                    const float* next_b1, const void* next_wds_frag, const float* next_bds, void* y,
+                                    void* shortcut, int batch, int H, int W, int cmid_next, void* stream);
+/* Non-zero where a plan should take the entry point above for a (batch, H, W, 256) map: a kernel exists for cmid_next and
+ * BOTH 1x1 launches it replaces would run the activation-resident kernel under occ_conv1x1_nhwc_bf16's default rule
+ * (M >= 512 at full resolution and at stride 2), so that the fused launch returns the bits of the route it replaces.
+ * A pure function of its arguments; needs no GPU. */
+int occ_bottleneck64_next_pick(int batch, int H, int W, int cmid_next);
+
 /* ------------------------------------------------------------------------------------------
  * (e) Evaluation: RayIoU / mAVE counters of a batch of samples in one fused pass (csrc/ray_metrics_fused.hip) — the
  * reference's process_one_sample + main's non-free filter + calc_metrics (projects/mmdet3d_plugin/datasets/

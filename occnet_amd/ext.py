@@ -2558,6 +2558,60 @@ def bottleneck64_nhwc(x, pack, variant=0, out=None):
     return out
 
 
+def bottleneck64_next_pick(batch, H, W, cmid_next):
+    """True where bottleneck64_next_nhwc replaces bottleneck64_nhwc + the two conv1x1_nhwc launches behind it for a
+    (batch, 256, H, W) map (occ_bottleneck64_next_pick: a kernel for cmid_next, and both 1x1 launches on the resident
+    kernel by the launcher's default rule; a pure function of the shape, needs no GPU)."""
+    return bool(_lib.lib().occ_bottleneck64_next_pick(i32(batch), i32(H), i32(W), i32(int(cmid_next))))
+
+
+def bottleneck64_next_nhwc(x, pack, w1_frag, b1, wds_frag, bds, out=None):
+    """The last identity bottleneck of a stage and the two pointwise readers of its output in the next stage's first
+    block, one launch; the 256-channel map stays on chip.
+    x (N, 256, H, W) channels_last bf16; pack from bottleneck64_pack (identity block); w1_frag = conv1x1_pack_weight of the
+    next conv1 (cmid, 256), b1 (cmid) f32; wds_frag = conv1x1_pack_weight of the next downsample (4 cmid, 256), bds (4 cmid)
+    f32; cmid = 128
+    -> (y, shortcut): y = relu(conv1(block(x))) (N, cmid, H, W), shortcut = downsample(block(x)) at stride 2
+    (N, 4 cmid, (H-1)//2+1, (W-1)//2+1), both channels_last bf16.
+    out: a (y, shortcut) pair of such tensors on x's device to write into (every element is written), or None.
+    Bit-identical to bottleneck64_nhwc(x, pack, variant=2), then conv1x1_nhwc(., w1_frag, b1, relu=True, variant=2) and
+    conv1x1_nhwc(., wds_frag, bds, stride=2, variant=2)."""
+    _need_cl_bf16("bottleneck64_next_nhwc", "x", x)
+    _need_cuda_f32("b1", b1)
+    _need_cuda_f32("bds", bds)
+    N, Cin, H, W = x.shape
+    if Cin != 256 or pack['cin'] != 256 or pack['ds']:
+        raise OccAmdError("bottleneck64_next_nhwc: x must have 256 channels and the pack be an identity block's")
+    cmid = b1.numel()
+    for name, wf, cout in (("w1_frag", w1_frag, cmid), ("wds_frag", wds_frag, 4 * cmid)):
+        if not (isinstance(wf, torch.Tensor) and wf.is_cuda and wf.dtype == torch.int16 and wf.dim() == 1
+                and wf.is_contiguous() and wf.numel() == cout * 256):
+            raise OccAmdError(f"bottleneck64_next_nhwc: {name} must come from conv1x1_pack_weight ({cout}*256 bf16, "
+                              "fragment order)")
+    if bds.numel() != 4 * cmid:
+        raise OccAmdError("bottleneck64_next_nhwc: bds must have 4 * cmid entries")
+    shapes = ((N, cmid, H, W), (N, 4 * cmid, (H - 1) // 2 + 1, (W - 1) // 2 + 1))
+    if out is None:
+        y, sc = (torch.empty(s, dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last) for s in shapes)
+    else:
+        y, sc = out
+        for name, t, s in (("out[0]", y, shapes[0]), ("out[1]", sc, shapes[1])):
+            _need_cl_bf16("bottleneck64_next_nhwc", name, t)
+            if tuple(t.shape) != s or t.device != x.device:
+                raise OccAmdError(f"bottleneck64_next_nhwc: {name} must be a {s} tensor on x's device")
+        if len({y.data_ptr(), sc.data_ptr(), x.data_ptr()}) != 3:
+            raise OccAmdError("bottleneck64_next_nhwc: x and the two outputs must be distinct tensors")
+    with torch.cuda.device(x.device), _timed('bb_bottleneck64'):
+        rc = _lib.lib().occ_bottleneck64_next_nhwc_bf16(ptr(x), ptr(pack['w1']), ptr(pack['b1']), ptr(pack['w2']),
+                                                        ptr(pack['b2']), ptr(pack['w3']), ptr(pack['b3']), ptr(w1_frag),
+                                                        ptr(b1), ptr(wds_frag), ptr(bds), ptr(y), ptr(sc), i32(N), i32(H),
+                                                        i32(W), i32(cmid), stream_ptr(x.device))
+    _note_flops('bb_bottleneck64', 2.0 * N * H * W * (256 * 64 + 9 * 64 * 64 + 64 * 256 + 256 * cmid)
+                + 2.0 * N * shapes[1][2] * shapes[1][3] * 256 * 4 * cmid)
+    _lib.check(rc, "bottleneck64_next_nhwc")
+    return y, sc
+
+
 def conv3x3_pack_weight(weight):
     """torch Conv2d weight (Cout, Cin, 3, 3) float32 -> packed bf16 [Cin/32][tap][co][32] (int16 storage)."""
     _need_cuda_f32("weight", weight)

@@ -79,15 +79,22 @@ class FusedInferenceBackbone(nn.Module):
     convolution (`fuse_conv_bn_weights`), bf16, channels_last (NHWC) memory end to end, so the FPN outputs are
     already in the (Cam, H, W, C) layout the hot path reads.  With `hip_tail` (bf16, default) every layer of the
     configs' ResNet-50 + FPN runs on this repository's kernels: whole stem (ext.stem_conv7x7_pool), whole
-    64-mid-channel bottlenecks (ext.bottleneck64_nhwc), 1x1 / 3x3 convolutions with bias, residual and ReLU fused
-    (ext.conv1x1_nhwc incl. the FPN top-down step, ext.conv3x3_nhwc); convolutions of other shapes fall back to
+    64-mid-channel bottlenecks (ext.bottleneck64_nhwc; with `fuse_next_stage` the last one of a stage that is no FPN input
+    also computes the next block's conv1 and shortcut, ext.bottleneck64_next_nhwc), 1x1 / 3x3 convolutions with bias,
+    residual and ReLU fused (ext.conv1x1_nhwc incl. the FPN top-down step, ext.conv3x3_nhwc); convolutions of other shapes fall back to
     MIOpen + one fused bias/residual/ReLU launch.  `hip_tail=False` keeps stock torch ops (any dtype).  Built from the
     live modules' parameters (it owns folded COPIES: rebuild after changing weights).  The backbone is outside
     SURVEY.md §8's hand-written scope; these kernels exist because end-to-end samples/s (images -> voxels) is the
     headline metric."""
 
-    def __init__(self, backbone, neck, dtype=torch.bfloat16, hip_tail=True, fused_bottleneck=True, prefix_stages=None):
+    def __init__(self, backbone, neck, dtype=torch.bfloat16, hip_tail=True, fused_bottleneck=True, prefix_stages=None,
+                 fuse_next_stage=False):
         super().__init__()
+        # fuse_next_stage: a stage's last whole bottleneck also computes the next stage's conv1 and shortcut where
+        # _next_block_operands allows it (the same bits, two launches and the stage's output map less).  Opt-in: a plan
+        # built without it launches every block's convolutions one by one, as callers that watch or replace those
+        # launches expect; the model's enable_fused_backbone asks for it.
+        self.fuse_next_stage = bool(fuse_next_stage)
         # prefix_stages = k: fold only the stem and the first k stages, no neck (forward_prefix: the frozen part of
         # a training step)
         self.prefix_stages = prefix_stages
@@ -225,10 +232,46 @@ class FusedInferenceBackbone(nn.Module):
             x = F.max_pool2d(self._conv(stem, x, relu=True), kernel_size=3, stride=2, padding=1)
         return self._forward_stages(x)
 
-    def _run_stage(self, si, x):
+    def _next_block_operands(self, si):
+        """(conv1, downsample) records of stage si + 1's first block where stage si's last launch can compute both
+        (ext.bottleneck64_next_nhwc), else None.  The conditions that do not depend on the input: the plan was built with
+        fuse_next_stage; the last block of the stage is a whole identity bottleneck; its output has no other reader (the stage is not an FPN input and the plan does not
+        end there); and the two readers are a stride-1 conv1 (256 -> cmid) and a stride-2 1x1 downsample (256 -> 4 cmid) on
+        the own 1x1 kernel."""
+        whole = self._bneck.get((si, len(self.stages[si]) - 1)) if self.fuse_next_stage else None
+        if whole is None or whole['ds'] or whole['cin'] != 256:
+            return None
+        if si in self.out_indices or si + 1 >= len(self.stages):
+            return None
+        c1, _, _, ds = self.stages[si + 1][0]
+        if ds is None or c1.kind != '1x1' or ds.kind != '1x1':
+            return None
+        if tuple(c1.stride) != (1, 1) or tuple(ds.stride) != (2, 2) or c1.weight.shape[1] != 256 \
+                or ds.weight.shape[1] != 256 or ds.cout != 4 * c1.cout:
+            return None
+        return c1, ds
+
+    def _run_stage(self, si, x, head=None, fuse_next=True):
+        """One stage -> (x, head).  head = (y, identity) of the NEXT stage's first block when this stage's last launch
+        computed them in place of its own output (x is then None), else None; the `head` argument is what the previous
+        stage handed over.  fuse_next=False keeps every stage's own output (forward_prefix)."""
+        last = len(self.stages[si]) - 1
         for bi, (c1, c2, c3, ds) in enumerate(self.stages[si]):
+            if bi == 0 and head is not None:
+                y, identity = head
+                fused = self._conv23_fused(c2, c3, y, identity)
+                x = fused if fused is not None else self._conv(c3, self._conv(c2, y, relu=True), add=identity)
+                continue
             whole = self._bneck.get((si, bi))
             if whole is not None and x.is_contiguous(memory_format=_CL):
+                # OCC_BOTTLENECK64_NEXT=0 keeps the block's own output and the two 1x1 launches (development A/B inside one
+                # build; the same bits)
+                nxt = self._next_block_operands(si) if fuse_next and bi == last else None
+                if nxt is not None and not os.environ.get('OCC_BOTTLENECK64_NEXT', '1').startswith('0') \
+                        and x.dtype == torch.bfloat16 \
+                        and ext.bottleneck64_next_pick(x.shape[0], x.shape[2], x.shape[3], nxt[0].cout):
+                    n1, nds = nxt
+                    return None, ext.bottleneck64_next_nhwc(x, whole, n1.pack, n1.bias, nds.pack, nds.bias)
                 # OCC_BOTTLENECK64_V2=0 keeps the first kernel (development A/B inside one build; the same bits)
                 first = os.environ.get('OCC_BOTTLENECK64_V2', '1').startswith('0')
                 x = ext.bottleneck64_nhwc(x, whole, variant=1 if first else 0)
@@ -237,7 +280,7 @@ class FusedInferenceBackbone(nn.Module):
             y = self._conv(c1, x, relu=True)
             fused = self._conv23_fused(c2, c3, y, identity)
             x = fused if fused is not None else self._conv(c3, self._conv(c2, y, relu=True), add=identity)
-        return x
+        return x, None
 
     def _conv23_fused(self, c2, c3, y, identity):
         """conv2 (3x3) + conv3 (1x1 + residual + ReLU) as one launch where ext.conv3x3_conv1x1_pick fuses the shape
@@ -260,13 +303,14 @@ class FusedInferenceBackbone(nn.Module):
         """x (N, 3, H, W) fp32 contiguous -> activation after the folded stages, (N, C, h, w) bf16 channels_last."""
         x = ext.stem_conv7x7_pool(x, self.stem_frag, self.stem.bias)
         for si in range(len(self.stages)):
-            x = self._run_stage(si, x)
+            x, _ = self._run_stage(si, x, fuse_next=False)
         return x
 
     def _forward_stages(self, x):
         feats = []
+        head = None
         for si in range(len(self.stages)):
-            x = self._run_stage(si, x)
+            x, head = self._run_stage(si, x, head)
             if si in self.out_indices:
                 feats.append(x)
         nk = self.neck

@@ -160,20 +160,23 @@ class BEVFormerOcc(BaseModule):
                     ext.attach_absmax(out[-1], am)
         return out
 
-    def enable_fused_backbone(self, dtype=torch.bfloat16, hip_tail=True, use_graph=False, fused_bottleneck=True):
+    def enable_fused_backbone(self, dtype=torch.bfloat16, hip_tail=True, use_graph=False, fused_bottleneck=True,
+                              fuse_next_stage=True):
         """Inference-only: run ResNet+FPN through FusedInferenceBackbone (eval BN folded into the
         convolutions, NHWC; with hip_tail on bf16 the stem, the 64-channel bottlenecks and the 1x1 / 3x3
-        convolutions run on this repository's kernels with bias, residual and ReLU in their epilogues).  Call again
+        convolutions run on this repository's kernels with bias, residual and ReLU in their epilogues; with fuse_next_stage
+        the last layer1 block also computes layer2's first conv1 and shortcut).  Call again
         after changing backbone weights; pass dtype=None to disable."""
         from .backbone import FusedInferenceBackbone
         object.__setattr__(self, '_inference_backbone', None)
         object.__setattr__(self, '_inference_backbone_args', dict(
-            dtype=dtype, hip_tail=hip_tail, use_graph=use_graph, fused_bottleneck=fused_bottleneck))
+            dtype=dtype, hip_tail=hip_tail, use_graph=use_graph, fused_bottleneck=fused_bottleneck,
+            fuse_next_stage=fuse_next_stage))
         # folded while training (no explicit .train() call needed for that): the sources may move before the first forward
         object.__setattr__(self, '_plan_dirty', bool(self.training))
         if dtype is not None:
             plan = FusedInferenceBackbone(self.img_backbone, self.img_neck, dtype=dtype, hip_tail=hip_tail,
-                                          fused_bottleneck=fused_bottleneck)
+                                          fused_bottleneck=fused_bottleneck, fuse_next_stage=fuse_next_stage)
             plan.use_graph = use_graph
             plan.built_epoch = cache_epoch()
             plan.signature = self._backbone_signature()

@@ -41,7 +41,7 @@ if args.mode == "plan":
             m.running_var.copy_(torch.rand(m.running_var.shape, generator=g).cuda() * 0.5 + 0.75)
     with torch.no_grad():
         ref = [t.float() for t in neck(bb(x[:1]))]
-    plan = FusedInferenceBackbone(bb, neck, dtype=torch.bfloat16)
+    plan = FusedInferenceBackbone(bb, neck, dtype=torch.bfloat16, fuse_next_stage=True)
     with torch.no_grad():
         got = plan(x[:1])
     for a, b in zip(ref, got):
