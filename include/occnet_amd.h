@@ -30,6 +30,8 @@
  *   occ_linear_f32                   <- the nn.Linear / FFN / LayerNorm call sites of a BEVFormerLayer
  *   occ_dvr_render_forward_f32       <- dvr.render_forward, tools/ray_iou/lib/dvr/dvr.cu:70-388
  *   occ_ray_metrics_accumulate       <- process_one_sample + main + calc_metrics, P/datasets/ray_metrics.py:89-257
+ *   occ_submission_rays              <- NuSceneOcc.format_results' per-sample loop (process_one_sample + the int8 / float16
+ *        casts), P/datasets/nuscenes_occ.py:217-241
  *   occ_heads_loss_fwd_f32 / _bwd_f32 <- the heads (transformer_occ.py:132-141,318-319) + BEVFormerOccHead.loss /
  *        loss_single, P/bevformer/dense_heads/bevformer_occ_head.py:163-196, and their autograd backward
  */
@@ -894,6 +896,38 @@ int occ_ray_metrics_accumulate(const void* sem_pred, int sem_pred_dtype, const f
                                int64_t* state, float* rows_pred, float* rows_gt, void* workspace,
                                int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R,
                                void* stream);
+
+/* Submission rows of a batch of predictions in one launch pair (csrc/submission_rays.hip) — the per-sample loop of the
+ * reference's format_results (projects/mmdet3d_plugin/datasets/nuscenes_occ.py:217-241: process_one_sample, then
+ * astype(np.int8) / astype(np.float16)) without a host round trip: occupancy bit masks of the prediction, the ray cast of
+ * occ_ray_metrics_accumulate (the same text: csrc/ray_cast.h), class / flow read at the reported voxel, packed.
+ *   sem_pred (B, X, Y, Z) class ids, dtype code 0 = uint8, 1 = int64; flow_pred (B, X, Y, Z, 2) f32
+ *   origins (B, Tmax, 3) lidar origins in ego metres, 1 <= Tmax <= 8, origins_dtype 0 = float32, 1 = float64.  The
+ *                    conversion to voxel units follows the type as process_one_sample's tensor arithmetic does: float32
+ *                    origins -> float32 `ray + origin` and `(p - off) / voxel_size`, exactly as occ_ray_metrics_accumulate;
+ *                    float64 origins (what the reference's EgoPoseDataset yields) -> those statements in float64, rounded to
+ *                    float32 once.
+ *   origin_counts (B) i32 DEVICE or NULL, rays (R, 3) f32, off_x/y/z, voxel_size, free_id in 1..31: as above
+ *   out              occ_submission_rays_bytes(B, Tmax, R) bytes, 4-byte aligned: three sections, each starting on a
+ *                    256-byte boundary, N = B * Tmax * R rows, row (b * Tmax + t) * R + r (process_one_sample's order):
+ *                      cls  int8[N]     at 0                             low 8 bits of the class id: ids 0..127 are what
+ *                                       the host path defines; above that the C cast behind numpy's astype(np.int8) is
+ *                                       undefined — the rule HERE is two's-complement wrap (200 -> -56)
+ *                      dist fp16[N]     at align256(N)                   float32(distance * voxel_size) rounded to nearest
+ *                                       even, overflow -> inf; a ray that never enters the grid: -1 * voxel_size, voxel (0,0,0)
+ *                      flow fp16[N][2]  at align256(N) + align256(2 N)   rounded the same way
+ *                    rows of origins beyond origin_counts[b] are NOT written.
+ *   workspace        occ_submission_rays_workspace_bytes(B, X, Y, Z) bytes, 4-byte aligned, uninitialised: the prediction's
+ *                    pillar masks (uint16 for Z <= 16, uint32 for Z <= 32).  Z > 32: OCC_E_UNSUPPORTED (both queries that
+ *                    take Z answer 0).
+ * Two launches on `stream`, no synchronisation, no allocation, no copy.  Every argument is checked before the first launch.
+ */
+int64_t occ_submission_rays_bytes(int B, int Tmax, int R);
+int64_t occ_submission_rays_workspace_bytes(int B, int X, int Y, int Z);
+int occ_submission_rays(const void* sem_pred, int sem_pred_dtype, const float* flow_pred, const void* origins,
+                        int origins_dtype, const int32_t* origin_counts, const float* rays, float off_x, float off_y,
+                        float off_z, float voxel_size, int free_id, void* out, int64_t out_bytes, void* workspace,
+                        int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (f) Training tail: both occupancy heads AND their losses as one node (csrc/occ_heads_loss.hip) — the reference's

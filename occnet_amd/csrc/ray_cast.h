@@ -1,0 +1,124 @@
+// The ray caster shared by the device-resident evaluation (ray_metrics_fused.hip) and the submission writer
+// (submission_rays.hip): class read, occupancy bit masks per pillar, the origin / end-point conversion of process_one_sample,
+// the traversal set-up of csrc/dvr_render.hip and its "test"-phase walk over the masks.  One copy of the text: both files
+// report the same voxel and the same distance for the same ray, bit for bit.
+//
+// Lane predicates that select a load address are kept as 0 / 1 integers (common.h: lane_flag) and every load inside the
+// traversal is issued with a clamped, always-legal index; the traversal of a lane that is not cast runs zero steps.
+#pragma once
+#include <float.h>
+#include "common.h"
+
+namespace occ {
+
+__device__ __forceinline__ int rm_class_at(const void* __restrict__ sem, int is_i64, long i) {
+  if (!is_i64) return (int)static_cast<const unsigned char*>(sem)[i];
+  const long long v = static_cast<const long long*>(sem)[i];
+  return (v < -2147483647ll || v > 2147483647ll) ? -1 : (int)v;      // beyond int: occupied, counted in no class
+}
+
+// One thread per pillar of one grid: bit z set iff class(x, y, z) != free_id.  grid 0 = prediction, 1 = ground truth
+// (a launch with gridDim.y == 1 builds the prediction's masks only and never reads sem_gt).
+template <typename MaskT>
+__global__ __launch_bounds__(256) void ray_metrics_occupancy_kernel(
+    const void* __restrict__ sem_pred, int pred_i64, const void* __restrict__ sem_gt, int gt_i64,
+    MaskT* __restrict__ masks, long pillars, int Z, int free_id) {
+  const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (p >= pillars) return;
+  const int g = blockIdx.y;
+  const void* sem = g ? sem_gt : sem_pred;
+  const int is_i64 = g ? gt_i64 : pred_i64;
+  unsigned m = 0;
+  for (int z = 0; z < Z; ++z) m |= (rm_class_at(sem, is_i64, p * Z + z) != free_id ? 1u : 0u) << z;
+  masks[(long)g * pillars + p] = (MaskT)m;
+}
+
+struct RmHit {
+  float dist;       // ray parameter (voxel units) at which the ray leaves the reported voxel; -1: never entered the grid
+  int x, y, z;
+};
+
+struct RmRay {      // per-ray constants of the traversal (dvr_render_forward_kernel's set-up)
+  int vx, vy, vz, stepX, stepY, stepZ;
+  double tMaxX, tMaxY, tMaxZ, tDeltaX, tDeltaY, tDeltaZ;
+};
+
+#pragma clang fp contract(off)
+__device__ __forceinline__ RmRay rm_ray_setup(float fxo, float fyo, float fzo, float fxe, float fye, float fze) {
+#pragma clang fp contract(off)
+  RmRay r;
+  const double xo = fxo, yo = fyo, zo = fzo;
+  const double xe = fxe, ye = fye, ze = fze;
+  r.vx = (int)xo; r.vy = (int)yo; r.vz = (int)zo;
+  const double rx = xe - xo, ry = ye - yo, rz = ze - zo;
+  const double gt_d = sqrt(rx * rx + ry * ry + rz * rz);
+  const double dx = rx / gt_d, dy = ry / gt_d, dz = rz / gt_d;
+  r.stepX = (dx >= 0) ? 1 : -1; r.stepY = (dy >= 0) ? 1 : -1; r.stepZ = (dz >= 0) ? 1 : -1;
+  const double bx = r.vx + (r.stepX < 0 ? 0 : 1), by = r.vy + (r.stepY < 0 ? 0 : 1), bz = r.vz + (r.stepZ < 0 ? 0 : 1);
+  r.tMaxX = (dx != 0) ? (bx - xo) / dx : DBL_MAX;
+  r.tMaxY = (dy != 0) ? (by - yo) / dy : DBL_MAX;
+  r.tMaxZ = (dz != 0) ? (bz - zo) / dz : DBL_MAX;
+  r.tDeltaX = (dx != 0) ? r.stepX / dx : DBL_MAX;
+  r.tDeltaY = (dy != 0) ? r.stepY / dy : DBL_MAX;
+  r.tDeltaZ = (dz != 0) ? r.stepZ / dz : DBL_MAX;
+  return r;
+}
+
+// process_one_sample's conversion of a lidar origin o (ego metres) and a ray d to voxel units, then the set-up.  The arithmetic
+// follows the origin's type as torch's promotion does there: float32 origins -> float32 end = ray + origin and
+// (p - offset) / scaler in float32; float64 origins (what io.lidar_origins returns) -> the same statements in float64, rounded
+// to float32 once.
+__device__ __forceinline__ RmRay rm_ray_from_origin(float ox, float oy, float oz, float dx, float dy, float dz, float off_x,
+                                                    float off_y, float off_z, float voxel_size) {
+#pragma clang fp contract(off)
+  const float ex = dx + ox, ey = dy + oy, ez = dz + oz;
+  return rm_ray_setup((ox - off_x) / voxel_size, (oy - off_y) / voxel_size, (oz - off_z) / voxel_size,
+                      (ex - off_x) / voxel_size, (ey - off_y) / voxel_size, (ez - off_z) / voxel_size);
+}
+__device__ __forceinline__ RmRay rm_ray_from_origin(double ox, double oy, double oz, float dx, float dy, float dz, float off_x,
+                                                    float off_y, float off_z, float voxel_size) {
+#pragma clang fp contract(off)
+  const double ex = (double)dx + ox, ey = (double)dy + oy, ez = (double)dz + oz;
+  const double fx = off_x, fy = off_y, fz = off_z, s = voxel_size;
+  return rm_ray_setup((float)((ox - fx) / s), (float)((oy - fy) / s), (float)((oz - fz) / s),
+                      (float)((ex - fx) / s), (float)((ey - fy) / s), (float)((ez - fz) / s));
+}
+
+// "test"-phase traversal over one grid's pillar masks (X * Y words, pillar (x, y) at x * Y + y).  live == 0: zero steps.
+template <typename MaskT>
+__device__ __forceinline__ RmHit rm_cast(const RmRay& r, const MaskT* __restrict__ masks, int X, int Y, int Z, int live) {
+#pragma clang fp contract(off)
+  int vx = r.vx, vy = r.vy, vz = r.vz;
+  double tMaxX = r.tMaxX, tMaxY = r.tMaxY, tMaxZ = r.tMaxZ;
+  int was_inside = 0;
+  double last_d = 0.0;
+  int lx = 0, ly = 0, lz = 0;
+  const int last_step = live ? 1000 : -1;     // MAX_STEP = 1000: the reference runs steps 0..1000
+  for (int step = 0; step <= last_step; ++step) {
+    const int inside = lane_flag(0 <= vx) & lane_flag(vx < X) & lane_flag(0 <= vy) & lane_flag(vy < Y) &
+                       lane_flag(0 <= vz) & lane_flag(vz < Z);
+    if (!inside && was_inside) break;         // left the grid: never comes back
+    const int cx = vx, cy = vy, cz = vz;
+    double d;
+    if (tMaxX < tMaxY) {
+      if (tMaxX < tMaxZ) { d = tMaxX; vx += r.stepX; tMaxX += r.tDeltaX; }
+      else { d = tMaxZ; vz += r.stepZ; tMaxZ += r.tDeltaZ; }
+    } else {
+      if (tMaxY < tMaxZ) { d = tMaxY; vy += r.stepY; tMaxY += r.tDeltaY; }
+      else { d = tMaxZ; vz += r.stepZ; tMaxZ += r.tDeltaZ; }
+    }
+    const int pillar = inside ? cx * Y + cy : 0;                 // always a legal word
+    const unsigned m = (unsigned)masks[pillar];
+    if (inside) {
+      was_inside = 1;
+      last_d = d; lx = cx; ly = cy; lz = cz;
+      if ((m >> cz) & 1u) break;              // first occupied voxel: nothing after it matters in the "test" phase
+    }
+  }
+  RmHit h;
+  h.dist = was_inside ? (float)last_d : -1.f;
+  h.x = lx; h.y = ly; h.z = lz;
+  return h;
+}
+
+}  // namespace occ

@@ -2068,6 +2068,90 @@ def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins,
     return (rows_pred, rows_gt) if return_rays else None
 
 
+def _align256(n):
+    return (int(n) + 255) // 256 * 256
+
+
+def submission_rays_layout(B, Tmax, R):
+    """Byte offsets of the packed submission buffer's sections -> (N, off_cls, off_dist, off_flow, total); N = B * Tmax * R
+    rows, every section on a 256-byte boundary (include/occnet_amd.h)."""
+    n = int(B) * int(Tmax) * int(R)
+    off_dist = _align256(n)
+    off_flow = off_dist + _align256(2 * n)
+    return n, 0, off_dist, off_flow, off_flow + _align256(4 * n)
+
+
+def submission_rays_bytes(B, Tmax, R):
+    return int(_lib.lib().occ_submission_rays_bytes(i32(B), i32(Tmax), i32(R)))
+
+
+def submission_rays_workspace_bytes(B, X, Y, Z):
+    return int(_lib.lib().occ_submission_rays_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z)))
+
+
+def submission_rays_views(packed, B, Tmax, R):
+    """(cls int8 (B, Tmax, R), dist float16 (B, Tmax, R), flow float16 (B, Tmax, R, 2)) views into a packed uint8 buffer
+    (a device tensor, or the pinned host copy of one)."""
+    n, _, off_dist, off_flow, _ = submission_rays_layout(B, Tmax, R)
+    cls = packed[:n].view(torch.int8).view(B, Tmax, R)
+    dist = packed[off_dist:off_dist + 2 * n].view(torch.float16).view(B, Tmax, R)
+    flow = packed[off_flow:off_flow + 4 * n].view(torch.float16).view(B, Tmax, R, 2)
+    return cls, dist, flow
+
+
+def submission_rays(sem_pred, flow_pred, origins, rays, pc_min, voxel_size, free_id=16, origin_counts=None, out=None,
+                    workspace=None):
+    """Cast `rays` from every lidar origin through the predicted grid and pack class / depth / flow per ray in the types of
+    submission.gz (int8 / float16 / float16 x 2), in two launches on the current stream: no synchronisation, no copy
+    (csrc/submission_rays.hip).
+    sem_pred (B, X, Y, Z) uint8 or int64, flow_pred (B, X, Y, Z, 2) float32, origins (B, Tmax, 3) float32 or float64 in ego
+    metres (Tmax <= 8; the conversion to voxel units runs in the origins' type, as process_one_sample's does), origin_counts
+    None or (B) int32 DEVICE tensor, rays (R, 3) float32, pc_min = pc_range[:3].
+    out: None, or a uint8 device tensor of at least submission_rays_bytes(B, Tmax, R) bytes; workspace: None, or one of at least
+    submission_rays_workspace_bytes(B, X, Y, Z) bytes.
+    -> (cls, dist, flow): (B, Tmax, R) int8, (B, Tmax, R) float16, (B, Tmax, R, 2) float16 views into the packed buffer; rows
+    of origins beyond origin_counts are not written (zero when `out` is None)."""
+    for n, t in (("flow_pred", flow_pred), ("rays", rays)):
+        _need_cuda_f32(n, t)
+    if not isinstance(sem_pred, torch.Tensor) or not sem_pred.is_cuda:
+        raise OccAmdError("sem_pred must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+    if sem_pred.dtype not in _SEM_DTYPE_CODES or not sem_pred.is_contiguous():
+        raise OccAmdError(f"sem_pred must be a contiguous uint8 or int64 tensor, got {sem_pred.dtype}")
+    if not isinstance(origins, torch.Tensor) or not origins.is_cuda:
+        raise OccAmdError("origins must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+    if origins.dtype not in _ORIGIN_DTYPE_CODES or not origins.is_contiguous():
+        raise OccAmdError(f"origins must be a contiguous float32 or float64 tensor, got {origins.dtype}")
+    if sem_pred.dim() != 4 or origins.dim() != 3 or rays.dim() != 2:
+        raise OccAmdError("submission_rays: expected sem (B,X,Y,Z), flow (B,X,Y,Z,2), origins (B,T,3), rays (R,3)")
+    B, X, Y, Z = sem_pred.shape
+    Tmax, R = origins.shape[1], rays.shape[0]
+    if (tuple(flow_pred.shape) != (B, X, Y, Z, 2) or origins.shape[0] != B or origins.shape[2] != 3 or rays.shape[1] != 3):
+        raise OccAmdError("submission_rays: inconsistent shapes")
+    if origin_counts is not None and not (origin_counts.is_cuda and origin_counts.dtype == torch.int32
+                                          and origin_counts.is_contiguous() and origin_counts.numel() == B):
+        raise OccAmdError("submission_rays: origin_counts must be a contiguous int32 device tensor of B entries")
+    dev = sem_pred.device
+    need = max(submission_rays_workspace_bytes(B, X, Y, Z), 256)      # Z > 32 answers 0: the call itself reports it
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
+        raise OccAmdError(f"submission_rays: workspace must be a uint8 device tensor of >= {need} bytes")
+    need_out = max(submission_rays_bytes(B, Tmax, R), 256)            # Tmax = 0 answers 0: the call itself reports it
+    if out is None:
+        out = torch.zeros(need_out, dtype=torch.uint8, device=dev)
+    elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= need_out):
+        raise OccAmdError(f"submission_rays: out must be a contiguous uint8 device tensor of >= {need_out} bytes")
+    with torch.cuda.device(dev), _timed('submission_rays'):
+        rc = _lib.lib().occ_submission_rays(
+            ptr(sem_pred), i32(_SEM_DTYPE_CODES[sem_pred.dtype]), ptr(flow_pred), ptr(origins),
+            i32(_ORIGIN_DTYPE_CODES[origins.dtype]), ptr(origin_counts), ptr(rays), f32(pc_min[0]), f32(pc_min[1]),
+            f32(pc_min[2]), f32(voxel_size), i32(free_id), ptr(out), i64(out.numel()), ptr(workspace),
+            i64(workspace.numel()), i32(B), i32(Tmax), i32(X), i32(Y), i32(Z), i32(R), stream_ptr(dev))
+    _lib.check(rc, "submission_rays")
+    return submission_rays_views(out, B, Tmax, R)
+
+
+_ORIGIN_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}
 _HEADS_LOSS_PARAMS = ("w1_occ", "b1_occ", "w2_occ", "b2_occ", "w1_flow", "b1_flow", "w2_flow", "b2_flow")
 
 

@@ -14,6 +14,9 @@ or the nuScenes devkit.  Host-side formatting only (no model compute lives here)
   make_img_meta                                    the img_metas keys the path consumes (encoder.py:94-101,133-134)
   lidar_origins                                    tools/ray_iou/ego_pose_extractor.py:84-121 (origins the rays start from)
   format_submission / read_submission              P/datasets/nuscenes_occ.py:189-257 (submission.gz)
+  format_submission_device                         the same file from device tensors (metrics.SubmissionWriter: the one
+                                                   exception to "no compute here" — it drives csrc/submission_rays.hip)
+  merge_submission_parts                           the parts of a multi-rank run -> one submission.gz (host only)
 """
 import gzip
 import os
@@ -329,12 +332,104 @@ def format_submission(samples, submission_prefix, header=None, device='cuda'):
         pcd = process_one_sample(sem_pred, rays, origins, flow_pred, device)
         results[token] = {'pcd_cls': pcd[:, 0].astype(np.int8), 'pcd_dist': pcd[:, 1].astype(np.float16),
                           'pcd_flow': pcd[:, 2:4].astype(np.float16)}
+    return write_submission(results, submission_prefix, header)
+
+
+def write_submission(results, submission_prefix, header=None):
+    """{token: {pcd_cls, pcd_dist, pcd_flow}} -> `<prefix>/submission.gz`, the bytes format_submission writes -> path."""
+    os.makedirs(submission_prefix, exist_ok=True)
     final = dict(SUBMISSION_HEADER if header is None else header)
     final['results'] = results
     path = os.path.join(submission_prefix, 'submission.gz')
     with open(path, 'wb') as f:
         f.write(gzip.compress(pickle.dumps(final), mtime=0))
     return path
+
+
+def format_submission_device(samples, submission_prefix, header=None, device='cuda', batch=8):
+    """format_submission with the ray cast, the class / flow look-up and the int8 / float16 casts on the device
+    (metrics.SubmissionWriter, csrc/submission_rays.hip): same sample tuples (numpy arrays or device tensors), same file.
+    Samples are taken `batch` at a time, their origins padded to the batch's largest T; a batch also ends where the origins'
+    float type changes, because the conversion to voxel units runs in that type (as process_one_sample's does).  -> path."""
+    from .metrics import ray_metrics as rm
+    from .metrics.submission_device import SubmissionWriter
+    dev = torch.device(device)
+    writer = SubmissionWriter(rm._pc_range, rm._voxel_size, free_id=len(rm.occ_class_names) - 1, device=dev)
+    pend = []
+
+    def flush():
+        if not pend:
+            return
+        tmax = max(o.shape[0] for _, _, _, o in pend)
+        origins = torch.zeros(len(pend), tmax, 3, dtype=pend[0][3].dtype)
+        for b, (_, _, _, o) in enumerate(pend):
+            origins[b, :o.shape[0]] = o
+        sem = torch.stack([s for _, s, _, _ in pend])
+        flow = torch.stack([f for _, _, f, _ in pend])
+        writer.add([t for t, _, _, _ in pend], sem, flow, origins, origin_counts=[o.shape[0] for _, _, _, o in pend])
+        pend.clear()
+
+    for token, sem_pred, flow_pred, origins in samples:
+        sem = torch.as_tensor(sem_pred)
+        if sem.dtype not in (torch.uint8, torch.int64):
+            sem = sem.to(torch.int64)
+        sem = sem.to(dev, non_blocking=True).reshape(OCC_SHAPE)
+        flow = torch.as_tensor(flow_pred).to(dev, torch.float32, non_blocking=True).reshape(OCC_SHAPE + (2,))
+        org = torch.as_tensor(origins).cpu()
+        if org.dtype not in (torch.float32, torch.float64):
+            org = org.to(torch.float64)
+        org = org.reshape(-1, 3)
+        if pend and (len(pend) >= int(batch) or pend[0][3].dtype != org.dtype or pend[0][1].dtype != sem.dtype):
+            flush()
+        pend.append((token, sem, flow, org))
+    flush()
+    return writer.write(submission_prefix, header)
+
+
+def merge_submission_parts(part_paths, submission_prefix, header=None, order=None):
+    """Host only: the parts that the ranks of a multi-rank run saved (SubmissionWriter.save_part) -> one submission.gz.
+    order: the token list of the file; default round-robin over the parts — sample i of the run is entry i // N of part
+    i mod N, the sharding of occnet_amd/dist.py (shard_indices).  That sharding wraps its tail so that every rank gets the
+    same count: the repeats it makes (the k-th entry after the last new token is token k again, with the same rows) are
+    dropped.  Any other token held twice, a token of `order` that no part holds, or a part's token that `order` leaves out
+    raises ValueError.  -> path."""
+    parts = []
+    for p in part_paths:
+        with open(p, 'rb') as f:
+            parts.append(pickle.loads(gzip.decompress(f.read())))
+    lists = [list(part) for part in parts]
+    n = len(lists)
+    round_robin = all(len(a) - len(b) in (0, 1) for a, b in zip(lists, lists[1:]))      # the sizes such a sharding gives
+    if round_robin:
+        seq = [(r, lists[r][k]) for k in range(len(lists[0]) if lists else 0) for r in range(n) if k < len(lists[r])]
+    else:
+        seq = [(r, tok) for r in range(n) for tok in lists[r]]
+    merged, found, wrapped = {}, [], 0
+    for r, tok in seq:
+        rows = parts[r][tok]
+        if tok not in merged and not wrapped:
+            merged[tok] = rows
+            found.append(tok)
+        elif (round_robin and wrapped < len(found) and tok == found[wrapped] and sorted(rows) == sorted(merged[tok])
+              and all(np.array_equal(rows[k], merged[tok][k], equal_nan=True) and rows[k].dtype == merged[tok][k].dtype
+                      for k in rows)):
+            wrapped += 1
+        else:
+            raise ValueError(f"merge_submission_parts: token {tok!r} of {part_paths[r]} appears twice, or follows the "
+                             "wrapped tail of the sharding")
+    if order is None:
+        if not round_robin:
+            raise ValueError("merge_submission_parts: the parts' sizes are not those of a round-robin sharding "
+                             f"({[len(l) for l in lists]}): pass order=")
+        order = found
+    order = list(order)
+    if len(set(order)) != len(order):
+        raise ValueError("merge_submission_parts: order names a token twice")
+    missing = [t for t in order if t not in merged]
+    extra = [t for t in merged if t not in set(order)]
+    if missing or extra:
+        raise ValueError(f"merge_submission_parts: order and parts disagree (missing {missing}, not in order {extra})")
+    return write_submission({t: merged[t] for t in order}, submission_prefix, header)
 
 
 def read_submission(path):
