@@ -32,6 +32,7 @@
  *   occ_ray_metrics_accumulate       <- process_one_sample + main + calc_metrics, P/datasets/ray_metrics.py:89-257
  *   occ_submission_rays              <- NuSceneOcc.format_results' per-sample loop (process_one_sample + the int8 / float16
  *        casts), P/datasets/nuscenes_occ.py:217-241
+ *   occ_submission_score_accumulate  <- calc_metrics of the stand-alone scorer, tools/ray_iou/metric.py:31-73
  *   occ_heads_loss_fwd_f32 / _bwd_f32 <- the heads (transformer_occ.py:132-141,318-319) + BEVFormerOccHead.loss /
  *        loss_single, P/bevformer/dense_heads/bevformer_occ_head.py:163-196, and their autograd backward
  */
@@ -928,6 +929,39 @@ int occ_submission_rays(const void* sem_pred, int sem_pred_dtype, const float* f
                         int origins_dtype, const int32_t* origin_counts, const float* rays, float off_x, float off_y,
                         float off_z, float voxel_size, int free_id, void* out, int64_t out_bytes, void* workspace,
                         int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R, void* stream);
+
+/* Score of submission rows as the challenge server computes it (csrc/submission_score.hip) — the reference's stand-alone
+ * scorer tools/ray_iou/metric.py:calc_metrics (:31-73) over B samples of per-ray rows, without a host round trip.  It differs
+ * from occ_ray_metrics_accumulate's scorer in what it reads (the rows of the file: int8 class, float16 depth and flow) and in
+ * its AVE rule: once a flow class (c < 8) has any true positive in a sample at a threshold, the flow error of EVERY valid ray
+ * of that sample is added, and the count of all those rays (metric.py:70-73).
+ *   pred_format, gt_format   0 = the packed sections of occ_submission_rays: *_cls int8[N], *_dist fp16[N] (2-byte aligned),
+ *                    *_flow fp16[N][2] (4-byte aligned);  1 = float32 rows (N, 4) = [class, dist, flow_x, flow_y] in *_cls,
+ *                    16-byte aligned (*_dist / *_flow are not read): the class is truncated toward zero as astype(np.int32)
+ *                    does; a class value that is NaN, infinite or beyond int32 counts as an out-of-range class.
+ *   counts (B) i32 DEVICE: sample b owns rows [b * stride, b * stride + counts[b]) of both sides (for the writer's buffers
+ *                    stride = Tmax * R, counts[b] = origin_counts[b] * R); clamped to 0 .. stride; rows beyond are never read
+ *                    into the score.  Both sides hold B * stride rows.
+ *   a ray is valid iff gt_cls != free_id; classes outside 0..free_id match no class (the ray stays valid); depth thresholds
+ *   1 / 2 / 4 m on the float32 |pred_dist - gt_dist|, strictly below; err = sqrtf(ux * ux + uy * uy) in float32, uncontracted.
+ *   state            occ_submission_score_state_words(free_id) = 17 * (free_id + 1) int64 words, ACCUMULATED into (the caller
+ *                    zeroes them once): gt_cnt[c] | pred_cnt[c] | tp[j][c] | ave_cnt[j][c] | ave_sum[j][c] | ave_inf[j][c] |
+ *                    ave_nan[j][c].  ave_sum: fixed point, quantum 2^-28 m/s (sums below 2^35 m/s: the full validation split
+ *                    fits while the mean flow error over its valid rays stays below 50 m/s).  A NaN error adds 1 to ave_nan,
+ *                    an infinite one (or one >= 2^34 m/s) 1 to ave_inf, instead of to ave_sum; both count in ave_cnt.  Integer
+ *                    atomics only: the state is bit-identical run to run and for any split of the samples over calls.
+ *   workspace        occ_submission_score_workspace_bytes(B) bytes, 8-byte aligned, uninitialised: the per-block records.
+ *   max_chunks       0 = the launcher's grid (one block per 1024 rows of stride, at most 128 per sample); > 0 caps the blocks
+ *                    per sample (1: one block per sample); < 0 OCC_E_INVALID.  The state does not depend on it.
+ * free_id in 1..31, 1 <= B <= 65535.  Two launches on `stream`, no synchronisation, no allocation, no copy.  Every argument is
+ * checked before the first launch.
+ */
+int64_t occ_submission_score_state_words(int free_id);
+int64_t occ_submission_score_workspace_bytes(int B);
+int occ_submission_score_accumulate(int pred_format, const void* pred_cls, const void* pred_dist, const void* pred_flow,
+                                    int gt_format, const void* gt_cls, const void* gt_dist, const void* gt_flow,
+                                    const int32_t* counts, int free_id, int64_t* state, void* workspace,
+                                    int64_t workspace_bytes, int B, int64_t stride, int max_chunks, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * (f) Training tail: both occupancy heads AND their losses as one node (csrc/occ_heads_loss.hip) — the reference's

@@ -2151,6 +2151,71 @@ def submission_rays(sem_pred, flow_pred, origins, rays, pc_min, voxel_size, free
     return submission_rays_views(out, B, Tmax, R)
 
 
+def submission_score_state_words(free_id=16):
+    """int64 words of the submission score's state for classes 0..free_id (17 per class; layout: include/occnet_amd.h)."""
+    n = int(_lib.lib().occ_submission_score_state_words(i32(free_id)))
+    if n <= 0:
+        raise OccAmdError(f"submission_score_state_words: free_id must be 1..31, got {free_id}")
+    return n
+
+
+def submission_score_workspace_bytes(B):
+    return int(_lib.lib().occ_submission_score_workspace_bytes(i32(B)))
+
+
+def _score_side(name, side, B, stride):
+    """One side of submission_score_accumulate -> (format code, cls / rows, dist, flow): a float32 (B, stride, 4) tensor of
+    rows, or the (cls int8, dist float16, flow float16) sections of a packed buffer with B * stride rows each."""
+    if isinstance(side, torch.Tensor):
+        if not (side.is_cuda and side.dtype == torch.float32 and side.is_contiguous()):
+            raise OccAmdError(f"{name} rows must be a contiguous float32 device (HIP) tensor: the MI355X path has no CPU "
+                              "fallback")
+        if side.numel() != B * stride * 4 or side.shape[-1] != 4:
+            raise OccAmdError(f"submission_score_accumulate: {name} rows must hold B * stride = {B * stride} rows of 4")
+        return 1, side, None, None
+    cls, dist, flow = side
+    for t, dt, per in ((cls, torch.int8, 1), (dist, torch.float16, 1), (flow, torch.float16, 2)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dt and t.is_contiguous()):
+            raise OccAmdError(f"{name} sections must be contiguous int8 / float16 / float16 device (HIP) tensors: the MI355X "
+                              "path has no CPU fallback")
+        if t.numel() != B * stride * per:
+            raise OccAmdError(f"submission_score_accumulate: {name} sections must hold B * stride = {B * stride} rows")
+    return 0, cls, dist, flow
+
+
+def submission_score_accumulate(state, pred, gt, counts, stride, free_id=16, workspace=None, max_chunks=0):
+    """Add the terms of tools/ray_iou/metric.py:calc_metrics for B samples of per-ray rows to `state` (int64 device tensor of
+    submission_score_state_words(free_id) words), in two launches on the current stream: no synchronisation, no copy
+    (csrc/submission_score.hip).
+    pred / gt: each either a float32 (B, stride, 4) tensor of rows [class, dist, flow_x, flow_y], or the tuple (cls int8, dist
+    float16, flow float16) of a packed buffer's sections with B * stride rows (ext.submission_rays_views); counts (B) int32
+    DEVICE tensor: sample b owns rows [b * stride, b * stride + counts[b]).
+    workspace: None, or a uint8 device tensor of at least submission_score_workspace_bytes(B) bytes (uninitialised);
+    max_chunks: 0, or a cap on the blocks per sample (the state does not depend on it)."""
+    if not (isinstance(counts, torch.Tensor) and counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous()):
+        raise OccAmdError("submission_score_accumulate: counts must be a contiguous int32 device tensor of B entries")
+    B, stride = int(counts.numel()), int(stride)
+    if B < 1 or stride < 1:
+        raise OccAmdError(f"submission_score_accumulate: bad dimension (B={B} stride={stride})")
+    if not (state.is_cuda and state.dtype == torch.int64 and state.is_contiguous()
+            and state.numel() == submission_score_state_words(free_id)):
+        raise OccAmdError("submission_score_accumulate: state must be a contiguous int64 device tensor of "
+                          f"{submission_score_state_words(free_id)} words")
+    pf, pc, pd, pfl = _score_side("pred", pred, B, stride)
+    gf, gc, gd, gfl = _score_side("gt", gt, B, stride)
+    dev = state.device
+    need = max(submission_score_workspace_bytes(B), 256)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
+        raise OccAmdError(f"submission_score_accumulate: workspace must be a uint8 device tensor of >= {need} bytes")
+    with torch.cuda.device(dev), _timed('submission_score_accumulate'):
+        rc = _lib.lib().occ_submission_score_accumulate(
+            i32(pf), ptr(pc), ptr(pd), ptr(pfl), i32(gf), ptr(gc), ptr(gd), ptr(gfl), ptr(counts), i32(free_id), ptr(state),
+            ptr(workspace), i64(workspace.numel()), i32(B), i64(stride), i32(max_chunks), stream_ptr(dev))
+    _lib.check(rc, "submission_score_accumulate")
+
+
 _ORIGIN_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}
 _HEADS_LOSS_PARAMS = ("w1_occ", "b1_occ", "w2_occ", "b2_occ", "w1_flow", "b1_flow", "w2_flow", "b2_flow")
 

@@ -435,3 +435,22 @@ def merge_submission_parts(part_paths, submission_prefix, header=None, order=Non
 def read_submission(path):
     with open(path, 'rb') as f:
         return pickle.loads(gzip.decompress(f.read()))
+
+
+def score_submission(pred, gt, device='cuda', free_id=16, batch=8):
+    """The score the challenge server gives a submission: the counterpart of the reference's tools/ray_iou/metric.py:compute
+    on the device (metrics.SubmissionScore, csrc/submission_score.hip).  pred, gt: each the path of a submission.gz-style file
+    (the ground truth's is the reference's nuscenes_infos_val_occ_pcd.gz), the dict such a file holds, or its `results` dict
+    {token: {pcd_cls, pcd_dist, pcd_flow}}.  Walks the ground truth's tokens; a token without a prediction raises
+    RuntimeError.  -> metric.py's `output` dict (RayIoU@1, RayIoU@2, RayIoU@4, RayIoU, mAVE, final_Occ_Score) plus iou_list
+    and ave_list."""
+    from .metrics.submission_score import SubmissionScore
+
+    def results(x):
+        if isinstance(x, (str, os.PathLike)):
+            x = read_submission(x)
+        return x['results'] if 'results' in x and 'pcd_cls' not in x['results'] else x
+
+    score = SubmissionScore(free_id=free_id, device=device)
+    score.update_results(results(pred), results(gt), batch=batch)
+    return score.compute()

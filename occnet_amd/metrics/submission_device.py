@@ -23,10 +23,10 @@ from .ray_metrics import generate_lidar_rays
 
 
 class _Slot:
-    """One in-flight batch: packed device buffer, mask workspace, pinned host copy, pinned staging of origins and counts."""
+    """One in-flight batch: packed device buffer (and the ground truth's, for add_scored), mask workspace, pinned host copy, pinned staging of origins and counts."""
 
     def __init__(self):
-        self.dev = self.workspace = self.host = self.origins = self.counts = None
+        self.dev = self.dev_gt = self.workspace = self.host = self.origins = self.counts = None
         self.event = None
         self.pending = None          # (tokens, counts, B, Tmax, R) of the batch whose copy `event` marks
 
@@ -65,19 +65,37 @@ class SubmissionWriter:
         lidar_origins (B, T, 3) float32 or float64 ego metres (T <= 8; host or device); origin_counts: None (every sample has
         T origins) or a HOST list of B ints in 1..T.  Two kernels, one non-blocking copy into a pinned slot, one event; the
         call waits only for the slot it is about to reuse (the batch enqueued `depth` calls ago)."""
+        self._enqueue(tokens, sem_pred, flow_pred, lidar_origins, origin_counts)
+
+    def add_scored(self, tokens, sem_pred, flow_pred, sem_gt, flow_gt, lidar_origins, score, origin_counts=None):
+        """`add`, and the score the server will give these rows: the prediction's rows go exactly as in `add`; the ground truth
+        (sem_gt, flow_gt: as sem_pred, flow_pred) goes through the same ext.submission_rays into a second device buffer of the
+        slot, and `score` (metrics.SubmissionScore) takes both packed buffers in one update_packed.  Two more launch
+        pairs (cast, score), nothing more copied, no synchronisation."""
+        self._enqueue(tokens, sem_pred, flow_pred, lidar_origins, origin_counts, gt=(sem_gt, flow_gt), score=score)
+
+    def _enqueue(self, tokens, sem_pred, flow_pred, lidar_origins, origin_counts, gt=None, score=None):
         from .. import ext
         tokens = [tokens] if isinstance(tokens, str) else list(tokens)
         B = len(tokens)
         if len(set(tokens)) != B or any(t in self._tokens for t in tokens):
             dup = sorted({t for t in tokens if t in self._tokens or tokens.count(t) > 1})
             raise ValueError(f"SubmissionWriter.add: duplicate token(s) {dup}")
-        for name, t in (("sem_pred", sem_pred), ("flow_pred", flow_pred)):
+        grids = (("sem_pred", sem_pred), ("flow_pred", flow_pred)) + \
+            ((("sem_gt", gt[0]), ("flow_gt", gt[1])) if gt is not None else ())
+        for name, t in grids:
             if not isinstance(t, torch.Tensor) or not t.is_cuda:
                 raise ext.OccAmdError(f"{name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
-        if sem_pred.dtype not in (torch.uint8, torch.int64):
-            raise ext.OccAmdError(f"sem_pred must be uint8 or int64, got {sem_pred.dtype}")
+        for name, t in grids[::2]:
+            if t.dtype not in (torch.uint8, torch.int64):
+                raise ext.OccAmdError(f"{name} must be uint8 or int64, got {t.dtype}")
         sem_pred = sem_pred.reshape([B] + self.occ_size).contiguous()
         flow_pred = flow_pred.reshape([B] + self.occ_size + [2]).contiguous()
+        if gt is not None:
+            if score is None or score.free_id != self.free_id:
+                raise ValueError("SubmissionWriter.add_scored: score must be a SubmissionScore of the writer's free_id")
+            sem_gt = gt[0].reshape([B] + self.occ_size).contiguous()
+            flow_gt = gt[1].reshape([B] + self.occ_size + [2]).contiguous()
         origins = torch.as_tensor(lidar_origins)
         if origins.dtype not in (torch.float32, torch.float64):
             origins = origins.to(torch.float64)
@@ -114,6 +132,11 @@ class SubmissionWriter:
             origins = staged.to(dev, non_blocking=True)
         ext.submission_rays(sem_pred, flow_pred, origins.contiguous(), rays, self.pc_range[:3], self.voxel_size, self.free_id,
                             origin_counts=counts_dev, out=slot.dev, workspace=slot.workspace)
+        if gt is not None:                           # same stream: the masks' workspace is free again when this cast starts
+            slot.dev_gt = _grown(slot.dev_gt, nbytes, dtype=torch.uint8, device=dev)
+            ext.submission_rays(sem_gt, flow_gt, origins.contiguous(), rays, self.pc_range[:3], self.voxel_size, self.free_id,
+                                origin_counts=counts_dev, out=slot.dev_gt, workspace=slot.workspace)
+            score.update_packed(slot.dev, slot.dev_gt, B, Tmax, R, counts_dev * R)
         slot.host[:nbytes].copy_(slot.dev[:nbytes], non_blocking=True)
         slot.event = torch.cuda.Event()
         slot.event.record()
