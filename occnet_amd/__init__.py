@@ -10,14 +10,12 @@ Layout:
 __version__ = "0.1.0"
 
 
-# Derived-weight caches (packed hi/lo Linear weights, concatenated query Linears, folded TSA position terms,
-# per-(level, camera) value-projection biases, the decoder's folded BatchNorm, the folded inference backbone)
-# are keyed on (data_ptr, tensor._version, cache_epoch()).  In-place updates through autograd-visible ops
-# (optimizer steps, p.copy_ under no_grad) bump _version; writes through `param.data` do not — so everything
-# that may write that way bumps the epoch instead: load_state_dict on any plugin module (post hook) and an explicit
-# occnet_amd.invalidate_caches() after EMA / manual .data surgery.  (A train()/eval() mode change does not: the folded
-# inference backbone, the one cache that holds COPIES without per-tensor keys, re-checks a (data_ptr, _version)
-# signature of its source parameters the first time it is used after the model has been in training mode.)
+# Tensors derived from weights are cached by one protocol, occnet_amd/derived.py: keys carry every source's
+# (data_ptr, _version, shape, stride, device) and cache_epoch().  Writes through `param.data` bump no _version, so whatever
+# writes that way bumps the epoch: load_state_dict on any plugin module (post hook), BEVFormerOcc.train()'s content
+# fingerprint on a train -> eval transition, and an explicit occnet_amd.invalidate_caches() after EMA / manual .data surgery.
+# (The folded inference backbone holds COPIES: it re-checks derived.signature() of its source parameters the first time it is
+# used after the model has been in training mode.)
 _CACHE_EPOCH = 0
 
 
@@ -30,10 +28,10 @@ def invalidate_caches(model=None):
     backbone from the live parameters.  Call after writing parameters through `.data`."""
     global _CACHE_EPOCH
     _CACHE_EPOCH += 1
-    from . import ext
-    ext._PACKED_W.clear()
-    ext._STACKED_VP.clear()
-    ext._STACKED_GB.clear()
-    ext._CHAIN_PACKS.clear()
+    for cache in derived._REGISTERED:
+        cache.clear()
     if model is not None and getattr(model, '_inference_backbone', None) is not None:
         model.enable_fused_backbone(**model._inference_backbone_args)
+
+
+from . import derived  # noqa: E402  (it reads cache_epoch)

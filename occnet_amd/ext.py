@@ -14,7 +14,8 @@ import os
 
 import torch
 
-from . import _lib, cache_epoch
+from . import _lib
+from .derived import DerivedCache
 from ._lib import OccAmdError, OccAmdUnsupported, f32, i32, i64, ptr, stream_ptr
 
 
@@ -801,34 +802,24 @@ def _rows2d(name, t, k=None):
 # chain), 'bf16x3' = three bf16 MFMAs on hi/lo-split operands with f32 accumulation (relative error of a
 # product <= 2^-16; 2-3x faster).  The default can be overridden with OCC_LINEAR_PRECISION.
 LINEAR_PRECISION = os.environ.get("OCC_LINEAR_PRECISION", "bf16x3")
-_PACKED_W = {}          # (data_ptr, version, shape) -> packed hi/lo bf16 weight (small LRU)
+_PACKED_W = DerivedCache("linear_pack_weight_bf16x3", 256, register=True)
 
 
 def linear_pack_weight_bf16x3(weight):
     """(N, K) float32 Linear weight -> bf16 hi/lo split in MFMA fragment order
-    packed[K/16][ceil(N/32)][hi, lo][lane][8] (int16 storage, columns zero-padded to a multiple of 32), cached."""
-    # temporaries (a transposed weight in a backward pass, a concatenation rebuilt every forward) are marked by their
-    # producer and packed without entering the cache: an entry keeps its tensor alive and can never hit again
-    no_cache = getattr(weight, '_occ_no_cache', False)
-    key = (weight.data_ptr(), weight._version, tuple(weight.shape), str(weight.device), cache_epoch())
-    hit = None if no_cache else _PACKED_W.get(key)
-    if hit is not None:
-        return hit[1]
-    _need_cuda_f32("weight", weight)
-    N, K = weight.shape
-    packed = torch.empty((N + 31) // 32 * 32 * K * 2, dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = _lib.lib().occ_linear_pack_weight_bf16x3(ptr(weight), ptr(packed), i32(N), i32(K),
-                                                      stream_ptr(weight.device))
-    _lib.check(rc, "linear_pack_weight_bf16x3")
-    if no_cache:
+    packed[K/16][ceil(N/32)][hi, lo][lane][8] (int16 storage, columns zero-padded to a multiple of 32), cached.
+    Temporaries (a transposed weight in a backward pass, a concatenation rebuilt every forward) are marked `_occ_no_cache`
+    by their producer and packed without entering the cache."""
+    def build():
+        _need_cuda_f32("weight", weight)
+        N, K = weight.shape
+        packed = torch.empty((N + 31) // 32 * 32 * K * 2, dtype=torch.int16, device=weight.device)
+        with torch.cuda.device(weight.device):
+            rc = _lib.lib().occ_linear_pack_weight_bf16x3(ptr(weight), ptr(packed), i32(N), i32(K),
+                                                          stream_ptr(weight.device))
+        _lib.check(rc, "linear_pack_weight_bf16x3")
         return packed
-    if len(_PACKED_W) >= 256:
-        _PACKED_W.pop(next(iter(_PACKED_W)))
-    # the entry keeps the weight tensor alive: while it is cached its address cannot be recycled by
-    # another tensor, so (data_ptr, version) identifies the contents
-    _PACKED_W[key] = (weight, packed)
-    return packed
+    return _PACKED_W.get((weight,), build)
 
 
 def _check_out_scale(what, out_scale, planes, out):
@@ -985,8 +976,8 @@ def absmax_words_f32(a_or_bound):
     return pattern.to(torch.int32).reshape(1).repeat(8)
 
 
-_LN_BOUND = {}          # (gamma, beta identity, epoch) -> (sources kept alive, words)
-_TSA_RANGE_TERMS = {}   # (weight, bias identity, epoch) -> (sources kept alive, row_l1, bias_max)
+_LN_BOUND = DerivedCache("layernorm_bound_words", 64, register=True)        # (gamma, beta) -> words
+_TSA_RANGE_TERMS = DerivedCache("tsa_value_scale", 64, register=True)       # (weight, bias) -> (row_l1, bias_max)
 
 
 def layernorm_bound_words(ln):
@@ -997,19 +988,13 @@ def layernorm_bound_words(ln):
     rounding of the mean, and sqrt(N) / sqrt(N - 1) is inside the slack from N = 129 on (they run at N = 256).  Cached on
     (gamma, beta) identity."""
     g, b = (ln.weight, ln.bias) if isinstance(ln, torch.nn.LayerNorm) else (ln[0], ln[1])
-    key = (_ident(g), _ident(b), str(g.device), cache_epoch())
-    hit = _LN_BOUND.get(key)
-    if hit is not None:
-        return hit[1]
-    n = g.numel()
-    bound = g.detach().float().abs().amax() * (float(max(n - 1, 0)) ** 0.5 * 1.00390625)
-    if b is not None:
-        bound = bound + b.detach().float().abs().amax()
-    words = absmax_words_f32(bound)
-    if len(_LN_BOUND) >= 64:
-        _LN_BOUND.pop(next(iter(_LN_BOUND)))
-    _LN_BOUND[key] = ((g, b), words)
-    return words
+    def build():
+        n = g.numel()
+        bound = g.detach().float().abs().amax() * (float(max(n - 1, 0)) ** 0.5 * 1.00390625)
+        if b is not None:
+            bound = bound + b.detach().float().abs().amax()
+        return absmax_words_f32(bound)
+    return _LN_BOUND.get((g, b), build)
 
 
 def _attach_ln_bound(t, gamma, beta):
@@ -1026,18 +1011,15 @@ def tsa_value_scale(value_proj, words):
     (bound * row_l1 * (1 + 2^-8) + bias_max) * s <= 2^15 with row_l1 = max_n sum_k |W_nk|, bias_max = max|b| (device tensors,
     cached per weight version) — occ_value_range_scale_from_amax, one 64-thread launch."""
     w, b = value_proj.weight, value_proj.bias
-    key = (_ident(w), _ident(b), str(w.device), cache_epoch())
-    hit = _TSA_RANGE_TERMS.get(key)
-    if hit is None:
+    def build():
         row_l1 = w.detach().float().abs().sum(1).amax().reshape(1)
         bias_max = (b.detach().float().abs().amax() if b is not None else torch.zeros((), device=w.device)).reshape(1)
-        if len(_TSA_RANGE_TERMS) >= 64:
-            _TSA_RANGE_TERMS.pop(next(iter(_TSA_RANGE_TERMS)))
-        hit = _TSA_RANGE_TERMS[key] = ((w, b), row_l1, bias_max)
+        return row_l1, bias_max
+    row_l1, bias_max = _TSA_RANGE_TERMS.get((w, b), build)
     if not (isinstance(words, torch.Tensor) and words.is_cuda and words.dtype == torch.int32 and words.numel() == 8
             and words.is_contiguous()):
         raise OccAmdError("tsa_value_scale: words must be 8 contiguous int32 device words")
-    return _range_scale_from_amax(words, hit[1], hit[2], 'tsa_value_range')[:1]
+    return _range_scale_from_amax(words, row_l1, bias_max, 'tsa_value_range')[:1]
 
 
 def linear_q16rows(a, weight, bias, scale, groups, act=None, residual=None, ln=None):
@@ -1139,23 +1121,19 @@ def value_proj_bf16(a_list, weight, group_bias, out, rows_per_group, out_group_r
     return out
 
 
-_STACKED_VP = {}        # (weights' (ptr, version) ..., epoch) -> (stacked weight, its pack) of value_proj_bf16_planes
-_STACKED_GB = {}        # (bias tables' (ptr, version) ..., epoch) -> (their concatenation, the sources kept alive)
+_STACKED_VP = DerivedCache("value_proj_planes_prepare", 8, register=True)    # weights -> (stacked weight, its pack, weights)
+_STACKED_GB = DerivedCache("value_proj_bf16_planes bias", 8, register=True)  # bias tables -> their concatenation
 
 
 def value_proj_planes_prepare(weights):
     """The stacked + packed weight of value_proj_bf16_planes for this list of projections (cached on the weights'
     identities): built on the CURRENT stream.  A caller that launches value_proj_bf16_planes on a side stream calls this
     on the main stream first, so that no main-stream reader of the cache entry can race its construction."""
-    key = tuple((w.data_ptr(), w._version) for w in weights) + (str(weights[0].device), cache_epoch())
-    hit = _STACKED_VP.get(key)
-    if hit is None:
+    def build():
         stacked = torch.cat([w.detach() for w in weights], 0).contiguous()
         stacked._occ_no_cache = True
-        if len(_STACKED_VP) >= 8:
-            _STACKED_VP.pop(next(iter(_STACKED_VP)))
-        hit = _STACKED_VP[key] = (stacked, linear_pack_weight_bf16x3(stacked), list(weights))
-    return hit
+        return stacked, linear_pack_weight_bf16x3(stacked), list(weights)
+    return _STACKED_VP.get(weights, build)
 
 
 def value_proj_bf16_planes(a_list, weights, group_biases, out, rows_per_group, out_group_rows, out_row0, out_scale=None):
@@ -1186,13 +1164,7 @@ def value_proj_bf16_planes(a_list, weights, group_biases, out, rows_per_group, o
     if group_biases is not None and group_biases[0] is not None:
         # (S, G, P*N), cached on the per-projection bias tables' identities: it was a cat kernel per step in front of the
         # side stream's projection launch
-        gkey = tuple((g.data_ptr(), g._version) for g in group_biases) + (str(out.device), cache_epoch())
-        ghit = _STACKED_GB.get(gkey)
-        if ghit is None:
-            if len(_STACKED_GB) >= 8:
-                _STACKED_GB.pop(next(iter(_STACKED_GB)))
-            ghit = _STACKED_GB[gkey] = (torch.cat(list(group_biases), 2).contiguous(), list(group_biases))
-        gb_keep = ghit[0]
+        gb_keep = _STACKED_GB.get(group_biases, lambda: torch.cat(list(group_biases), 2).contiguous())
         G = gb_keep.shape[1]
         gb_ptrs = (ctypes.c_void_p * S)(*[gb_keep[s].data_ptr() for s in range(S)])
     arr64 = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])
@@ -1278,59 +1250,45 @@ def linear(a, weight, bias=None, a2=None, a2_add=None, act=None, residual=None, 
 # OCC_LINEAR_CHAIN=0 keeps the encoder on one launch per Linear (the round-3 path); the chain kernels need
 # embed_dims = 256 and the bf16x3 precision mode
 LINEAR_CHAIN = os.environ.get("OCC_LINEAR_CHAIN", "1") != "0"
-_CHAIN_PACKS = {}       # identity key of the stage weights / biases -> (sources kept alive, packed buffer)
-
-
-def _ident(t):
-    return None if t is None else (t.data_ptr(), t._version, tuple(t.shape))
+_CHAIN_PACKS = DerivedCache("linear chain packs", 128, register=True)   # stage weights ("w") / biases ("b") -> packed buffer
 
 
 def linear_chain_pack(weights):
     """[(N_i, K_i) float32 weights in consumption order] -> one int16 buffer: every weight packed by
     occ_linear_chain_pack_bf16x3 (256-row groups, 16 KB per k-step, zero rows beyond N), concatenated.  Cached on the
-    weights' identities (address, version) and the cache epoch."""
-    key = ("w",) + tuple(_ident(w) for w in weights) + (str(weights[0].device), cache_epoch())
-    hit = _CHAIN_PACKS.get(key)
-    if hit is not None:
-        return hit[1]
-    lib = _lib.lib()
-    sizes = []
-    for w in weights:
-        _need_cuda_f32("weight", w)
-        if w.dim() != 2 or w.shape[1] % 16:
-            raise OccAmdUnsupported("linear_chain_pack: weights must be (N, K) with K % 16 == 0")
-        sizes.append(int(lib.occ_linear_chain_packed_bytes(i32(w.shape[0]), i32(w.shape[1]))) // 2)
-    packed = torch.empty(sum(sizes), dtype=torch.int16, device=weights[0].device)
-    off = 0
-    with torch.cuda.device(packed.device):
-        for w, n in zip(weights, sizes):
-            rc = lib.occ_linear_chain_pack_bf16x3(ptr(w), ctypes.c_void_p(packed.data_ptr() + off * 2), i32(w.shape[0]),
-                                                  i32(w.shape[1]), stream_ptr(packed.device))
-            _lib.check(rc, "linear_chain_pack_bf16x3")
-            off += n
-    if len(_CHAIN_PACKS) >= 128:
-        _CHAIN_PACKS.pop(next(iter(_CHAIN_PACKS)))
-    _CHAIN_PACKS[key] = (list(weights), packed)      # the sources stay referenced: their addresses cannot be recycled
-    return packed
+    weights' identities."""
+    def build():
+        lib = _lib.lib()
+        sizes = []
+        for w in weights:
+            _need_cuda_f32("weight", w)
+            if w.dim() != 2 or w.shape[1] % 16:
+                raise OccAmdUnsupported("linear_chain_pack: weights must be (N, K) with K % 16 == 0")
+            sizes.append(int(lib.occ_linear_chain_packed_bytes(i32(w.shape[0]), i32(w.shape[1]))) // 2)
+        packed = torch.empty(sum(sizes), dtype=torch.int16, device=weights[0].device)
+        off = 0
+        with torch.cuda.device(packed.device):
+            for w, n in zip(weights, sizes):
+                rc = lib.occ_linear_chain_pack_bf16x3(ptr(w), ctypes.c_void_p(packed.data_ptr() + off * 2), i32(w.shape[0]),
+                                                      i32(w.shape[1]), stream_ptr(packed.device))
+                _lib.check(rc, "linear_chain_pack_bf16x3")
+                off += n
+        return packed
+    return _CHAIN_PACKS.get(weights, build, ("w",))
 
 
 def _chain_bias(parts, device):
     """[(bias tensor or None, padded length)] -> one float32 vector (zeros where a bias is None / beyond its length)."""
-    key = ("b",) + tuple((_ident(b), n) for b, n in parts) + (str(device), cache_epoch())
-    hit = _CHAIN_PACKS.get(key)
-    if hit is not None:
-        return hit[1]
-    out = torch.zeros(sum(n for _, n in parts), dtype=torch.float32, device=device)
-    off = 0
-    for b, n in parts:
-        if b is not None:
-            _need_cuda_f32("bias", b)
-            out[off:off + b.numel()] = b.detach().reshape(-1)
-        off += n
-    if len(_CHAIN_PACKS) >= 128:
-        _CHAIN_PACKS.pop(next(iter(_CHAIN_PACKS)))
-    _CHAIN_PACKS[key] = ([b for b, _ in parts], out)
-    return out
+    def build():
+        out = torch.zeros(sum(n for _, n in parts), dtype=torch.float32, device=device)
+        off = 0
+        for b, n in parts:
+            if b is not None:
+                _need_cuda_f32("bias", b)
+                out[off:off + b.numel()] = b.detach().reshape(-1)
+            off += n
+        return out
+    return _CHAIN_PACKS.get([b for b, _ in parts], build, ("b", device) + tuple(n for _, n in parts))
 
 
 def _ln_params(ln, n=256):

@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import cache_epoch, ext
+from .. import cache_epoch, derived, ext
 from .backbone_plan import FusedInferenceBackbone, own_conv_kind
 from .bricks import BaseModule, ConvModule
 from .registry import BACKBONES, NECKS
@@ -38,14 +38,11 @@ def conv_bn_folded(x, conv, bn):
 
 def _bn_fold_constants(bn):
     """(1 / sqrt(var + eps), mean / sqrt(var + eps)) of an eval-mode BatchNorm, cached until a buffer is written."""
-    key = (bn.running_mean._version, bn.running_var._version, bn.running_var.data_ptr(), cache_epoch())
-    cached = getattr(bn, '_occ_fold', None)
-    if cached is None or cached[0] != key:
+    def build():
         with torch.no_grad():
             rstd = torch.rsqrt(bn.running_var + bn.eps)
-            cached = (key, rstd, bn.running_mean * rstd)
-        object.__setattr__(bn, '_occ_fold', cached)
-    return cached[1], cached[2]
+            return rstd, bn.running_mean * rstd
+    return derived.owned(bn, '_occ_fold').get((bn.running_mean, bn.running_var), build)
 
 
 class ConvBNActFunction(torch.autograd.Function):

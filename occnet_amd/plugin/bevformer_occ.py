@@ -8,7 +8,7 @@ train_cfg / test_cfg is injected into the head's config.
 """
 import torch
 
-from .. import cache_epoch, ext
+from .. import cache_epoch, derived, ext
 from ..io import identity_photometric
 from .bricks import BaseModule
 from .grid_mask import GridMask
@@ -96,7 +96,7 @@ class BEVFormerOcc(BaseModule):
 
     def _backbone_signature(self):
         mods = [m for m in (getattr(self, 'img_backbone', None), getattr(self, 'img_neck', None)) if m is not None]
-        return tuple((t.data_ptr(), t._version) for m in mods for t in list(m.parameters()) + list(m.buffers()))
+        return derived.signature(t for m in mods for t in list(m.parameters()) + list(m.buffers()))
 
     def _current_plan(self):
         """The folded inference backbone, rebuilt when its source parameters changed since the fold."""

@@ -10,7 +10,7 @@ import os
 import torch
 import torch.nn as nn
 
-from .. import cache_epoch
+from .. import derived
 from .._lib import OccAmdUnsupported
 from .bricks import BaseModule, CrossEntropyLoss, L1Loss
 from .registry import HEADS, build_loss, build_positional_encoding, build_transformer
@@ -57,19 +57,12 @@ class BEVFormerOccHead(BaseModule):
         embedding tables, so without autograd the SAME tensor is handed out until they change: downstream
         caches (the encoder's query-major copy, the TSA position term) key on its identity."""
         pe = self.positional_encoding
-        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in pe.parameters())
-        key = None
-        if not needs_grad:
-            key = (bs, str(device), dtype, cache_epoch()) + tuple((p.data_ptr(), p._version) for p in pe.parameters())
-            if getattr(self, '_pos_key', None) == key:
-                return self._pos_val
-        bev_mask = torch.zeros((bs, self.bev_h, self.bev_w), device=device).to(dtype)
-        bev_pos = pe(bev_mask).to(dtype)
-        if key is not None:
-            bev_pos = bev_pos.detach()
-            object.__setattr__(self, '_pos_key', key)
-            object.__setattr__(self, '_pos_val', bev_pos)
-        return bev_pos
+        def build():
+            bev_mask = torch.zeros((bs, self.bev_h, self.bev_w), device=device).to(dtype)
+            return pe(bev_mask).to(dtype)
+        if torch.is_grad_enabled() and any(p.requires_grad for p in pe.parameters()):
+            return build()
+        return derived.owned(self, '_pos').get(list(pe.parameters()), lambda: build().detach(), (bs, device, dtype))
 
     def _bev_inputs(self, mlvl_feats):
         """-> (bev_queries, bev_pos, grid_length) of a forward pass over mlvl_feats."""

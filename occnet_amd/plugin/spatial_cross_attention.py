@@ -23,7 +23,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import cache_epoch, ext
+from .. import ext
+from ..derived import DerivedCache
 from .._lib import OccAmdError, OccAmdUnsupported
 from .bricks import BaseModule, X3Linear, constant_init, xavier_init
 from .functions import MultiScaleDeformableAttnFunction_fp32
@@ -40,16 +41,13 @@ class _CatLinearCache:
     """Concatenated (weight, bias) of several nn.Linear layers, rebuilt when a parameter changes."""
 
     def __init__(self):
-        self._key, self._w, self._b = None, None, None
+        self._cache = DerivedCache("cat_linears", 1)
 
     def get(self, linears):
-        key = tuple((l.weight.data_ptr(), l.weight._version, l.bias.data_ptr(), l.bias._version)
-                    for l in linears) + (cache_epoch(),)
-        if key != self._key:
-            self._w = torch.cat([l.weight.detach() for l in linears], 0).contiguous()
-            self._b = torch.cat([l.bias.detach() for l in linears], 0).contiguous()
-            self._key = key
-        return self._w, self._b
+        return self._cache.get(
+            [t for l in linears for t in (l.weight, l.bias)],
+            lambda: (torch.cat([l.weight.detach() for l in linears], 0).contiguous(),
+                     torch.cat([l.bias.detach() for l in linears], 0).contiguous()))
 
 
 @ATTENTION.register_module()

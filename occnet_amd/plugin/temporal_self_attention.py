@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import cache_epoch, ext
+from .. import derived, ext
 from .._lib import OccAmdUnsupported
 from .bricks import BaseModule, X3Linear, constant_init, xavier_init
 from .functions import MultiScaleDeformableAttnFunction_fp32
@@ -98,14 +98,9 @@ class TemporalSelfAttention(BaseModule):
 
     def _folded_query_weights(self, w, b, query_pos):
         c = self.embed_dims
-        key = (w.data_ptr(), w._version, b.data_ptr(), b._version, query_pos.data_ptr(),
-               query_pos._version, tuple(query_pos.shape), cache_epoch())
-        if getattr(self, '_fold_key', None) != key:
-            w_sum = (w[:, :c] + w[:, c:]).contiguous()
-            pos_term = ext.linear(query_pos.contiguous(), w[:, c:].contiguous(), b)
-            # the keyed tensors stay referenced so their addresses cannot be recycled under the cache
-            self._fold_key, self._fold_src, self._fold_val = key, (w, b, query_pos), (w_sum, pos_term)
-        return self._fold_val
+        return derived.owned(self, '_fold').get(
+            (w, b, query_pos),
+            lambda: ((w[:, :c] + w[:, c:]).contiguous(), ext.linear(query_pos.contiguous(), w[:, c:].contiguous(), b)))
 
     # training through the fused gather and its backward (ext.TSAFusedFunction) instead of _unfused's decomposition
     # (OCC_TSA_TRAIN_FUSED=1; default off)

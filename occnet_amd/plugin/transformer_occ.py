@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import cache_epoch, ext
+from .. import derived, ext
 from .._lib import OccAmdUnsupported
 from .bricks import BaseModule, ConvModule, X3Linear
 from .registry import TRANSFORMER, build_transformer_layer_sequence
@@ -194,14 +194,11 @@ class LazyFeatures:
         reductions on the stream when the weight state changes, never read back (round 6: no host synchronisation, valid
         inside a captured graph, follows the live weights)."""
         w = value_proj.weight
-        key = (w.data_ptr(), w._version, gb.data_ptr(), gb._version, cache_epoch())
-        hit = getattr(value_proj, '_occ_range_terms', None)
-        if hit is None or hit[0] != key:
+
+        def build():
             with torch.no_grad():
-                t = torch.stack([w.detach().float().abs().sum(1).amax(), gb.detach().abs().amax()])
-            hit = (key, t, w, gb)                                # the sources stay referenced: the key stays unambiguous
-            value_proj._occ_range_terms = hit
-        return hit[1]
+                return torch.stack([w.detach().float().abs().sum(1).amax(), gb.detach().abs().amax()])
+        return derived.owned(value_proj, '_occ_range_terms').get((w, gb), build)
 
     def _absmax_words(self):
         """The 8 device words of max|x| the producer of the maps accumulated (the backbone plan's FPN output convolutions),
@@ -243,20 +240,18 @@ class LazyFeatures:
 
     def _group_bias(self, value_proj):
         """per-(level, camera) bias = (cams_embeds + level_embeds) . W^T + b: constant while the parameters are,
-        cached on the projection module (the entry holds the parameters, so the keys stay unambiguous)"""
+        cached on the projection module"""
         w, b = value_proj.weight, value_proj.bias
         o = self.owner
-        srcs = (w, b, o.level_embeds, o.cams_embeds if o.use_cams_embeds else None)
-        key = tuple((t.data_ptr(), t._version) if t is not None else None for t in srcs) + (len(self.hw), cache_epoch())
-        hit = getattr(value_proj, '_occ_group_bias', None)
-        if hit is None or hit[0] != key:
+
+        def build():
             emb = self.embeds()                                                 # (L, cam, C)
             gb = emb.view(-1, self.c) @ w.t().float()
             if b is not None:
                 gb = gb + b.float()
-            hit = (key, gb.view(len(self.hw), self.num_cam, w.shape[0]).contiguous(), srcs)
-            value_proj._occ_group_bias = hit
-        return hit[1]
+            return gb.view(len(self.hw), self.num_cam, w.shape[0]).contiguous()
+        return derived.owned(value_proj, '_occ_group_bias').get(
+            (w, b, o.level_embeds, o.cams_embeds if o.use_cams_embeds else None), build, (len(self.hw),))
 
     @property
     def group_rows(self):
@@ -361,7 +356,6 @@ class TransformerOcc(BaseModule):
         # autograd path only: dtype the MIOpen Conv3d decoder runs in under torch.autocast (None = fp32 as the
         # reference).  MIOpen's fp32 Conv3d backward costs 196 ms per step at 200x200x16, bf16 7 ms.
         self.decoder_autocast_dtype = None
-        self._dec_key, self._dec_pack = None, None
 
     def init_layers(self):
         self.level_embeds = nn.Parameter(torch.Tensor(self.num_feature_levels, self.embed_dims))
@@ -458,8 +452,8 @@ class TransformerOcc(BaseModule):
             ts += [m.conv.weight, m.norm.weight, m.norm.bias, m.norm.running_mean, m.norm.running_var]
             if m.conv.bias is not None:
                 ts.append(m.conv.bias)
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (cache_epoch(),)
-        if key != self._dec_key:
+
+        def build():
             pack = []
             with torch.no_grad():
                 for m in mods:
@@ -470,17 +464,17 @@ class TransformerOcc(BaseModule):
                         shift = shift + m.conv.bias.float() * scale
                     pack.append((ext.conv3d_pack_weight(m.conv.weight.detach().float().contiguous()),
                                  scale.contiguous(), shift.contiguous()))
-            self._dec_key, self._dec_pack = key, pack
-        return self._dec_pack
+            return pack
+        return derived.owned(self, '_dec_pack').get(ts, build)
 
     def _heads_pack(self):
         p, f = self.predicter, self.flow_predicter
         ts = (p[0].weight, p[0].bias, p[2].weight, p[2].bias, f[0].weight, f[0].bias, f[2].weight, f[2].bias)
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (cache_epoch(),)
-        if key != getattr(self, '_hp_key', None):
+
+        def build():
             with torch.no_grad():
-                self._hp_key, self._hp_val = key, ext.conv3d_heads_pack(*[t.detach().float().contiguous() for t in ts])
-        return self._hp_val
+                return ext.conv3d_heads_pack(*[t.detach().float().contiguous() for t in ts])
+        return derived.owned(self, '_hp').get(ts, build)
 
     def _fused_decoder_ok(self, bev):
         if not (self.use_fused_decoder and self.use_3d and bev.is_cuda and bev.dtype == torch.float32):

@@ -700,3 +700,50 @@ def test_value_proj_fp16_output_saturates_instead_of_overflowing(P):
             normal.view(cams * hws[0], N)[7] = False
             rel = ((got[normal] - ref[normal]).abs() / ref[normal].abs().clamp_min(1.0)).max()
             assert float(rel) < 2e-3 and not bool(big[normal].any())
+
+
+# ---- the derived-tensor caches behind the pack functions (occnet_amd/derived.py; the protocol itself: test_derived_cache_host.py)
+def test_linear_pack_weight_is_cached_per_weight_state():
+    from occnet_amd import ext
+    w = torch.randn(32, 16, generator=torch.Generator().manual_seed(70)).cuda()
+    p0 = ext.linear_pack_weight_bf16x3(w)
+    assert ext.linear_pack_weight_bf16x3(w) is p0
+    with torch.no_grad():
+        w.add_(0)                                            # same contents, new version
+    p1 = ext.linear_pack_weight_bf16x3(w)
+    assert p1 is not p0 and torch.equal(p1, p0)
+    keys = set(ext._PACKED_W.keys())
+    t = w.clone()
+    t._occ_no_cache = True                                   # a temporary: packed, never stored
+    p2 = ext.linear_pack_weight_bf16x3(t)
+    assert p2 is not p1 and p2 is not p0 and torch.equal(p2, p1) and set(ext._PACKED_W.keys()) == keys
+
+
+def test_value_proj_planes_prepare_is_cached_and_keeps_its_stack_out_of_the_pack_cache():
+    import occnet_amd
+    from occnet_amd import derived, ext
+    g = torch.Generator().manual_seed(71)
+    ws = [torch.randn(256, 16, generator=g).cuda() for _ in range(2)]
+    keys = set(ext._PACKED_W.keys())
+    hit = ext.value_proj_planes_prepare(ws)
+    assert ext.value_proj_planes_prepare(ws) is hit
+    stacked, pack, kept = hit
+    assert torch.equal(stacked, torch.cat(ws, 0)) and all(a is b for a, b in zip(kept, ws))
+    assert set(ext._PACKED_W.keys()) == keys and all(k[0] != derived.ident(stacked) for k in ext._PACKED_W.keys())
+    occnet_amd.invalidate_caches()
+    again = ext.value_proj_planes_prepare(ws)
+    assert again is not hit and again[0] is not stacked and torch.equal(again[0], stacked) and torch.equal(again[1], pack)
+    assert len(ext._PACKED_W) == 0
+
+
+def test_linear_chain_pack_and_bias_are_cached():
+    from occnet_amd import ext
+    g = torch.Generator().manual_seed(72)
+    w = torch.randn(256, 16, generator=g).cuda()
+    pw = ext.linear_chain_pack([w])
+    assert ext.linear_chain_pack([w]) is pw
+    b = torch.randn(256, generator=g).cuda()
+    parts = [(b, 256), (None, 256)]
+    pb = ext._chain_bias(parts, b.device)
+    assert ext._chain_bias(parts, b.device) is pb and pb is not pw
+    assert pb.shape == (512,) and torch.equal(pb[:256], b) and not bool(pb[256:].any())

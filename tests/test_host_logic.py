@@ -544,7 +544,7 @@ def test_fp16_value_range_terms_and_aten_scale():
     t = lf._range_terms(vp, gb)                                # a 2-element tensor on the weights' device: never read back
     l1, bm = float(t[0]), float(t[1])
     assert l1 == float(vp.weight.abs().sum(1).max()) and bm == 7.25
-    assert lf._range_terms(vp, gb) is t and vp._occ_range_terms[0][1] == vp.weight._version
+    assert lf._range_terms(vp, gb) is t and vp._occ_range_terms.keys()[0][0][1] == vp.weight._version
     with torch.no_grad():
         vp.weight.mul_(3.0)                                    # in-place update: new weight state, measured again
     assert float(lf._range_terms(vp, gb)[0]) == 3.0 * l1
