@@ -963,6 +963,55 @@ int occ_submission_score_accumulate(int pred_format, const void* pred_cls, const
                                     const int32_t* counts, int free_id, int64_t* state, void* workspace,
                                     int64_t workspace_bytes, int B, int64_t stride, int max_chunks, void* stream);
 
+/* Pictures of a batch of class grids, rendered on the device (csrc/occ_render.hip): pin-hole camera views and a bird's-eye
+ * view as label / depth / colour images.  No counterpart in the reference that runs (its utils/vis.py needs Open3D and stops on
+ * an undefined name).  A camera pixel is one ray through the caster of occ_ray_metrics_accumulate / occ_submission_rays (the
+ * same text: csrc/ray_cast.h), so it reports the voxel and the distance those report for that ray.
+ *   sem (B, X, Y, Z) class ids, dtype code 0 = uint8, 1 = int64; sem_gt NULL, or the ground truth in the same layout (its own
+ *                    dtype code): DIFF MODE, below
+ *   cams (B, V, 12) f32: per view the camera centre o[3] in ego metres, then a row-major 3 x 3 matrix D with
+ *                    ego point = o + depth * D (px, py, 1)^T for the pixel centre (px, py) of the RENDERED image
+ *   frames NULL, or (B, V, Hs, Ws, 3) u8 HWC: the background, sampled nearest; Hs, Ws are read only with frames
+ *   palette (256, 3) u8 DEVICE (needed with rgb); cat_palette (6, 3) u8 DEVICE (needed with rgb and sem_gt)
+ *   off_x/y/z = pc_range[:3], voxel_size > 0, free_id in 1..31, far > 0 (metres: the length of a ray in units of (px, py, 1)
+ *                    depth), tol >= 0 (metres), alpha in 0..256, bg_rgb = 0xRRGGBB (the background without frames)
+ *   label u8 (B, V, h, w), depth f32 (B, V, h, w), rgb u8 (B, V, h, w, 3): each may be NULL, not all three
+ * ARITHMETIC CONTRACT of pixel (i, j), float32, uncontracted, in this order:
+ *   px = (float)j + 0.5f, py = (float)i + 0.5f;  dir_k = (D[k][0] * px + D[k][1] * py) + D[k][2];  ray_k = dir_k * far;
+ *   end = ray + o, origin and end to voxel units as (p - off) / voxel_size (float32, as occ_ray_metrics_accumulate); the
+ *   "test"-phase traversal -> voxel (x, y, z), dist;  depth = dist * voxel_size;  class = sem[b][x][y][z].
+ *   HIT iff dist >= 0 and class != free_id (a ray that never enters the grid reports voxel (0, 0, 0), dist -1: a miss).
+ *   label = hit ? class & 0xff : free_id;  depth = hit ? depth : -1
+ *   rgb[k]: bg = frames ? frames[b][v][((2 i + 1) Hs) / (2 h)][((2 j + 1) Ws) / (2 w)][k] : byte k of bg_rgb;
+ *           shade = 256 - (int)fminf((depth * 192.0f) / far, 192.0f);  lit = (palette[label][k] * shade) >> 8;
+ *           hit ? (lit * alpha + bg * (256 - alpha)) >> 8 : bg            (integer arithmetic after the one truncation)
+ * DIFF MODE: the ray is cast through both grids; `label` holds a category: 0 both miss, 1 both hit with the same class and
+ *   fabsf(depth_pred - depth_gt) < tol, 2 same class but depth off, 3 both hit and the class differs, 4 only the prediction
+ *   hits, 5 only the ground truth hits.  `depth` stays the prediction's.  rgb: category 0 -> bg; 1 -> palette[class_gt & 0xff],
+ *   2..5 -> cat_palette[category]; shaded by the prediction's depth (category 5: the ground truth's), blended as above.
+ * occ_render_bev: one pixel per pillar in grid order, label u8 (B, X, Y), rgb u8 (B, X, Y, 3), each may be NULL, not both.
+ *   top = highest occupied z of the pillar; label = class(x, y, top) & 0xff, rgb[k] = (palette[label][k] * (128 + (128 * (top +
+ *   1)) / Z)) >> 8; an empty pillar: label = free_id, rgb = bg_rgb.  With sem_gt the categories are 0 both empty, 1 same class
+ *   and same top, 2 same class and another top, 3 class differs, 4 prediction only, 5 ground truth only, coloured as above
+ *   (shade from the prediction's top, category 5: the ground truth's).
+ *   workspace        occ_render_workspace_bytes(B, X, Y, Z, diff) bytes, 4-byte aligned, uninitialised: the pillar masks (uint16
+ *                    for Z <= 16, uint32 for Z <= 32) of the prediction and, with diff != 0, of the ground truth.  Z > 32:
+ *                    OCC_E_UNSUPPORTED, reported before the pointer checks (query: 0).
+ * OCC_E_INVALID with a message that names the argument: a NULL sem / cams / workspace, no output, a missing palette, a
+ * non-positive size (B * V <= 65535; h, w, Hs, Ws <= 16384), a dtype code, free_id, bg_rgb, voxel_size, far <= 0, tol < 0, alpha
+ * outside 0..256, a workspace that is too small or misaligned.  Each call: one mask launch + one render launch on `stream`, no
+ * synchronisation, no allocation, no copy; every argument is checked before the first launch.
+ */
+int64_t occ_render_workspace_bytes(int B, int X, int Y, int Z, int diff);
+int occ_render_views(const void* sem, int sem_dtype, const void* sem_gt, int sem_gt_dtype, const float* cams,
+                     const uint8_t* frames, int Hs, int Ws, const uint8_t* palette, const uint8_t* cat_palette,
+                     float off_x, float off_y, float off_z, float voxel_size, int free_id, float far, float tol,
+                     int alpha, int bg_rgb, uint8_t* label, float* depth, uint8_t* rgb, void* workspace,
+                     int64_t workspace_bytes, int B, int V, int X, int Y, int Z, int h, int w, void* stream);
+int occ_render_bev(const void* sem, int sem_dtype, const void* sem_gt, int sem_gt_dtype, const uint8_t* palette,
+                   const uint8_t* cat_palette, int free_id, int bg_rgb, uint8_t* label, uint8_t* rgb, void* workspace,
+                   int64_t workspace_bytes, int B, int X, int Y, int Z, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * (f) Training tail: both occupancy heads AND their losses as one node (csrc/occ_heads_loss.hip) — the reference's
  * predicter / flow_predicter (transformer_occ.py:132-141,318-319) followed by BEVFormerOccHead.loss / loss_single

@@ -40,7 +40,7 @@ _INT64_RESULTS = (
     "occ_conv3x3_wgrad_workspace_bytes", "occ_bn3d_relu_train_partial_floats",
     "occ_ray_metrics_state_words", "occ_ray_metrics_workspace_bytes", "occ_heads_loss_workspace_bytes",
     "occ_submission_rays_bytes", "occ_submission_rays_workspace_bytes",
-    "occ_submission_score_state_words", "occ_submission_score_workspace_bytes")
+    "occ_submission_score_state_words", "occ_submission_score_workspace_bytes", "occ_render_workspace_bytes")
 
 _lib = None
 ABI = 3     # include/occnet_amd.h: bumped whenever a signature changes (2: range scales of the fp16 value rows; 3: their weight terms in device memory)

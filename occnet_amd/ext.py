@@ -2109,6 +2109,133 @@ def submission_rays(sem_pred, flow_pred, origins, rays, pc_min, voxel_size, free
     return submission_rays_views(out, B, Tmax, R)
 
 
+def render_workspace_bytes(B, X, Y, Z, diff=False):
+    """Bytes of the pillar-mask workspace of render_views / render_bev (both grids with diff); 0 for Z > 32."""
+    return int(_lib.lib().occ_render_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z), i32(1 if diff else 0)))
+
+
+def _render_sem(what, name, t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise OccAmdError(f"{what}: {name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+    if t.dtype not in _SEM_DTYPE_CODES or not t.is_contiguous() or t.dim() != 4:
+        raise OccAmdError(f"{what}: {name} must be a contiguous (B, X, Y, Z) uint8 or int64 tensor, got {t.dtype} "
+                          f"{tuple(t.shape)}")
+
+
+def _render_u8(what, name, t, shape):
+    if t is None:
+        return
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()
+            and tuple(t.shape) == tuple(shape)):
+        raise OccAmdError(f"{what}: {name} must be a contiguous uint8 device tensor of shape {tuple(shape)}")
+
+
+def _render_out(what, name, out, want, shape, dtype, dev):
+    """One optional output: `want` False -> None; `out` given -> a view of its first elements (it may be larger)."""
+    if not want:
+        return None
+    n = 1
+    for s in shape:
+        n *= int(s)
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=dev)
+    if not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == dtype and out.is_contiguous()
+            and out.numel() >= n):
+        raise OccAmdError(f"{what}: out[{name!r}] must be a contiguous {dtype} device tensor of >= {n} elements")
+    return out.reshape(-1)[:n].view(shape)
+
+
+def _render_workspace(what, workspace, need, dev):
+    need = max(need, 256)                                             # Z > 32 answers 0: the call itself reports it
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
+        raise OccAmdError(f"{what}: workspace must be a uint8 device tensor of >= {need} bytes")
+    return workspace
+
+
+def render_views(sem, cams, pc_min, voxel_size, size, free_id=16, sem_gt=None, frames=None, palette=None, cat_palette=None,
+                 far=100.0, tol=2.0, alpha=160, bg_rgb=0, want=('label', 'depth', 'rgb'), out=None, workspace=None):
+    """Pin-hole views of a batch of class grids, in two launches on the current stream: no synchronisation, no copy
+    (csrc/occ_render.hip; the per-pixel arithmetic is written out in include/occnet_amd.h).
+    sem (B, X, Y, Z) uint8 or int64; cams (B, V, 12) float32 (vis.view_rays); size = (h, w); sem_gt: None, or the ground truth
+    as sem -> `label` holds the six agreement categories; frames: None or (B, V, Hs, Ws, 3) uint8; palette (256, 3) uint8 and,
+    with sem_gt, cat_palette (6, 3) uint8 — needed when 'rgb' is wanted.  want: which of 'label', 'depth', 'rgb' to produce;
+    out: None, or a dict of preallocated contiguous device tensors by those names (each may be larger than needed); workspace:
+    None, or a uint8 device tensor of at least render_workspace_bytes(B, X, Y, Z, sem_gt is not None) bytes.
+    -> dict of the wanted images: label (B, V, h, w) uint8, depth (B, V, h, w) float32, rgb (B, V, h, w, 3) uint8."""
+    what = "render_views"
+    _render_sem(what, "sem", sem)
+    if sem_gt is not None:
+        _render_sem(what, "sem_gt", sem_gt)
+        if sem_gt.shape != sem.shape:
+            raise OccAmdError(f"{what}: sem_gt {tuple(sem_gt.shape)} does not match sem {tuple(sem.shape)}")
+    _need_cuda_f32("cams", cams)
+    B, X, Y, Z = sem.shape
+    if cams.dim() != 3 or cams.shape[0] != B or cams.shape[2] != 12 or not cams.is_contiguous():
+        raise OccAmdError(f"{what}: cams must be a contiguous (B, V, 12) tensor, got {tuple(cams.shape)}")
+    V = cams.shape[1]
+    h, w = int(size[0]), int(size[1])
+    want = tuple(want)
+    if not want or any(k not in ('label', 'depth', 'rgb') for k in want):
+        raise OccAmdError(f"{what}: want must name at least one of 'label', 'depth', 'rgb', got {want}")
+    Hs = Ws = 0
+    if frames is not None:
+        if not isinstance(frames, torch.Tensor) or frames.dim() != 5:
+            raise OccAmdError(f"{what}: frames must be a (B, V, Hs, Ws, 3) uint8 device tensor")
+        Hs, Ws = int(frames.shape[2]), int(frames.shape[3])
+        _render_u8(what, "frames", frames, (B, V, Hs, Ws, 3))
+    _render_u8(what, "palette", palette, (256, 3))
+    _render_u8(what, "cat_palette", cat_palette, (6, 3))
+    dev = sem.device
+    out = out or {}
+    label = _render_out(what, 'label', out.get('label'), 'label' in want, (B, V, h, w), torch.uint8, dev)
+    depth = _render_out(what, 'depth', out.get('depth'), 'depth' in want, (B, V, h, w), torch.float32, dev)
+    rgb = _render_out(what, 'rgb', out.get('rgb'), 'rgb' in want, (B, V, h, w, 3), torch.uint8, dev)
+    workspace = _render_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
+    with torch.cuda.device(dev), _timed('render_views'):
+        rc = _lib.lib().occ_render_views(
+            ptr(sem), i32(_SEM_DTYPE_CODES[sem.dtype]), ptr(sem_gt),
+            i32(0 if sem_gt is None else _SEM_DTYPE_CODES[sem_gt.dtype]), ptr(cams), ptr(frames), i32(Hs), i32(Ws),
+            ptr(palette), ptr(cat_palette), f32(pc_min[0]), f32(pc_min[1]), f32(pc_min[2]), f32(voxel_size), i32(free_id),
+            f32(far), f32(tol), i32(alpha), i32(bg_rgb), ptr(label), ptr(depth), ptr(rgb), ptr(workspace),
+            i64(workspace.numel()), i32(B), i32(V), i32(X), i32(Y), i32(Z), i32(h), i32(w), stream_ptr(dev))
+    _lib.check(rc, what)
+    return {k: v for k, v in (('label', label), ('depth', depth), ('rgb', rgb)) if v is not None}
+
+
+def render_bev(sem, free_id=16, sem_gt=None, palette=None, cat_palette=None, bg_rgb=0, want=('label', 'rgb'), out=None,
+               workspace=None):
+    """Bird's-eye view of a batch of class grids — the top occupied voxel of every pillar, in grid order — in two launches on
+    the current stream (csrc/occ_render.hip).  Arguments as render_views.
+    -> dict of the wanted images: label (B, X, Y) uint8 (with sem_gt: the agreement categories), rgb (B, X, Y, 3) uint8."""
+    what = "render_bev"
+    _render_sem(what, "sem", sem)
+    if sem_gt is not None:
+        _render_sem(what, "sem_gt", sem_gt)
+        if sem_gt.shape != sem.shape:
+            raise OccAmdError(f"{what}: sem_gt {tuple(sem_gt.shape)} does not match sem {tuple(sem.shape)}")
+    B, X, Y, Z = sem.shape
+    want = tuple(want)
+    if not want or any(k not in ('label', 'rgb') for k in want):
+        raise OccAmdError(f"{what}: want must name at least one of 'label', 'rgb', got {want}")
+    _render_u8(what, "palette", palette, (256, 3))
+    _render_u8(what, "cat_palette", cat_palette, (6, 3))
+    dev = sem.device
+    out = out or {}
+    label = _render_out(what, 'label', out.get('label'), 'label' in want, (B, X, Y), torch.uint8, dev)
+    rgb = _render_out(what, 'rgb', out.get('rgb'), 'rgb' in want, (B, X, Y, 3), torch.uint8, dev)
+    workspace = _render_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
+    with torch.cuda.device(dev), _timed('render_bev'):
+        rc = _lib.lib().occ_render_bev(
+            ptr(sem), i32(_SEM_DTYPE_CODES[sem.dtype]), ptr(sem_gt),
+            i32(0 if sem_gt is None else _SEM_DTYPE_CODES[sem_gt.dtype]), ptr(palette), ptr(cat_palette), i32(free_id),
+            i32(bg_rgb), ptr(label), ptr(rgb), ptr(workspace), i64(workspace.numel()), i32(B), i32(X), i32(Y), i32(Z),
+            stream_ptr(dev))
+    _lib.check(rc, what)
+    return {k: v for k, v in (('label', label), ('rgb', rgb)) if v is not None}
+
+
 def submission_score_state_words(free_id=16):
     """int64 words of the submission score's state for classes 0..free_id (17 per class; layout: include/occnet_amd.h)."""
     n = int(_lib.lib().occ_submission_score_state_words(i32(free_id)))
