@@ -39,6 +39,7 @@
 //
 // A pixel outside the image is a dead lane: zero traversal steps, clamped legal load addresses, no store.  Predicates that select
 // a load address are 0 / 1 integers (common.h: lane_flag).  One mask launch + one render launch on the caller's stream.
+#include <limits.h>
 #include "ray_cast.h"
 
 namespace occ {
@@ -156,60 +157,34 @@ __global__ __launch_bounds__(256) void occ_render_bev_kernel(const RdArgs a) {
   }
 }
 
-template <typename MaskT>
-static void render_masks_launch(hipStream_t st, const RdArgs& a) {
-  const long pillars = (long)a.B * a.X * a.Y;
-  // gridDim.y == 1: the prediction's masks only (sem_gt is never read)
-  hipLaunchKernelGGL(ray_metrics_occupancy_kernel<MaskT>, dim3((unsigned)((pillars + 255) / 256), a.sem_gt ? 2 : 1), dim3(256),
-                     0, st, a.sem, a.sem_i64, a.sem_gt, a.gt_i64, static_cast<MaskT*>(const_cast<void*>(a.masks)), pillars, a.Z,
-                     a.free_id);
-}
+// one mask launch + one render launch of Kernel<MaskT, DIFF>, from the entry point's `a` (RdArgs), `workspace` and stream `st`
+#define OCC_RENDER_LAUNCH(Kernel, grid)                                                                                        \
+  with_mask_type(a.Z, [&](auto m) {                                                                                            \
+    using MaskT = decltype(m);                                                                                                 \
+    launch_pillar_masks(st, a.sem, a.sem_i64, a.sem_gt, a.gt_i64, static_cast<MaskT*>(workspace), a.B, a.X, a.Y, a.Z,          \
+                        a.free_id);                                                                                            \
+    if (a.sem_gt) hipLaunchKernelGGL((Kernel<MaskT, 1>), grid, dim3(256), 0, st, a);                                           \
+    else hipLaunchKernelGGL((Kernel<MaskT, 0>), grid, dim3(256), 0, st, a);                                                    \
+  })
 
-template <typename MaskT>
-static void render_views_launch(hipStream_t st, const RdArgs& a) {
-  render_masks_launch<MaskT>(st, a);
-  const dim3 grid((unsigned)((a.w + 31) / 32), (unsigned)((a.h + 7) / 8), (unsigned)(a.B * a.V));
-  if (a.sem_gt) hipLaunchKernelGGL((occ_render_views_kernel<MaskT, 1>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((occ_render_views_kernel<MaskT, 0>), grid, dim3(256), 0, st, a);
-}
-
-template <typename MaskT>
-static void render_bev_launch(hipStream_t st, const RdArgs& a) {
-  render_masks_launch<MaskT>(st, a);
-  const dim3 grid((unsigned)(((long)a.B * a.X * a.Y + 255) / 256));
-  if (a.sem_gt) hipLaunchKernelGGL((occ_render_bev_kernel<MaskT, 1>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((occ_render_bev_kernel<MaskT, 0>), grid, dim3(256), 0, st, a);
+// the checks shared by the two entry points, the grid's first; `what` names the caller in the message
+static int render_check_common(const char* what, const void* sem, int sem_dtype, const void* sem_gt, int sem_gt_dtype,
+                               const uint8_t* palette, const uint8_t* cat_palette, int free_id, int bg_rgb, const void* rgb,
+                               const void* workspace, int64_t workspace_bytes, int B, int X, int Y, int Z) {
+  const int rc = check_grid_args(what, sem, sem_dtype, sem_gt, sem_gt_dtype, free_id, workspace, workspace_bytes, B, INT_MAX, X,
+                                 Y, Z);
+  if (rc != OCC_OK) return rc;
+  OCC_CHECK_ARG((int64_t)B * X * Y <= (int64_t)1 << 30, "%s: grid %dx%dx%dx%d too large", what, B, X, Y, Z);
+  OCC_CHECK_ARG(!rgb || palette, "%s: null pointer argument (palette is needed with rgb)", what);
+  OCC_CHECK_ARG(!rgb || !sem_gt || cat_palette, "%s: null pointer argument (cat_palette is needed with rgb and sem_gt)", what);
+  OCC_CHECK_ARG(bg_rgb >= 0 && bg_rgb <= 0xffffff, "%s: bg_rgb must be 0x000000..0xffffff (got %d)", what, bg_rgb);
+  return OCC_OK;
 }
 
 }  // namespace occ
 
 extern "C" int64_t occ_render_workspace_bytes(int B, int X, int Y, int Z, int diff) {
-  if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || Z > 32) return 0;
-  return ((int64_t)B * X * Y * (Z <= 16 ? 2 : 4) * (diff ? 2 : 1) + 255) / 256 * 256;
-}
-
-// the checks shared by the two entry points; `what` names the caller in the message
-static int render_check_common(const char* what, const void* sem, int sem_dtype, const void* sem_gt, int sem_gt_dtype,
-                               const uint8_t* palette, const uint8_t* cat_palette, int free_id, int bg_rgb, const void* rgb,
-                               const void* workspace, int64_t workspace_bytes, int B, int X, int Y, int Z) {
-  using namespace occ;
-  OCC_CHECK_ARG(sem, "%s: null pointer argument (sem)", what);
-  OCC_CHECK_ARG(workspace, "%s: null pointer argument (workspace)", what);
-  OCC_CHECK_ARG(!rgb || palette, "%s: null pointer argument (palette is needed with rgb)", what);
-  OCC_CHECK_ARG(!rgb || !sem_gt || cat_palette, "%s: null pointer argument (cat_palette is needed with rgb and sem_gt)", what);
-  OCC_CHECK_ARG(B > 0 && X > 0 && Y > 0 && Z > 0, "%s: bad dimension (B=%d X=%d Y=%d Z=%d)", what, B, X, Y, Z);
-  OCC_CHECK_ARG((int64_t)X * Y * Z <= (int64_t)1 << 30 && (int64_t)B * X * Y <= (int64_t)1 << 30,
-                "%s: grid %dx%dx%dx%d too large", what, B, X, Y, Z);
-  OCC_CHECK_ARG(sem_dtype == 0 || sem_dtype == 1, "%s: sem_dtype code must be 0 (uint8) or 1 (int64), got %d", what, sem_dtype);
-  OCC_CHECK_ARG(!sem_gt || sem_gt_dtype == 0 || sem_gt_dtype == 1,
-                "%s: sem_gt_dtype code must be 0 (uint8) or 1 (int64), got %d", what, sem_gt_dtype);
-  OCC_CHECK_ARG(free_id >= 1 && free_id <= 31, "%s: free_id must be 1..31 (got %d)", what, free_id);
-  OCC_CHECK_ARG(bg_rgb >= 0 && bg_rgb <= 0xffffff, "%s: bg_rgb must be 0x000000..0xffffff (got %d)", what, bg_rgb);
-  const int64_t need = occ_render_workspace_bytes(B, X, Y, Z, sem_gt != nullptr);
-  OCC_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes,
-                (long long)need);
-  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, "%s: workspace must be 4-byte aligned", what);
-  return OCC_OK;
+  return occ::pillar_mask_bytes(B, X, Y, Z, diff ? 2 : 1);
 }
 
 extern "C" int occ_render_views(const void* sem, int sem_dtype, const void* sem_gt, int sem_gt_dtype, const float* cams,
@@ -218,15 +193,11 @@ extern "C" int occ_render_views(const void* sem, int sem_dtype, const void* sem_
                                 int alpha, int bg_rgb, uint8_t* label, float* depth, uint8_t* rgb, void* workspace,
                                 int64_t workspace_bytes, int B, int V, int X, int Y, int Z, int h, int w, void* stream) {
   using namespace occ;
-  if (Z > 32) {                                // before the pointer checks: the workspace query answers 0 bytes for it
-    set_error("render_views: Z = %d has no pillar bit mask (Z <= 32)", Z);
-    return OCC_E_UNSUPPORTED;
-  }
-  OCC_CHECK_ARG(cams, "render_views: null pointer argument (cams)");
-  OCC_CHECK_ARG(label || depth || rgb, "render_views: null pointer argument (give at least one of label, depth, rgb)");
   const int rc = render_check_common("render_views", sem, sem_dtype, sem_gt, sem_gt_dtype, palette, cat_palette, free_id, bg_rgb,
                                      rgb, workspace, workspace_bytes, B, X, Y, Z);
   if (rc != OCC_OK) return rc;
+  OCC_CHECK_ARG(cams, "render_views: null pointer argument (cams)");
+  OCC_CHECK_ARG(label || depth || rgb, "render_views: null pointer argument (give at least one of label, depth, rgb)");
   OCC_CHECK_ARG(V > 0 && h > 0 && w > 0 && (int64_t)B * V <= 65535 && h <= 16384 && w <= 16384,
                 "render_views: bad dimension (B=%d V=%d h=%d w=%d; B * V <= 65535, h, w <= 16384)", B, V, h, w);
   OCC_CHECK_ARG(!frames || (Hs > 0 && Ws > 0 && Hs <= 16384 && Ws <= 16384),
@@ -241,7 +212,7 @@ extern "C" int occ_render_views(const void* sem, int sem_dtype, const void* sem_
            tol, sem_dtype, sem_gt ? sem_gt_dtype : 0, free_id, alpha, bg_rgb, frames ? Hs : 1, frames ? Ws : 1, B, V, X, Y, Z,
            h, w};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (Z <= 16) render_views_launch<uint16_t>(st, a); else render_views_launch<uint32_t>(st, a);
+  OCC_RENDER_LAUNCH(occ_render_views_kernel, dim3((unsigned)((w + 31) / 32), (unsigned)((h + 7) / 8), (unsigned)(B * V)));
   OCC_CHECK_LAUNCH("render_views");
   return OCC_OK;
 }
@@ -250,18 +221,15 @@ extern "C" int occ_render_bev(const void* sem, int sem_dtype, const void* sem_gt
                               const uint8_t* cat_palette, int free_id, int bg_rgb, uint8_t* label, uint8_t* rgb,
                               void* workspace, int64_t workspace_bytes, int B, int X, int Y, int Z, void* stream) {
   using namespace occ;
-  if (Z > 32) {
-    set_error("render_bev: Z = %d has no pillar bit mask (Z <= 32)", Z);
-    return OCC_E_UNSUPPORTED;
-  }
-  OCC_CHECK_ARG(label || rgb, "render_bev: null pointer argument (give at least one of label, rgb)");
   const int rc = render_check_common("render_bev", sem, sem_dtype, sem_gt, sem_gt_dtype, palette, cat_palette, free_id, bg_rgb,
                                      rgb, workspace, workspace_bytes, B, X, Y, Z);
   if (rc != OCC_OK) return rc;
+  OCC_CHECK_ARG(label || rgb, "render_bev: null pointer argument (give at least one of label, rgb)");
   RdArgs a{sem, sem_gt, nullptr, nullptr, palette, cat_palette, workspace, label, nullptr, rgb, 0.f, 0.f, 0.f, 1.f, 1.f, 0.f,
            sem_dtype, sem_gt ? sem_gt_dtype : 0, free_id, 256, bg_rgb, 1, 1, B, 1, X, Y, Z, 1, 1};
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (Z <= 16) render_bev_launch<uint16_t>(st, a); else render_bev_launch<uint32_t>(st, a);
+  OCC_RENDER_LAUNCH(occ_render_bev_kernel, dim3((unsigned)(((long)B * X * Y + 255) / 256)));
   OCC_CHECK_LAUNCH("render_bev");
   return OCC_OK;
 }
+#undef OCC_RENDER_LAUNCH

@@ -1,7 +1,8 @@
-// The ray caster shared by the device-resident evaluation (ray_metrics_fused.hip) and the submission writer
-// (submission_rays.hip): class read, occupancy bit masks per pillar, the origin / end-point conversion of process_one_sample,
-// the traversal set-up of csrc/dvr_render.hip and its "test"-phase walk over the masks.  One copy of the text: both files
-// report the same voxel and the same distance for the same ray, bit for bit.
+// The ray caster shared by the device-resident evaluation (ray_metrics_fused.hip), the submission writer (submission_rays.hip)
+// and the renderer (occ_render.hip): class read, occupancy bit masks per pillar, the origin / end-point conversion of
+// process_one_sample, the traversal set-up of csrc/dvr_render.hip and its "test"-phase walk over the masks.  One copy of the
+// text: the files report the same voxel and the same distance for the same ray, bit for bit.  Below the kernels, the host side
+// their entry points share: the workspace size, the grid-argument checks, the mask launch and the mask-type dispatch.
 //
 // Lane predicates that select a load address are kept as 0 / 1 integers (common.h: lane_flag) and every load inside the
 // traversal is issued with a clamped, always-legal index; the traversal of a lane that is not cast runs zero steps.
@@ -119,6 +120,54 @@ __device__ __forceinline__ RmHit rm_cast(const RmRay& r, const MaskT* __restrict
   h.dist = was_inside ? (float)last_d : -1.f;
   h.x = lx; h.y = ly; h.z = lz;
   return h;
+}
+
+// ---- host side: what every entry point over the pillar masks asks, checks and launches -----------------------------------------
+
+// Bytes of the pillar masks of `grids` grids (1: prediction, 2: prediction + ground truth), rounded up to 256: uint16 words up to
+// Z = 16, uint32 up to Z = 32.  0: no such masks (a non-positive dimension, or Z > 32).
+inline int64_t pillar_mask_bytes(int B, int X, int Y, int Z, int grids) {
+  if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || Z > 32) return 0;
+  return ((int64_t)grids * B * X * Y * (Z <= 16 ? 2 : 4) + 255) / 256 * 256;
+}
+
+// The checks of the grid arguments; `what` names the entry point in the message.  sem_gt == nullptr: one grid.  Z > 32 answers
+// OCC_E_UNSUPPORTED before any pointer is looked at: the workspace queries answer 0 bytes for it.
+inline int check_grid_args(const char* what, const void* sem, int sem_dtype, const void* sem_gt, int sem_gt_dtype, int free_id,
+                           const void* workspace, int64_t workspace_bytes, int B, int max_B, int X, int Y, int Z) {
+  if (Z > 32) {
+    set_error("%s: Z = %d has no pillar bit mask (Z <= 32)", what, Z);
+    return OCC_E_UNSUPPORTED;
+  }
+  OCC_CHECK_ARG(sem, "%s: null pointer argument (sem)", what);
+  OCC_CHECK_ARG(workspace, "%s: null pointer argument (workspace)", what);
+  OCC_CHECK_ARG(B > 0 && B <= max_B && X > 0 && Y > 0 && Z > 0, "%s: bad dimension (B=%d X=%d Y=%d Z=%d)", what, B, X, Y, Z);
+  OCC_CHECK_ARG((int64_t)X * Y * Z <= (int64_t)1 << 30, "%s: grid %dx%dx%d too large", what, X, Y, Z);
+  OCC_CHECK_ARG(sem_dtype == 0 || sem_dtype == 1, "%s: class dtype code must be 0 (uint8) or 1 (int64), got sem_dtype = %d", what,
+                sem_dtype);
+  OCC_CHECK_ARG(!sem_gt || sem_gt_dtype == 0 || sem_gt_dtype == 1,
+                "%s: class dtype code must be 0 (uint8) or 1 (int64), got sem_gt_dtype = %d", what, sem_gt_dtype);
+  OCC_CHECK_ARG(free_id >= 1 && free_id <= 31, "%s: free_id must be 1..31 (got %d)", what, free_id);
+  const int64_t need = pillar_mask_bytes(B, X, Y, Z, sem_gt ? 2 : 1);
+  OCC_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%lld < %lld bytes)", what, (long long)workspace_bytes,
+                (long long)need);
+  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(workspace) % 4 == 0, "%s: workspace must be 4-byte aligned", what);
+  return OCC_OK;
+}
+
+// f(MaskT{}) with the mask word that holds Z bits
+template <typename F>
+inline void with_mask_type(int Z, F&& f) {
+  if (Z <= 16) f(uint16_t{}); else f(uint32_t{});
+}
+
+// The masks of the prediction, and with sem_gt of the ground truth behind them (gridDim.y == 1 never reads sem_gt).
+template <typename MaskT>
+inline void launch_pillar_masks(hipStream_t stream, const void* sem, int dt, const void* sem_gt, int gt_dt, MaskT* masks, int B,
+                                int X, int Y, int Z, int free_id) {
+  const long pillars = (long)B * X * Y;
+  hipLaunchKernelGGL(ray_metrics_occupancy_kernel<MaskT>, dim3((unsigned)((pillars + 255) / 256), sem_gt ? 2 : 1), dim3(256), 0,
+                     stream, sem, dt, sem_gt, gt_dt, masks, pillars, Z, free_id);
 }
 
 }  // namespace occ

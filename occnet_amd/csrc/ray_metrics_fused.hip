@@ -128,11 +128,7 @@ extern "C" int64_t occ_ray_metrics_state_words(int free_id) {
   return (int64_t)(free_id + 1) * occ::kRmWordsPerCls;
 }
 
-extern "C" int64_t occ_ray_metrics_workspace_bytes(int B, int X, int Y, int Z) {
-  if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || Z > 32) return 0;
-  const int64_t bytes = 2 * (int64_t)B * X * Y * (Z <= 16 ? 2 : 4);
-  return (bytes + 255) / 256 * 256;
-}
+extern "C" int64_t occ_ray_metrics_workspace_bytes(int B, int X, int Y, int Z) { return occ::pillar_mask_bytes(B, X, Y, Z, 2); }
 
 extern "C" int occ_ray_metrics_accumulate(const void* sem_pred, int sem_pred_dtype, const float* flow_pred,
                                           const void* sem_gt, int sem_gt_dtype, const float* flow_gt,
@@ -142,46 +138,26 @@ extern "C" int occ_ray_metrics_accumulate(const void* sem_pred, int sem_pred_dty
                                           int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R,
                                           void* stream) {
   using namespace occ;
-  if (Z > 32) {                                // before the pointer checks: the workspace query answers 0 bytes for it
-    set_error("ray_metrics_accumulate: Z = %d has no pillar bit mask (Z <= 32)", Z);
-    return OCC_E_UNSUPPORTED;
-  }
-  OCC_CHECK_ARG(sem_pred && flow_pred && sem_gt && flow_gt && origins && rays && state && workspace,
-                "ray_metrics_accumulate: null pointer argument");
+  const int rc = check_grid_args("ray_metrics_accumulate", sem_pred, sem_pred_dtype, sem_gt, sem_gt_dtype, free_id, workspace,
+                                 workspace_bytes, B, 65535, X, Y, Z);
+  if (rc != OCC_OK) return rc;
+  OCC_CHECK_ARG(flow_pred && sem_gt && flow_gt && origins && rays && state, "ray_metrics_accumulate: null pointer argument");
   OCC_CHECK_ARG((rows_pred == nullptr) == (rows_gt == nullptr),
                 "ray_metrics_accumulate: rows_pred and rows_gt must be given together");
-  OCC_CHECK_ARG(B > 0 && X > 0 && Y > 0 && Z > 0 && R > 0 && B <= 65535,
-                "ray_metrics_accumulate: bad dimension (B=%d X=%d Y=%d Z=%d R=%d)", B, X, Y, Z, R);
-  OCC_CHECK_ARG((int64_t)X * Y * Z <= (int64_t)1 << 30, "ray_metrics_accumulate: grid %dx%dx%d too large", X, Y, Z);
+  OCC_CHECK_ARG(R > 0, "ray_metrics_accumulate: bad dimension (R=%d)", R);
   OCC_CHECK_ARG(Tmax >= 1 && Tmax <= 8, "ray_metrics_accumulate: origins per sample must be 1..8 (Tmax=%d)", Tmax);
-  OCC_CHECK_ARG((sem_pred_dtype == 0 || sem_pred_dtype == 1) && (sem_gt_dtype == 0 || sem_gt_dtype == 1),
-                "ray_metrics_accumulate: dtype code must be 0 (uint8) or 1 (int64), got %d / %d", sem_pred_dtype,
-                sem_gt_dtype);
-  OCC_CHECK_ARG(free_id >= 1 && free_id < kRmMaxCls, "ray_metrics_accumulate: free_id must be 1..%d (got %d)",
-                kRmMaxCls - 1, free_id);
   OCC_CHECK_ARG(voxel_size > 0.f, "ray_metrics_accumulate: voxel_size must be positive");
-  OCC_CHECK_ARG(workspace_bytes >= occ_ray_metrics_workspace_bytes(B, X, Y, Z),
-                "ray_metrics_accumulate: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                (long long)occ_ray_metrics_workspace_bytes(B, X, Y, Z));
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const long pillars = (long)B * X * Y;
-  const dim3 og((unsigned)((pillars + 255) / 256), 2), cg((unsigned)((R + 255) / 256), (unsigned)Tmax, (unsigned)B);
+  const dim3 cg((unsigned)((R + 255) / 256), (unsigned)Tmax, (unsigned)B);
   unsigned long long* s = reinterpret_cast<unsigned long long*>(state);
-  if (Z <= 16) {
-    uint16_t* masks = static_cast<uint16_t*>(workspace);
-    hipLaunchKernelGGL(ray_metrics_occupancy_kernel<uint16_t>, og, dim3(256), 0, st, sem_pred, sem_pred_dtype, sem_gt,
-                       sem_gt_dtype, masks, pillars, Z, free_id);
-    hipLaunchKernelGGL(ray_metrics_cast_kernel<uint16_t>, cg, dim3(256), 0, st, sem_pred, sem_pred_dtype, flow_pred, sem_gt,
-                       sem_gt_dtype, flow_gt, origins, origin_counts, rays, masks, s, rows_pred, rows_gt, off_x, off_y,
-                       off_z, voxel_size, free_id, B, Tmax, X, Y, Z, R);
-  } else {
-    uint32_t* masks = static_cast<uint32_t*>(workspace);
-    hipLaunchKernelGGL(ray_metrics_occupancy_kernel<uint32_t>, og, dim3(256), 0, st, sem_pred, sem_pred_dtype, sem_gt,
-                       sem_gt_dtype, masks, pillars, Z, free_id);
-    hipLaunchKernelGGL(ray_metrics_cast_kernel<uint32_t>, cg, dim3(256), 0, st, sem_pred, sem_pred_dtype, flow_pred, sem_gt,
-                       sem_gt_dtype, flow_gt, origins, origin_counts, rays, masks, s, rows_pred, rows_gt, off_x, off_y,
-                       off_z, voxel_size, free_id, B, Tmax, X, Y, Z, R);
-  }
+  with_mask_type(Z, [&](auto m) {
+    using MaskT = decltype(m);
+    MaskT* masks = static_cast<MaskT*>(workspace);
+    launch_pillar_masks(st, sem_pred, sem_pred_dtype, sem_gt, sem_gt_dtype, masks, B, X, Y, Z, free_id);
+    hipLaunchKernelGGL(ray_metrics_cast_kernel<MaskT>, cg, dim3(256), 0, st, sem_pred, sem_pred_dtype, flow_pred, sem_gt,
+                       sem_gt_dtype, flow_gt, origins, origin_counts, rays, masks, s, rows_pred, rows_gt, off_x, off_y, off_z,
+                       voxel_size, free_id, B, Tmax, X, Y, Z, R);
+  });
   OCC_CHECK_LAUNCH("ray_metrics_accumulate");
   return OCC_OK;
 }

@@ -65,25 +65,6 @@ __global__ __launch_bounds__(256) void submission_rays_kernel(
   }
 }
 
-template <typename MaskT, typename OriginT>
-static void submission_launch(hipStream_t st, const void* sem_pred, int dt, const float* flow_pred, const void* origins,
-                              const int32_t* origin_counts, const float* rays, float off_x, float off_y, float off_z,
-                              float voxel_size, int free_id, unsigned char* out, void* workspace, int B, int Tmax, int X,
-                              int Y, int Z, int R) {
-  const long pillars = (long)B * X * Y;
-  const int64_t n = (int64_t)B * Tmax * R;
-  MaskT* masks = static_cast<MaskT*>(workspace);
-  signed char* cls = reinterpret_cast<signed char*>(out);
-  _Float16* dist = reinterpret_cast<_Float16*>(out + sub_align256(n));
-  _Float16* flow = reinterpret_cast<_Float16*>(out + sub_align256(n) + sub_align256(2 * n));
-  // gridDim.y == 1: the prediction's masks only (sem_gt is never read)
-  hipLaunchKernelGGL(ray_metrics_occupancy_kernel<MaskT>, dim3((unsigned)((pillars + 255) / 256), 1), dim3(256), 0, st,
-                     sem_pred, dt, (const void*)nullptr, 0, masks, pillars, Z, free_id);
-  hipLaunchKernelGGL((submission_rays_kernel<MaskT, OriginT>), dim3((unsigned)((R + 255) / 256), (unsigned)Tmax, (unsigned)B),
-                     dim3(256), 0, st, sem_pred, dt, flow_pred, static_cast<const OriginT*>(origins), origin_counts, rays,
-                     masks, cls, dist, flow, off_x, off_y, off_z, voxel_size, Tmax, X, Y, Z, R);
-}
-
 }  // namespace occ
 
 extern "C" int64_t occ_submission_rays_bytes(int B, int Tmax, int R) {
@@ -93,8 +74,7 @@ extern "C" int64_t occ_submission_rays_bytes(int B, int Tmax, int R) {
 }
 
 extern "C" int64_t occ_submission_rays_workspace_bytes(int B, int X, int Y, int Z) {
-  if (B <= 0 || X <= 0 || Y <= 0 || Z <= 0 || Z > 32) return 0;
-  return occ::sub_align256((int64_t)B * X * Y * (Z <= 16 ? 2 : 4));
+  return occ::pillar_mask_bytes(B, X, Y, Z, 1);
 }
 
 extern "C" int occ_submission_rays(const void* sem_pred, int sem_pred_dtype, const float* flow_pred, const void* origins,
@@ -103,39 +83,37 @@ extern "C" int occ_submission_rays(const void* sem_pred, int sem_pred_dtype, con
                                    void* workspace, int64_t workspace_bytes, int B, int Tmax, int X, int Y, int Z, int R,
                                    void* stream) {
   using namespace occ;
-  if (Z > 32) {                                // before the pointer checks: the workspace query answers 0 bytes for it
-    set_error("submission_rays: Z = %d has no pillar bit mask (Z <= 32)", Z);
-    return OCC_E_UNSUPPORTED;
-  }
-  OCC_CHECK_ARG(sem_pred && flow_pred && origins && rays && out && workspace, "submission_rays: null pointer argument");
-  OCC_CHECK_ARG(B > 0 && X > 0 && Y > 0 && Z > 0 && R > 0 && B <= 65535 && R <= (1 << 24),
-                "submission_rays: bad dimension (B=%d X=%d Y=%d Z=%d R=%d)", B, X, Y, Z, R);
-  OCC_CHECK_ARG((int64_t)X * Y * Z <= (int64_t)1 << 30, "submission_rays: grid %dx%dx%d too large", X, Y, Z);
+  const int rc = check_grid_args("submission_rays", sem_pred, sem_pred_dtype, nullptr, 0, free_id, workspace, workspace_bytes, B,
+                                 65535, X, Y, Z);
+  if (rc != OCC_OK) return rc;
+  OCC_CHECK_ARG(flow_pred && origins && rays && out, "submission_rays: null pointer argument");
+  OCC_CHECK_ARG(R > 0 && R <= (1 << 24), "submission_rays: bad dimension (R=%d)", R);
   OCC_CHECK_ARG(Tmax >= 1 && Tmax <= 8, "submission_rays: origins per sample must be 1..8 (Tmax=%d)", Tmax);
-  OCC_CHECK_ARG(sem_pred_dtype == 0 || sem_pred_dtype == 1,
-                "submission_rays: class dtype code must be 0 (uint8) or 1 (int64), got %d", sem_pred_dtype);
   OCC_CHECK_ARG(origins_dtype == 0 || origins_dtype == 1,
                 "submission_rays: origins dtype code must be 0 (float32) or 1 (float64), got %d", origins_dtype);
-  OCC_CHECK_ARG(free_id >= 1 && free_id <= 31, "submission_rays: free_id must be 1..31 (got %d)", free_id);
   OCC_CHECK_ARG(voxel_size > 0.f, "submission_rays: voxel_size must be positive");
   OCC_CHECK_ARG(out_bytes >= occ_submission_rays_bytes(B, Tmax, R), "submission_rays: output too small (%lld < %lld bytes)",
                 (long long)out_bytes, (long long)occ_submission_rays_bytes(B, Tmax, R));
-  OCC_CHECK_ARG(workspace_bytes >= occ_submission_rays_workspace_bytes(B, X, Y, Z),
-                "submission_rays: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                (long long)occ_submission_rays_workspace_bytes(B, X, Y, Z));
-  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(out) % 4 == 0 && reinterpret_cast<uintptr_t>(workspace) % 4 == 0,
-                "submission_rays: out and workspace must be 4-byte aligned");
+  OCC_CHECK_ARG(reinterpret_cast<uintptr_t>(out) % 4 == 0, "submission_rays: out must be 4-byte aligned");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   unsigned char* o = static_cast<unsigned char*>(out);
-#define OCC_SUB_LAUNCH(MaskT, OriginT)                                                                                      \
-  submission_launch<MaskT, OriginT>(st, sem_pred, sem_pred_dtype, flow_pred, origins, origin_counts, rays, off_x, off_y,    \
-                                    off_z, voxel_size, free_id, o, workspace, B, Tmax, X, Y, Z, R)
-  if (Z <= 16) {
-    if (origins_dtype) OCC_SUB_LAUNCH(uint16_t, double); else OCC_SUB_LAUNCH(uint16_t, float);
-  } else {
-    if (origins_dtype) OCC_SUB_LAUNCH(uint32_t, double); else OCC_SUB_LAUNCH(uint32_t, float);
-  }
-#undef OCC_SUB_LAUNCH
+  const int64_t n = (int64_t)B * Tmax * R;
+  signed char* cls = reinterpret_cast<signed char*>(o);
+  _Float16* dist = reinterpret_cast<_Float16*>(o + sub_align256(n));
+  _Float16* flow = reinterpret_cast<_Float16*>(o + sub_align256(n) + sub_align256(2 * n));
+  const dim3 grid((unsigned)((R + 255) / 256), (unsigned)Tmax, (unsigned)B);
+  with_mask_type(Z, [&](auto m) {
+    using MaskT = decltype(m);
+    MaskT* masks = static_cast<MaskT*>(workspace);
+    launch_pillar_masks(st, sem_pred, sem_pred_dtype, nullptr, 0, masks, B, X, Y, Z, free_id);
+    auto cast = [&](auto origin) {
+      using OriginT = decltype(origin);
+      hipLaunchKernelGGL((submission_rays_kernel<MaskT, OriginT>), grid, dim3(256), 0, st, sem_pred, sem_pred_dtype, flow_pred,
+                         static_cast<const OriginT*>(origins), origin_counts, rays, masks, cls, dist, flow, off_x, off_y, off_z,
+                         voxel_size, Tmax, X, Y, Z, R);
+    };
+    if (origins_dtype) cast(double{}); else cast(float{});
+  });
   OCC_CHECK_LAUNCH("submission_rays");
   return OCC_OK;
 }

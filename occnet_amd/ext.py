@@ -1960,6 +1960,37 @@ def dvr_render_forward(sigma, origin, points, tindex, grid=None, phase_name="tes
 
 
 _SEM_DTYPE_CODES = {torch.uint8: 0, torch.int64: 1}
+_ORIGIN_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}
+
+
+# ---- the argument checks shared by the evaluation wrappers (ray metrics, submission rows and score, renderer) ----
+def _eval_grid(what, name, t):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise OccAmdError(f"{what}: {name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+    if t.dtype not in _SEM_DTYPE_CODES or not t.is_contiguous() or t.dim() != 4:
+        raise OccAmdError(f"{what}: {name} must be a contiguous (B, X, Y, Z) uint8 or int64 tensor, got {t.dtype} "
+                          f"{tuple(t.shape)}")
+
+
+def _eval_origin_counts(what, origin_counts, B):
+    if origin_counts is not None and not (origin_counts.is_cuda and origin_counts.dtype == torch.int32
+                                          and origin_counts.is_contiguous() and origin_counts.numel() == B):
+        raise OccAmdError(f"{what}: origin_counts must be a contiguous int32 device tensor of B entries")
+
+
+def _eval_state(what, state, words):
+    if not (state.is_cuda and state.dtype == torch.int64 and state.is_contiguous() and state.numel() == words):
+        raise OccAmdError(f"{what}: state must be a contiguous int64 device tensor of {words} words")
+
+
+def _eval_workspace(what, workspace, need, dev):
+    """The caller's uint8 device workspace once it is seen to hold `need` bytes, or a fresh one."""
+    need = max(need, 256)                                             # Z > 32 answers 0: the call itself reports it
+    if workspace is None:
+        return torch.empty(need, dtype=torch.uint8, device=dev)
+    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
+        raise OccAmdError(f"{what}: workspace must be a uint8 device tensor of >= {need} bytes")
+    return workspace
 
 
 def ray_metrics_state_words(free_id=16):
@@ -1984,33 +2015,22 @@ def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins,
     workspace: None, or a uint8 device tensor of at least ray_metrics_workspace_bytes(B, X, Y, Z) bytes.
     -> None, or with return_rays (rows_pred, rows_gt), each (B, Tmax, R, 4) float32 (label, depth, flow_x, flow_y); rows of
     origins beyond origin_counts stay zero."""
+    what = "ray_metrics_accumulate"
     for n, t in (("flow_pred", flow_pred), ("flow_gt", flow_gt), ("origins", origins), ("rays", rays)):
         _need_cuda_f32(n, t)
-    for n, t in (("sem_pred", sem_pred), ("sem_gt", sem_gt)):
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise OccAmdError(f"{n} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
-        if t.dtype not in _SEM_DTYPE_CODES or not t.is_contiguous():
-            raise OccAmdError(f"{n} must be a contiguous uint8 or int64 tensor, got {t.dtype}")
-    if not (state.is_cuda and state.dtype == torch.int64 and state.is_contiguous()
-            and state.numel() == ray_metrics_state_words(free_id)):
-        raise OccAmdError("ray_metrics_accumulate: state must be a contiguous int64 device tensor of "
-                          f"{ray_metrics_state_words(free_id)} words")
-    if sem_pred.dim() != 4 or sem_gt.shape != sem_pred.shape or origins.dim() != 3 or rays.dim() != 2:
+    _eval_grid(what, "sem_pred", sem_pred)
+    _eval_grid(what, "sem_gt", sem_gt)
+    _eval_state(what, state, ray_metrics_state_words(free_id))
+    if sem_gt.shape != sem_pred.shape or origins.dim() != 3 or rays.dim() != 2:
         raise OccAmdError("ray_metrics_accumulate: expected sem (B,X,Y,Z), flow (B,X,Y,Z,2), origins (B,T,3), rays (R,3)")
     B, X, Y, Z = sem_pred.shape
     Tmax, R = origins.shape[1], rays.shape[0]
     if (tuple(flow_pred.shape) != (B, X, Y, Z, 2) or flow_gt.shape != flow_pred.shape or origins.shape[0] != B
             or origins.shape[2] != 3 or rays.shape[1] != 3):
         raise OccAmdError("ray_metrics_accumulate: inconsistent shapes")
-    if origin_counts is not None and not (origin_counts.is_cuda and origin_counts.dtype == torch.int32
-                                          and origin_counts.is_contiguous() and origin_counts.numel() == B):
-        raise OccAmdError("ray_metrics_accumulate: origin_counts must be a contiguous int32 device tensor of B entries")
+    _eval_origin_counts(what, origin_counts, B)
     dev = sem_pred.device
-    need = max(ray_metrics_workspace_bytes(B, X, Y, Z), 256)      # Z > 32 answers 0: the call itself reports it
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
-        raise OccAmdError(f"ray_metrics_accumulate: workspace must be a uint8 device tensor of >= {need} bytes")
+    workspace = _eval_workspace(what, workspace, ray_metrics_workspace_bytes(B, X, Y, Z), dev)
     rows_pred = rows_gt = None
     if return_rays:
         rows_pred = torch.zeros((B, Tmax, R, 4), dtype=torch.float32, device=dev)
@@ -2022,7 +2042,7 @@ def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins,
             f32(pc_min[0]), f32(pc_min[1]), f32(pc_min[2]), f32(voxel_size), i32(free_id), ptr(state), ptr(rows_pred),
             ptr(rows_gt), ptr(workspace), i64(workspace.numel()), i32(B), i32(Tmax), i32(X), i32(Y), i32(Z), i32(R),
             stream_ptr(dev))
-    _lib.check(rc, "ray_metrics_accumulate")
+    _lib.check(rc, what)
     return (rows_pred, rows_gt) if return_rays else None
 
 
@@ -2069,31 +2089,23 @@ def submission_rays(sem_pred, flow_pred, origins, rays, pc_min, voxel_size, free
     submission_rays_workspace_bytes(B, X, Y, Z) bytes.
     -> (cls, dist, flow): (B, Tmax, R) int8, (B, Tmax, R) float16, (B, Tmax, R, 2) float16 views into the packed buffer; rows
     of origins beyond origin_counts are not written (zero when `out` is None)."""
+    what = "submission_rays"
     for n, t in (("flow_pred", flow_pred), ("rays", rays)):
         _need_cuda_f32(n, t)
-    if not isinstance(sem_pred, torch.Tensor) or not sem_pred.is_cuda:
-        raise OccAmdError("sem_pred must be a device (HIP) tensor: the MI355X path has no CPU fallback")
-    if sem_pred.dtype not in _SEM_DTYPE_CODES or not sem_pred.is_contiguous():
-        raise OccAmdError(f"sem_pred must be a contiguous uint8 or int64 tensor, got {sem_pred.dtype}")
+    _eval_grid(what, "sem_pred", sem_pred)
     if not isinstance(origins, torch.Tensor) or not origins.is_cuda:
         raise OccAmdError("origins must be a device (HIP) tensor: the MI355X path has no CPU fallback")
     if origins.dtype not in _ORIGIN_DTYPE_CODES or not origins.is_contiguous():
         raise OccAmdError(f"origins must be a contiguous float32 or float64 tensor, got {origins.dtype}")
-    if sem_pred.dim() != 4 or origins.dim() != 3 or rays.dim() != 2:
+    if origins.dim() != 3 or rays.dim() != 2:
         raise OccAmdError("submission_rays: expected sem (B,X,Y,Z), flow (B,X,Y,Z,2), origins (B,T,3), rays (R,3)")
     B, X, Y, Z = sem_pred.shape
     Tmax, R = origins.shape[1], rays.shape[0]
     if (tuple(flow_pred.shape) != (B, X, Y, Z, 2) or origins.shape[0] != B or origins.shape[2] != 3 or rays.shape[1] != 3):
         raise OccAmdError("submission_rays: inconsistent shapes")
-    if origin_counts is not None and not (origin_counts.is_cuda and origin_counts.dtype == torch.int32
-                                          and origin_counts.is_contiguous() and origin_counts.numel() == B):
-        raise OccAmdError("submission_rays: origin_counts must be a contiguous int32 device tensor of B entries")
+    _eval_origin_counts(what, origin_counts, B)
     dev = sem_pred.device
-    need = max(submission_rays_workspace_bytes(B, X, Y, Z), 256)      # Z > 32 answers 0: the call itself reports it
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
-        raise OccAmdError(f"submission_rays: workspace must be a uint8 device tensor of >= {need} bytes")
+    workspace = _eval_workspace(what, workspace, submission_rays_workspace_bytes(B, X, Y, Z), dev)
     need_out = max(submission_rays_bytes(B, Tmax, R), 256)            # Tmax = 0 answers 0: the call itself reports it
     if out is None:
         out = torch.zeros(need_out, dtype=torch.uint8, device=dev)
@@ -2105,21 +2117,13 @@ def submission_rays(sem_pred, flow_pred, origins, rays, pc_min, voxel_size, free
             i32(_ORIGIN_DTYPE_CODES[origins.dtype]), ptr(origin_counts), ptr(rays), f32(pc_min[0]), f32(pc_min[1]),
             f32(pc_min[2]), f32(voxel_size), i32(free_id), ptr(out), i64(out.numel()), ptr(workspace),
             i64(workspace.numel()), i32(B), i32(Tmax), i32(X), i32(Y), i32(Z), i32(R), stream_ptr(dev))
-    _lib.check(rc, "submission_rays")
+    _lib.check(rc, what)
     return submission_rays_views(out, B, Tmax, R)
 
 
 def render_workspace_bytes(B, X, Y, Z, diff=False):
     """Bytes of the pillar-mask workspace of render_views / render_bev (both grids with diff); 0 for Z > 32."""
     return int(_lib.lib().occ_render_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z), i32(1 if diff else 0)))
-
-
-def _render_sem(what, name, t):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise OccAmdError(f"{what}: {name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
-    if t.dtype not in _SEM_DTYPE_CODES or not t.is_contiguous() or t.dim() != 4:
-        raise OccAmdError(f"{what}: {name} must be a contiguous (B, X, Y, Z) uint8 or int64 tensor, got {t.dtype} "
-                          f"{tuple(t.shape)}")
 
 
 def _render_u8(what, name, t, shape):
@@ -2145,15 +2149,6 @@ def _render_out(what, name, out, want, shape, dtype, dev):
     return out.reshape(-1)[:n].view(shape)
 
 
-def _render_workspace(what, workspace, need, dev):
-    need = max(need, 256)                                             # Z > 32 answers 0: the call itself reports it
-    if workspace is None:
-        return torch.empty(need, dtype=torch.uint8, device=dev)
-    if not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
-        raise OccAmdError(f"{what}: workspace must be a uint8 device tensor of >= {need} bytes")
-    return workspace
-
-
 def render_views(sem, cams, pc_min, voxel_size, size, free_id=16, sem_gt=None, frames=None, palette=None, cat_palette=None,
                  far=100.0, tol=2.0, alpha=160, bg_rgb=0, want=('label', 'depth', 'rgb'), out=None, workspace=None):
     """Pin-hole views of a batch of class grids, in two launches on the current stream: no synchronisation, no copy
@@ -2165,9 +2160,9 @@ def render_views(sem, cams, pc_min, voxel_size, size, free_id=16, sem_gt=None, f
     None, or a uint8 device tensor of at least render_workspace_bytes(B, X, Y, Z, sem_gt is not None) bytes.
     -> dict of the wanted images: label (B, V, h, w) uint8, depth (B, V, h, w) float32, rgb (B, V, h, w, 3) uint8."""
     what = "render_views"
-    _render_sem(what, "sem", sem)
+    _eval_grid(what, "sem", sem)
     if sem_gt is not None:
-        _render_sem(what, "sem_gt", sem_gt)
+        _eval_grid(what, "sem_gt", sem_gt)
         if sem_gt.shape != sem.shape:
             raise OccAmdError(f"{what}: sem_gt {tuple(sem_gt.shape)} does not match sem {tuple(sem.shape)}")
     _need_cuda_f32("cams", cams)
@@ -2192,7 +2187,7 @@ def render_views(sem, cams, pc_min, voxel_size, size, free_id=16, sem_gt=None, f
     label = _render_out(what, 'label', out.get('label'), 'label' in want, (B, V, h, w), torch.uint8, dev)
     depth = _render_out(what, 'depth', out.get('depth'), 'depth' in want, (B, V, h, w), torch.float32, dev)
     rgb = _render_out(what, 'rgb', out.get('rgb'), 'rgb' in want, (B, V, h, w, 3), torch.uint8, dev)
-    workspace = _render_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
+    workspace = _eval_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
     with torch.cuda.device(dev), _timed('render_views'):
         rc = _lib.lib().occ_render_views(
             ptr(sem), i32(_SEM_DTYPE_CODES[sem.dtype]), ptr(sem_gt),
@@ -2210,9 +2205,9 @@ def render_bev(sem, free_id=16, sem_gt=None, palette=None, cat_palette=None, bg_
     the current stream (csrc/occ_render.hip).  Arguments as render_views.
     -> dict of the wanted images: label (B, X, Y) uint8 (with sem_gt: the agreement categories), rgb (B, X, Y, 3) uint8."""
     what = "render_bev"
-    _render_sem(what, "sem", sem)
+    _eval_grid(what, "sem", sem)
     if sem_gt is not None:
-        _render_sem(what, "sem_gt", sem_gt)
+        _eval_grid(what, "sem_gt", sem_gt)
         if sem_gt.shape != sem.shape:
             raise OccAmdError(f"{what}: sem_gt {tuple(sem_gt.shape)} does not match sem {tuple(sem.shape)}")
     B, X, Y, Z = sem.shape
@@ -2225,7 +2220,7 @@ def render_bev(sem, free_id=16, sem_gt=None, palette=None, cat_palette=None, bg_
     out = out or {}
     label = _render_out(what, 'label', out.get('label'), 'label' in want, (B, X, Y), torch.uint8, dev)
     rgb = _render_out(what, 'rgb', out.get('rgb'), 'rgb' in want, (B, X, Y, 3), torch.uint8, dev)
-    workspace = _render_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
+    workspace = _eval_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
     with torch.cuda.device(dev), _timed('render_bev'):
         rc = _lib.lib().occ_render_bev(
             ptr(sem), i32(_SEM_DTYPE_CODES[sem.dtype]), ptr(sem_gt),
@@ -2282,18 +2277,11 @@ def submission_score_accumulate(state, pred, gt, counts, stride, free_id=16, wor
     B, stride = int(counts.numel()), int(stride)
     if B < 1 or stride < 1:
         raise OccAmdError(f"submission_score_accumulate: bad dimension (B={B} stride={stride})")
-    if not (state.is_cuda and state.dtype == torch.int64 and state.is_contiguous()
-            and state.numel() == submission_score_state_words(free_id)):
-        raise OccAmdError("submission_score_accumulate: state must be a contiguous int64 device tensor of "
-                          f"{submission_score_state_words(free_id)} words")
+    _eval_state("submission_score_accumulate", state, submission_score_state_words(free_id))
     pf, pc, pd, pfl = _score_side("pred", pred, B, stride)
     gf, gc, gd, gfl = _score_side("gt", gt, B, stride)
     dev = state.device
-    need = max(submission_score_workspace_bytes(B), 256)
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not (workspace.is_cuda and workspace.dtype == torch.uint8 and workspace.numel() >= need):
-        raise OccAmdError(f"submission_score_accumulate: workspace must be a uint8 device tensor of >= {need} bytes")
+    workspace = _eval_workspace("submission_score_accumulate", workspace, submission_score_workspace_bytes(B), dev)
     with torch.cuda.device(dev), _timed('submission_score_accumulate'):
         rc = _lib.lib().occ_submission_score_accumulate(
             i32(pf), ptr(pc), ptr(pd), ptr(pfl), i32(gf), ptr(gc), ptr(gd), ptr(gfl), ptr(counts), i32(free_id), ptr(state),
@@ -2301,7 +2289,6 @@ def submission_score_accumulate(state, pred, gt, counts, stride, free_id=16, wor
     _lib.check(rc, "submission_score_accumulate")
 
 
-_ORIGIN_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}
 _HEADS_LOSS_PARAMS = ("w1_occ", "b1_occ", "w2_occ", "b2_occ", "w1_flow", "b1_flow", "w2_flow", "b2_flow")
 
 

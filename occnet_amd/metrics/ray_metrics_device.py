@@ -21,43 +21,22 @@ import warnings
 import numpy as np
 import torch
 
-from .ray_metrics import flow_class_names, generate_lidar_rays, occ_class_names
+from .device_common import DeviceRays, IntState, class_grid, flow_grid, occ_size
+from .ray_metrics import flow_class_names, occ_class_names
 
 QUANTUM = 2.0 ** -28          # m/s per unit of ave_sum
 ROWS = 14
 
 
-class RayMetrics:
+class RayMetrics(IntState):
     def __init__(self, pc_range, voxel_size, free_id=16, rays=None, device='cuda'):
+        super().__init__(ROWS, free_id, device)
         self.pc_range = [float(v) for v in pc_range]
         self.voxel_size = float(voxel_size)
-        self.free_id = int(free_id)
-        self.ncls = self.free_id + 1
-        self.occ_size = [int(round((self.pc_range[3 + k] - self.pc_range[k]) / self.voxel_size)) for k in range(3)]
-        self.device = torch.device(device)
-        self._rays_host = generate_lidar_rays() if rays is None else rays
-        self._rays = None
-        self._workspace = None
-        self.state = torch.zeros(ROWS * self.ncls, dtype=torch.int64, device=self.device)
+        self.occ_size = occ_size(self.pc_range, self.voxel_size)
+        self._rays_dev = DeviceRays(rays, self.device)
 
     # ---- accumulation --------------------------------------------------------------------------------------------
-    def _rays_dev(self):
-        if self._rays is None:
-            r = self._rays_host
-            r = torch.from_numpy(np.ascontiguousarray(r, dtype=np.float32)) if isinstance(r, np.ndarray) else r
-            self._rays = r.to(self.device, torch.float32).contiguous()
-        return self._rays
-
-    def _sem(self, t):
-        t = torch.as_tensor(t)
-        if t.dtype not in (torch.uint8, torch.int64):
-            t = t.to(torch.int64)
-        t = t.to(self.device)
-        return t.reshape([-1] + self.occ_size).contiguous()
-
-    def _flow(self, t):
-        return torch.as_tensor(t).to(self.device, torch.float32).reshape([-1] + self.occ_size + [2]).contiguous()
-
     def update(self, sem_pred, flow_pred, sem_gt, flow_gt, lidar_origins, return_rays=False, origin_counts=None):
         """Add a batch (or one sample) to the state.  sem_* (B, X, Y, Z) uint8 / int64 — or any shape with X*Y*Z
         elements per sample, as main() takes them —, flow_* (B, X, Y, Z, 2) float32, lidar_origins (B, T, 3) ego metres
@@ -65,35 +44,16 @@ class RayMetrics:
         int32 device tensor.  Device tensors are used as they are; the call enqueues two kernels and never synchronises.
         -> None, or with return_rays (rows_pred, rows_gt) (B, T, R, 4) device tensors in process_one_sample's order."""
         from .. import ext
-        sem_pred, sem_gt = self._sem(sem_pred), self._sem(sem_gt)
-        flow_pred, flow_gt = self._flow(flow_pred), self._flow(flow_gt)
+        sem_pred, sem_gt = (class_grid(n, t, self.occ_size, self.device, convert=True)
+                            for n, t in (('sem_pred', sem_pred), ('sem_gt', sem_gt)))
+        flow_pred, flow_gt = (flow_grid(n, t, self.occ_size, self.device, convert=True)
+                              for n, t in (('flow_pred', flow_pred), ('flow_gt', flow_gt)))
         origins = torch.as_tensor(lidar_origins).to(self.device, torch.float32).reshape(sem_pred.shape[0], -1, 3)
         B, X, Y, Z = sem_pred.shape
-        need = max(ext.ray_metrics_workspace_bytes(B, X, Y, Z), 256)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
         return ext.ray_metrics_accumulate(self.state, sem_pred, flow_pred, sem_gt, flow_gt, origins.contiguous(),
                                           self._rays_dev(), self.pc_range[:3], self.voxel_size, self.free_id,
                                           origin_counts=origin_counts, return_rays=return_rays,
-                                          workspace=self._workspace)
-
-    def merge(self, other):
-        """Add another evaluator's state (same classes): integer addition, exact in any order."""
-        if other.state.numel() != self.state.numel():
-            raise ValueError("RayMetrics.merge: states of different class counts")
-        self.state += other.state.to(self.state.device)
-        return self
-
-    def all_reduce(self):
-        """Sum the state over the ranks of the default process group (no-op without one)."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.state, op=dist.ReduceOp.SUM)
-        return self
-
-    def reset(self):
-        self.state.zero_()
-        return self
+                                          workspace=self._grown_workspace(ext.ray_metrics_workspace_bytes(B, X, Y, Z)))
 
     # ---- scores --------------------------------------------------------------------------------------------------
     def compute(self):

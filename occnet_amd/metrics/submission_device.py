@@ -16,23 +16,9 @@ import gzip
 import os
 import pickle
 
-import numpy as np
 import torch
 
-from .ray_metrics import generate_lidar_rays
-
-
-class _Slot:
-    """One in-flight batch: packed device buffer (and the ground truth's, for add_scored), mask workspace, pinned host copy, pinned staging of origins and counts."""
-
-    def __init__(self):
-        self.dev = self.dev_gt = self.workspace = self.host = self.origins = self.counts = None
-        self.event = None
-        self.pending = None          # (tokens, counts, B, Tmax, R) of the batch whose copy `event` marks
-
-
-def _grown(t, n, **kw):
-    return t if t is not None and t.numel() >= n else torch.empty(n, **kw)
+from .device_common import DeviceRays, SlotRing, class_grid, flow_grid, occ_size
 
 
 class SubmissionWriter:
@@ -40,23 +26,12 @@ class SubmissionWriter:
         self.pc_range = [float(v) for v in pc_range]
         self.voxel_size = float(voxel_size)
         self.free_id = int(free_id)
-        self.occ_size = [int(round((self.pc_range[3 + k] - self.pc_range[k]) / self.voxel_size)) for k in range(3)]
+        self.occ_size = occ_size(self.pc_range, self.voxel_size)
         self.device = torch.device(device)
-        if int(depth) < 1:
-            raise ValueError("SubmissionWriter: depth must be at least 1")
-        self._rays_host = generate_lidar_rays() if rays is None else rays
-        self._rays = None
-        self._slots = [_Slot() for _ in range(int(depth))]
-        self._next = 0
-        self._tokens = set()
-        self._results = {}
-
-    def _rays_dev(self):
-        if self._rays is None:
-            r = self._rays_host
-            r = torch.from_numpy(np.ascontiguousarray(r, dtype=np.float32)) if isinstance(r, np.ndarray) else r
-            self._rays = r.to(self.device, torch.float32).contiguous()
-        return self._rays
+        # a slot: packed device buffer `dev` (and the ground truth's `dev_gt`, for add_scored), mask `workspace`, pinned `host`
+        # copy, pinned staging of `origins` and `counts`
+        self._ring = SlotRing("SubmissionWriter", depth, self._finish)
+        self._rays_dev = DeviceRays(rays, self.device)
 
     # ---- accumulation ------------------------------------------------------------------------------------------------
     def add(self, tokens, sem_pred, flow_pred, lidar_origins, origin_counts=None):
@@ -76,26 +51,15 @@ class SubmissionWriter:
 
     def _enqueue(self, tokens, sem_pred, flow_pred, lidar_origins, origin_counts, gt=None, score=None):
         from .. import ext
-        tokens = [tokens] if isinstance(tokens, str) else list(tokens)
+        tokens = self._ring.claim("SubmissionWriter.add", tokens)
         B = len(tokens)
-        if len(set(tokens)) != B or any(t in self._tokens for t in tokens):
-            dup = sorted({t for t in tokens if t in self._tokens or tokens.count(t) > 1})
-            raise ValueError(f"SubmissionWriter.add: duplicate token(s) {dup}")
-        grids = (("sem_pred", sem_pred), ("flow_pred", flow_pred)) + \
-            ((("sem_gt", gt[0]), ("flow_gt", gt[1])) if gt is not None else ())
-        for name, t in grids:
-            if not isinstance(t, torch.Tensor) or not t.is_cuda:
-                raise ext.OccAmdError(f"{name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
-        for name, t in grids[::2]:
-            if t.dtype not in (torch.uint8, torch.int64):
-                raise ext.OccAmdError(f"{name} must be uint8 or int64, got {t.dtype}")
-        sem_pred = sem_pred.reshape([B] + self.occ_size).contiguous()
-        flow_pred = flow_pred.reshape([B] + self.occ_size + [2]).contiguous()
+        sem_pred = class_grid("sem_pred", sem_pred, self.occ_size, self.device, B)
+        flow_pred = flow_grid("flow_pred", flow_pred, self.occ_size, self.device, B)
         if gt is not None:
             if score is None or score.free_id != self.free_id:
                 raise ValueError("SubmissionWriter.add_scored: score must be a SubmissionScore of the writer's free_id")
-            sem_gt = gt[0].reshape([B] + self.occ_size).contiguous()
-            flow_gt = gt[1].reshape([B] + self.occ_size + [2]).contiguous()
+            sem_gt = class_grid("sem_gt", gt[0], self.occ_size, self.device, B)
+            flow_gt = flow_grid("flow_gt", gt[1], self.occ_size, self.device, B)
         origins = torch.as_tensor(lidar_origins)
         if origins.dtype not in (torch.float32, torch.float64):
             origins = origins.to(torch.float64)
@@ -112,62 +76,50 @@ class SubmissionWriter:
         rays = self._rays_dev()
         R = rays.shape[0]
         X, Y, Z = self.occ_size
-        slot = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        self._drain(slot)
+        slot = self._ring.take()
         nbytes = ext.submission_rays_bytes(B, Tmax, R)
         dev = self.device
-        slot.dev = _grown(slot.dev, nbytes, dtype=torch.uint8, device=dev)
-        slot.workspace = _grown(slot.workspace, max(ext.submission_rays_workspace_bytes(B, X, Y, Z), 256), dtype=torch.uint8,
-                                device=dev)
-        slot.host = _grown(slot.host, nbytes, dtype=torch.uint8, pin_memory=True)
-        slot.counts = _grown(slot.counts, B, dtype=torch.int32, pin_memory=True)
-        slot.counts[:B] = torch.tensor(counts, dtype=torch.int32)
-        counts_dev = slot.counts[:B].to(dev, non_blocking=True)
+        packed = slot.grown('dev', nbytes, dtype=torch.uint8, device=dev)
+        workspace = slot.grown('workspace', max(ext.submission_rays_workspace_bytes(B, X, Y, Z), 256), dtype=torch.uint8,
+                               device=dev)
+        host = slot.grown('host', nbytes, dtype=torch.uint8, pin_memory=True)
+        counts_host = slot.grown('counts', B, dtype=torch.int32, pin_memory=True)
+        counts_host[:B] = torch.tensor(counts, dtype=torch.int32)
+        counts_dev = counts_host[:B].to(dev, non_blocking=True)
         if not origins.is_cuda:                      # staged through the slot's pinned memory: the upload does not block
-            slot.origins = _grown(slot.origins, B * Tmax * 3, dtype=torch.float64, pin_memory=True)
-            staged = slot.origins[:B * Tmax * 3].view(B, Tmax, 3) if origins.dtype == torch.float64 else \
-                slot.origins.view(torch.float32)[:B * Tmax * 3].view(B, Tmax, 3)
+            staging = slot.grown('origins', B * Tmax * 3, dtype=torch.float64, pin_memory=True)
+            staged = staging[:B * Tmax * 3].view(B, Tmax, 3) if origins.dtype == torch.float64 else \
+                staging.view(torch.float32)[:B * Tmax * 3].view(B, Tmax, 3)
             staged.copy_(origins)
             origins = staged.to(dev, non_blocking=True)
         ext.submission_rays(sem_pred, flow_pred, origins.contiguous(), rays, self.pc_range[:3], self.voxel_size, self.free_id,
-                            origin_counts=counts_dev, out=slot.dev, workspace=slot.workspace)
+                            origin_counts=counts_dev, out=packed, workspace=workspace)
         if gt is not None:                           # same stream: the masks' workspace is free again when this cast starts
-            slot.dev_gt = _grown(slot.dev_gt, nbytes, dtype=torch.uint8, device=dev)
+            packed_gt = slot.grown('dev_gt', nbytes, dtype=torch.uint8, device=dev)
             ext.submission_rays(sem_gt, flow_gt, origins.contiguous(), rays, self.pc_range[:3], self.voxel_size, self.free_id,
-                                origin_counts=counts_dev, out=slot.dev_gt, workspace=slot.workspace)
-            score.update_packed(slot.dev, slot.dev_gt, B, Tmax, R, counts_dev * R)
-        slot.host[:nbytes].copy_(slot.dev[:nbytes], non_blocking=True)
-        slot.event = torch.cuda.Event()
-        slot.event.record()
-        slot.pending = (tokens, counts, B, Tmax, R)
-        self._tokens.update(tokens)
+                                origin_counts=counts_dev, out=packed_gt, workspace=workspace)
+            score.update_packed(packed, packed_gt, B, Tmax, R, counts_dev * R)
+        host[:nbytes].copy_(packed[:nbytes], non_blocking=True)
+        self._ring.record(slot, tokens, (tokens, counts, host, B, Tmax, R))
 
-    def _drain(self, slot):
-        if slot.pending is None:
-            return
+    @staticmethod
+    def _finish(pending):
         from .. import ext
-        tokens, counts, B, Tmax, R = slot.pending
-        slot.event.synchronize()
-        cls, dist, flow = (v.numpy() for v in ext.submission_rays_views(slot.host, B, Tmax, R))
+        tokens, counts, host, B, Tmax, R = pending
+        cls, dist, flow = (v.numpy() for v in ext.submission_rays_views(host, B, Tmax, R))
         for b, (tok, n) in enumerate(zip(tokens, counts)):
-            self._results[tok] = {'pcd_cls': cls[b, :n].reshape(-1).copy(), 'pcd_dist': dist[b, :n].reshape(-1).copy(),
-                                  'pcd_flow': flow[b, :n].reshape(-1, 2).copy()}
-        slot.pending = None
+            yield tok, {'pcd_cls': cls[b, :n].reshape(-1).copy(), 'pcd_dist': dist[b, :n].reshape(-1).copy(),
+                        'pcd_flow': flow[b, :n].reshape(-1, 2).copy()}
 
     # ---- output ------------------------------------------------------------------------------------------------------
     def results(self):
         """Wait for every enqueued batch -> {token: {pcd_cls int8 (T*R), pcd_dist float16 (T*R), pcd_flow float16 (T*R, 2)}}
         in the order the samples were added."""
-        n = len(self._slots)
-        for k in range(n):                           # oldest batch first: the dict keeps insertion order
-            self._drain(self._slots[(self._next + k) % n])
-        return self._results
+        return self._ring.results()
 
     def reset(self):
         """Forget every sample (waiting for the enqueued ones first); the slots' buffers are kept."""
-        self.results()
-        self._tokens, self._results = set(), {}
+        self._ring.reset()
         return self
 
     def write(self, submission_prefix, header=None):

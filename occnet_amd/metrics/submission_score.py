@@ -23,30 +23,25 @@ import warnings
 import numpy as np
 import torch
 
+from .device_common import IntState
+
 QUANTUM = 2.0 ** -28          # m/s per unit of ave_sum
 ROWS = 17
 FLOW_CLASSES = 8
 _FIELDS = ('pcd_cls', 'pcd_dist', 'pcd_flow')
 
 
-class SubmissionScore:
+class SubmissionScore(IntState):
     def __init__(self, free_id=16, device='cuda'):
-        self.free_id = int(free_id)
-        if not 1 <= self.free_id <= 31:
+        if not 1 <= int(free_id) <= 31:
             raise ValueError(f"SubmissionScore: free_id must be 1..31, got {free_id}")
-        self.ncls = self.free_id + 1
-        self.device = torch.device(device)
-        self._workspace = None
-        self.state = torch.zeros(ROWS * self.ncls, dtype=torch.int64, device=self.device)
+        super().__init__(ROWS, free_id, device)
 
     # ---- accumulation ------------------------------------------------------------------------------------------------
     def _accumulate(self, pred, gt, counts, stride, max_chunks=0):
         from .. import ext
-        B = int(counts.numel())
-        need = max(ext.submission_score_workspace_bytes(B), 256)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        ext.submission_score_accumulate(self.state, pred, gt, counts, stride, self.free_id, workspace=self._workspace,
+        workspace = self._grown_workspace(ext.submission_score_workspace_bytes(int(counts.numel())))
+        ext.submission_score_accumulate(self.state, pred, gt, counts, stride, self.free_id, workspace=workspace,
                                         max_chunks=max_chunks)
 
     def _counts(self, counts, B, n):
@@ -126,24 +121,6 @@ class SubmissionScore:
             gt = self._upload([gt_results[t] for t in toks], stride)
             self._accumulate(pred, gt, self._counts(counts, len(toks), stride), stride)
         return len(tokens)
-
-    def merge(self, other):
-        """Add another scorer's state (same classes): integer addition, exact in any order."""
-        if other.state.numel() != self.state.numel():
-            raise ValueError("SubmissionScore.merge: states of different class counts")
-        self.state += other.state.to(self.state.device)
-        return self
-
-    def all_reduce(self):
-        """Sum the state over the ranks of the default process group (no-op without one)."""
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized():
-            dist.all_reduce(self.state, op=dist.ReduceOp.SUM)
-        return self
-
-    def reset(self):
-        self.state.zero_()
-        return self
 
     # ---- scores ------------------------------------------------------------------------------------------------------
     def compute(self):

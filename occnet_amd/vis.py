@@ -17,6 +17,8 @@ import zlib
 import numpy as np
 import torch
 
+from .metrics.device_common import SlotRing, class_grid, occ_size
+
 # this project's own colour table: classes 0..15 of the occupancy benchmark, 16 = free, 17 = the spare id some label sets add
 _CLASS_RGB = (
     (66, 135, 245),    # 0 car
@@ -110,19 +112,6 @@ def save_png(path, rgb):
     return path
 
 
-class _Slot:
-    """One in-flight batch: device images, mask workspace, their pinned host copies, the pinned staging of the cameras."""
-
-    def __init__(self):
-        self.views = self.bev = self.workspace = self.host_views = self.host_bev = self.cams = None
-        self.event = None
-        self.pending = None          # (tokens, views shape, bev shape) of the batch whose copies `event` marks
-
-
-def _grown(t, n, **kw):
-    return t if t is not None and t.numel() >= n else torch.empty(n, **kw)
-
-
 class OccRenderer:
     def __init__(self, pc_range, voxel_size, free_id=16, size=(232, 400), palette=None, far=100., alpha=160, tol=2.,
                  device='cuda', depth=2, bg_rgb=0x101418):
@@ -132,21 +121,18 @@ class OccRenderer:
         self.pc_range = [float(v) for v in pc_range]
         self.voxel_size = float(voxel_size)
         self.free_id = int(free_id)
-        self.occ_size = [int(round((self.pc_range[3 + k] - self.pc_range[k]) / self.voxel_size)) for k in range(3)]
+        self.occ_size = occ_size(self.pc_range, self.voxel_size)
         self.size = (int(size[0]), int(size[1]))
         self.far, self.alpha, self.tol, self.bg_rgb = float(far), int(alpha), float(tol), int(bg_rgb)
         self.device = torch.device(device)
-        if int(depth) < 1:
-            raise ValueError("OccRenderer: depth must be at least 1")
         pal = default_palette() if palette is None else np.asarray(palette)
         if pal.dtype != np.uint8 or pal.shape != (256, 3):
             raise ValueError(f"OccRenderer: palette must be (256, 3) uint8, got {pal.dtype} {pal.shape}")
         self._palette_host = torch.from_numpy(np.ascontiguousarray(pal))
         self._tables = None
-        self._slots = [_Slot() for _ in range(int(depth))]
-        self._next = 0
-        self._tokens = set()
-        self._results = {}
+        # a slot: device images `views` and `bev`, mask `workspace`, their pinned copies `host_views` and `host_bev`, the pinned
+        # staging of the cameras `cams`
+        self._ring = SlotRing("OccRenderer", depth, self._finish)
 
     def _dev_tables(self):
         if self._tables is None:
@@ -154,12 +140,7 @@ class OccRenderer:
         return self._tables
 
     def _grid(self, name, t, B=None):
-        from . import ext
-        if not isinstance(t, torch.Tensor) or not t.is_cuda:
-            raise ext.OccAmdError(f"{name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
-        if t.dtype not in (torch.uint8, torch.int64):
-            raise ext.OccAmdError(f"{name} must be uint8 or int64, got {t.dtype}")
-        return t.reshape([-1 if B is None else B] + self.occ_size).contiguous()
+        return class_grid(name, t, self.occ_size, self.device, B)
 
     # ---- direct calls --------------------------------------------------------------------------------------------------
     def views(self, sem, img_metas, frames=None, sem_gt=None, want=('label', 'depth', 'rgb'), out=None, workspace=None,
@@ -218,12 +199,9 @@ class OccRenderer:
         """Render a batch (views and BEV, rgb only) and start its copy into a pinned host slot: two launch pairs, two
         non-blocking copies, one event.  The call waits only for the slot it is about to reuse (the batch enqueued `depth`
         calls ago).  tokens: one per sample (a single str for one sample)."""
-        tokens = [tokens] if isinstance(tokens, str) else list(tokens)
-        B = len(tokens)
-        if len(set(tokens)) != B or any(t in self._tokens for t in tokens):
-            dup = sorted({t for t in tokens if t in self._tokens or tokens.count(t) > 1})
-            raise ValueError(f"OccRenderer.enqueue: duplicate token(s) {dup}")
         from . import ext
+        tokens = self._ring.claim("OccRenderer.enqueue", tokens)
+        B = len(tokens)
         sem = self._grid('sem', sem, B)
         sem_gt = None if sem_gt is None else self._grid('sem_gt', sem_gt, B)
         cams_host = view_rays(img_metas, self.size)
@@ -232,54 +210,38 @@ class OccRenderer:
         V = cams_host.shape[1]
         h, w = self.size
         X, Y, Z = self.occ_size
-        slot = self._slots[self._next]
-        self._next = (self._next + 1) % len(self._slots)
-        self._drain(slot)
+        slot = self._ring.take()
         dev = self.device
         nv, nb = B * V * h * w * 3, B * X * Y * 3
-        slot.views = _grown(slot.views, nv, dtype=torch.uint8, device=dev)
-        slot.bev = _grown(slot.bev, nb, dtype=torch.uint8, device=dev)
-        slot.workspace = _grown(slot.workspace, max(ext.render_workspace_bytes(B, X, Y, Z, True), 256), dtype=torch.uint8,
-                                device=dev)
-        slot.host_views = _grown(slot.host_views, nv, dtype=torch.uint8, pin_memory=True)
-        slot.host_bev = _grown(slot.host_bev, nb, dtype=torch.uint8, pin_memory=True)
-        slot.cams = _grown(slot.cams, B * V * 12, dtype=torch.float32, pin_memory=True)
-        staged = slot.cams[:B * V * 12].view(B, V, 12)
+        views = slot.grown('views', nv, dtype=torch.uint8, device=dev)
+        bev = slot.grown('bev', nb, dtype=torch.uint8, device=dev)
+        workspace = slot.grown('workspace', max(ext.render_workspace_bytes(B, X, Y, Z, True), 256), dtype=torch.uint8, device=dev)
+        host_views = slot.grown('host_views', nv, dtype=torch.uint8, pin_memory=True)
+        host_bev = slot.grown('host_bev', nb, dtype=torch.uint8, pin_memory=True)
+        staged = slot.grown('cams', B * V * 12, dtype=torch.float32, pin_memory=True)[:B * V * 12].view(B, V, 12)
         staged.copy_(cams_host)
         cams = staged.to(dev, non_blocking=True)                      # through the slot's pinned memory: does not block
-        self.views(sem, None, frames=frames, sem_gt=sem_gt, want=('rgb',), out={'rgb': slot.views}, workspace=slot.workspace,
-                   cams=cams)
-        self.bev(sem, sem_gt=sem_gt, want=('rgb',), out={'rgb': slot.bev}, workspace=slot.workspace)     # same stream
-        slot.host_views[:nv].copy_(slot.views[:nv], non_blocking=True)
-        slot.host_bev[:nb].copy_(slot.bev[:nb], non_blocking=True)
-        slot.event = torch.cuda.Event()
-        slot.event.record()
-        slot.pending = (tokens, (B, V, h, w, 3), (B, X, Y, 3))
-        self._tokens.update(tokens)
+        self.views(sem, None, frames=frames, sem_gt=sem_gt, want=('rgb',), out={'rgb': views}, workspace=workspace, cams=cams)
+        self.bev(sem, sem_gt=sem_gt, want=('rgb',), out={'rgb': bev}, workspace=workspace)               # same stream
+        host_views[:nv].copy_(views[:nv], non_blocking=True)
+        host_bev[:nb].copy_(bev[:nb], non_blocking=True)
+        self._ring.record(slot, tokens, (tokens, host_views[:nv].view(B, V, h, w, 3), host_bev[:nb].view(B, X, Y, 3)))
 
-    def _drain(self, slot):
-        if slot.pending is None:
-            return
-        tokens, vs, bs = slot.pending
-        slot.event.synchronize()
-        nv, nb = int(np.prod(vs)), int(np.prod(bs))
-        views = slot.host_views[:nv].view(vs).numpy()
-        bev = slot.host_bev[:nb].view(bs).numpy()
+    @staticmethod
+    def _finish(pending):
+        tokens, views, bev = pending
+        views, bev = views.numpy(), bev.numpy()
         for b, tok in enumerate(tokens):
-            self._results[tok] = {'views': views[b].copy(), 'bev': bev[b].copy()}
-        slot.pending = None
+            yield tok, {'views': views[b].copy(), 'bev': bev[b].copy()}
 
     def drain(self):
         """Wait for every enqueued batch, oldest first."""
-        n = len(self._slots)
-        for k in range(n):
-            self._drain(self._slots[(self._next + k) % n])
+        self._ring.results()
         return self
 
     def results(self):
         """-> {token: {'views' (V, h, w, 3) uint8, 'bev' (X, Y, 3) uint8 numpy}} in the order the samples were enqueued."""
-        self.drain()
-        return self._results
+        return self._ring.results()
 
 
 # ---- command line -----------------------------------------------------------------------------------------------------------

@@ -1,5 +1,5 @@
 """-m gpu: occupancy rendered on the device (csrc/occ_render.hip through ext.render_views / ext.render_bev, vis.OccRenderer and
-vis_loop.run_test) against the numpy restatement on the reference-pinned caster (tests/render_ref.py), on the small scenes of
+test_loop.run_test) against the numpy restatement on the reference-pinned caster (tests/render_ref.py), on the small scenes of
 tests/render_cases.py.  Every pixel of every output is compared bit for bit: rgb and label / category as bytes, depth as float32
 bits.  What the scenes are there for is asserted on the REFERENCE's output, never on the code under test.
 
@@ -335,7 +335,8 @@ class _StubModel:
 
 
 def test_vis_loop_feeds_the_renderer_and_leaves_the_rest_alone(tmp_path):
-    from occnet_amd import scored_loop, vis, vis_loop
+    from occnet_amd import vis
+    from occnet_amd.test_loop import run_test
     from occnet_amd.metrics import RayMetrics, SubmissionScore, SubmissionWriter
     size, name = (7, 13), '7x5x17'
     shape = rc.GRIDS[name]
@@ -365,11 +366,11 @@ def test_vis_loop_feeds_the_renderer_and_leaves_the_rest_alone(tmp_path):
         return (RayMetrics(pc_range, rc.VOXEL, rays=rays), SubmissionWriter(pc_range, rc.VOXEL, rays=rays), SubmissionScore())
 
     m0, w0, s0 = consumers()
-    assert scored_loop.run_test(_StubModel(outs), samples, metric=m0, writer=w0, score=s0) == 3
+    assert run_test(_StubModel(outs), samples, metric=m0, writer=w0, score=s0) == 3
     m1, w1, s1 = consumers()
     r = vis.OccRenderer(pc_range, rc.VOXEL, free_id=rc.FREE, size=size, far=rc.FAR, tol=rc.TOL, alpha=100, depth=2)
     model = _StubModel(outs)
-    assert vis_loop.run_test(model, iter(samples), metric=m1, writer=w1, score=s1, renderer=r, out_dir=str(tmp_path)) == 3
+    assert run_test(model, iter(samples), metric=m1, writer=w1, score=s1, renderer=r, out_dir=str(tmp_path)) == 3
     assert model.k == 3                                                       # the model ran once per sample
     assert torch.equal(m1.state, m0.state) and torch.equal(s1.state, s0.state) and int(m0.state.sum()) > 0
     a, b = w1.results(), w0.results()
@@ -384,10 +385,10 @@ def test_vis_loop_feeds_the_renderer_and_leaves_the_rest_alone(tmp_path):
         assert np.array_equal(res[tok]['views'], want_v) and np.array_equal(res[tok]['bev'], want_b), tok
         with open(tmp_path / f'{tok}.png', 'rb') as fh:
             assert fh.read(8) == b'\x89PNG\r\n\x1a\n'
-    # every second sample, nothing but the renderer; without a renderer it is scored_loop.run_test
+    # every second sample, nothing but the renderer; all consumers but the renderer: the same as run_test without a renderer
     r2 = vis.OccRenderer(pc_range, rc.VOXEL, free_id=rc.FREE, size=size, far=rc.FAR, tol=rc.TOL, alpha=100, depth=1)
-    assert vis_loop.run_test(_StubModel(outs), samples, renderer=r2, every=2) == 3
+    assert run_test(_StubModel(outs), samples, renderer=r2, every=2) == 3
     assert list(r2.results()) == ['s0', 's2'] and np.array_equal(r2.results()['s2']['views'], res['s2']['views'])
     m2, w2, s2 = consumers()
-    assert vis_loop.run_test(_StubModel(outs), samples, metric=m2, writer=w2, score=s2) == 3
+    assert run_test(_StubModel(outs), samples, metric=m2, writer=w2, score=s2) == 3
     assert torch.equal(m2.state, m0.state) and torch.equal(s2.state, s0.state)

@@ -1,5 +1,5 @@
 """-m gpu: the server-side scorer on the device (csrc/submission_score.hip through ext.submission_score_accumulate,
-metrics.SubmissionScore, SubmissionWriter.add_scored, io.score_submission and scored_loop.run_test) against the numpy restatement
+metrics.SubmissionScore, SubmissionWriter.add_scored, io.score_submission and test_loop.run_test) against the numpy restatement
 of the reference's tools/ray_iou/metric.py (tests/submission_score_ref.py) and the numbers metric.py itself left in
 tests/golden/ray_metrics.npz.  Every case compares all 17 * ncls state words for equality."""
 import os
@@ -317,7 +317,7 @@ class _StubModel:
 @pytest.mark.parametrize('dtypes', [(np.uint8, np.int64), (np.int64, np.uint8)])
 def test_add_scored_end_to_end(dtypes, tmp_path):
     from occnet_amd.metrics import SubmissionScore, SubmissionWriter
-    from occnet_amd.scored_loop import run_test
+    from occnet_amd.test_loop import run_test
     rng = np.random.default_rng(7)
     rays = rng.normal(size=(130, 3))
     rays = torch.from_numpy((rays / np.linalg.norm(rays, axis=1, keepdims=True)).astype(np.float32))

@@ -64,6 +64,33 @@ def test_byte_queries():
     assert lib.occ_submission_rays_workspace_bytes(2, 200, 200, 16) == lib.occ_ray_metrics_workspace_bytes(1, 200, 200, 16)
 
 
+@pytest.mark.parametrize('B,X,Y,Z', [(1, 6, 5, 3), (3, 7, 9, 20), (1, 200, 200, 16), (2, 400, 400, 32), (1, 200, 200, 33),
+                                     (0, 200, 200, 16)])
+def test_workspace_queries_agree(B, X, Y, Z):
+    """One formula behind the three queries: `grids` grids of B * X * Y mask words (2 bytes up to Z = 16, 4 up to 32), rounded up
+    to 256 bytes; 0 where there are no masks.  The evaluator holds two grids, the writer one, the renderer one or two."""
+    lib = _lib64()
+    lib.occ_ray_metrics_workspace_bytes.restype = ctypes.c_int64
+    lib.occ_render_workspace_bytes.restype = ctypes.c_int64
+
+    def want(batch, grids):
+        if batch <= 0 or Z > 32:
+            return 0
+        return (grids * batch * X * Y * (2 if Z <= 16 else 4) + 255) // 256 * 256
+
+    two = lib.occ_ray_metrics_workspace_bytes(B, X, Y, Z)
+    assert two == want(B, 2)
+    assert lib.occ_render_workspace_bytes(B, X, Y, Z, 1) == two
+    assert lib.occ_submission_rays_workspace_bytes(2 * B, X, Y, Z) == two
+    one = lib.occ_render_workspace_bytes(B, X, Y, Z, 0)
+    assert one == want(B, 1) == lib.occ_submission_rays_workspace_bytes(B, X, Y, Z)
+    raw = B * X * Y * (2 if Z <= 16 else 4)                       # one grid's bytes before the round-up
+    if raw % 256 == 0 or one == 0:
+        assert two == 2 * one
+    else:                                                         # the round-up bites: two grids are rounded once, not twice
+        assert two == (2 * raw + 255) // 256 * 256 and two <= 2 * one
+
+
 def test_argument_checks_without_gpu():
     lib = _lib64()
     null = ctypes.c_void_p(0)
