@@ -31,16 +31,51 @@ def declared_symbols(header=HEADER_PATH):
     return sorted(set(re.findall(r"\b(occ_[a-z0-9_]+)\s*\(", src)))
 
 
-# the size queries of the header that return int64_t (ctypes assumes int)
-_INT64_RESULTS = (
-    "occ_ms_deform_attn_backward_workspace_bytes", "occ_sca_fused_backward_workspace_bytes",
-    "occ_tsa_fused_backward_workspace_bytes", "occ_conv3d_heads_pack_bytes",
-    "occ_linear_chain_packed_bytes", "occ_linear_wgrad_workspace_bytes", "occ_conv3d_wgrad_workspace_bytes",
-    "occ_bias_act_bwd_partial_floats", "occ_dropout_add_ln_bwd_partial_floats", "occ_conv1x1_wgrad_workspace_bytes",
-    "occ_conv3x3_wgrad_workspace_bytes", "occ_bn3d_relu_train_partial_floats",
-    "occ_ray_metrics_state_words", "occ_ray_metrics_workspace_bytes", "occ_heads_loss_workspace_bytes",
-    "occ_submission_rays_bytes", "occ_submission_rays_workspace_bytes",
-    "occ_submission_score_state_words", "occ_submission_score_workspace_bytes", "occ_render_workspace_bytes")
+# every scalar type of the header; anything with a '*' is a pointer, any other type is refused (prototypes)
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "unsigned": ctypes.c_uint,
+            "uint32_t": ctypes.c_uint32, "float": ctypes.c_float}
+
+
+class DevicePtr(ctypes.c_void_p):
+    """argtypes entry of every pointer parameter: whatever c_void_p takes (None, an int, a c_void_p, a ctypes array,
+    byref(...)), and a torch.Tensor, passed as its data_ptr()."""
+
+    @classmethod
+    def from_param(cls, v):
+        if isinstance(v, torch.Tensor):
+            return ctypes.c_void_p(v.data_ptr())
+        return ctypes.c_void_p.from_param(v)
+
+
+def prototypes(src=None):
+    """{name: (restype, [(ctype, parameter name), ...])} of every function the header text `src` declares (None: the public
+    header).  The header is the single source of the binding's types: a type this table does not know raises OccAmdError
+    naming the prototype, so that a new one gets a deliberate mapping."""
+    if src is None:
+        with open(HEADER_PATH) as f:
+            src = f.read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+
+    def ctype(name, text, what):
+        words = [w for w in text.replace("*", " * ").split() if w != "const"]
+        if "*" in words:
+            return ctypes.c_char_p if what == "return value" and words == ["char", "*"] else DevicePtr
+        if " ".join(words) not in _SCALARS:
+            raise OccAmdError(f"{name}: no ctypes mapping for the type {text.strip()!r} of its {what} (see _lib._SCALARS)")
+        return _SCALARS[" ".join(words)]
+
+    out = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(occ_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        args = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            m = re.fullmatch(r"\s*(.*?[\s*])(\w+)\s*", p, flags=re.S)
+            if m is None:
+                raise OccAmdError(f"{name}: cannot read the parameter {p.strip()!r}")
+            args.append((ctype(name, m.group(1), f"parameter {m.group(2)!r}"), m.group(2)))
+        out[name] = (ctype(name, ret, "return value"), args)
+    return out
+
 
 _lib = None
 ABI = 3     # include/occnet_amd.h: bumped whenever a signature changes (2: range scales of the fp16 value rows; 3: their weight terms in device memory)
@@ -54,10 +89,9 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -m occnet_amd.build` "
                 "(the MI355X path has no CPU fallback)")
         _lib = ctypes.CDLL(LIB_PATH)
-        _lib.occ_last_error.restype = ctypes.c_char_p
-        _lib.occ_abi_version.restype = ctypes.c_int
-        for name in _INT64_RESULTS:
-            getattr(_lib, name).restype = ctypes.c_int64
+        for name, (restype, args) in prototypes().items():
+            fn = getattr(_lib, name)
+            fn.restype, fn.argtypes = restype, [t for t, _ in args]
         if _lib.occ_abi_version() != ABI:
             got, _lib = _lib.occ_abi_version(), None
             raise OccAmdError(f"{LIB_PATH} has C ABI {got}, this package binds ABI {ABI}: rebuild it "

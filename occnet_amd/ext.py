@@ -16,7 +16,8 @@ import torch
 
 from . import _lib
 from .derived import DerivedCache
-from ._lib import OccAmdError, OccAmdUnsupported, f32, i32, i64, ptr, stream_ptr
+from ._lib import OccAmdError, OccAmdUnsupported, f32, i32
+from ._lib import i64, ptr, stream_ptr  # noqa: F401  (not used here any more; callers import them from this module)
 
 
 _TIMING = None   # None, or {kernel name: [(start_event, end_event), ...]} (bench.py roofline leg)
@@ -39,12 +40,17 @@ def kernel_timing_only(names):
     _TIMING_ONLY = None if names is None else set(names)
 
 
+def _timing_on(name):
+    """True when launches booked under `name` are being timed (None: a launch that is not instrumented)."""
+    return name is not None and _TIMING is not None and (_TIMING_ONLY is None or name in _TIMING_ONLY)
+
+
 class _timed:
     def __init__(self, name):
         self.name = name
 
     def __enter__(self):
-        self.on = self.name is not None and _TIMING is not None and (_TIMING_ONLY is None or self.name in _TIMING_ONLY)
+        self.on = _timing_on(self.name)
         if self.on:
             self.ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             self.ev[0].record()
@@ -58,8 +64,20 @@ class _timed:
 
 def _note_flops(name, flops):
     """bench.py's backbone roofline: the FLOPs of an instrumented launch, next to its event pair."""
-    if name is not None and _TIMING is not None and (_TIMING_ONLY is None or name in _TIMING_ONLY):
+    if _timing_on(name):
         _TIMING.setdefault(name + '_flops', []).append(float(flops))
+
+
+def _launch(fn, dev, what, *args, timing=None, flops=None):
+    """The one way into a kernel launcher of the C ABI: fn(*args, stream) on `dev` and its current stream, timed under the
+    kernel_timing name `timing` (None: not instrumented) with `flops` booked next to the event pair (whether or not the call
+    succeeded), then the return code checked under the name `what`.  Tensors go in as they are (_lib.DevicePtr); a wrong
+    argument count or kind raises on the host, from the argtypes the binding read out of the header."""
+    with torch.cuda.device(dev), _timed(timing):
+        rc = fn(*args, torch.cuda.current_stream(dev).cuda_stream)
+    if flops is not None:
+        _note_flops(timing, flops)
+    _lib.check(rc, what)
 
 
 def kernel_times_ms(record):
@@ -105,12 +123,8 @@ def ms_deform_attn_forward(value, value_spatial_shapes, value_level_start_index,
             tuple(value_spatial_shapes.shape) != (L, 2) or value_level_start_index.numel() != L):
         raise OccAmdError("ms_deform_attn_forward: inconsistent shapes")
     out = torch.empty((B, Lq, M * D), dtype=torch.float32, device=value.device)
-    with torch.cuda.device(value.device):
-        rc = _lib.lib().occ_ms_deform_attn_forward_f32(
-            ptr(value), ptr(value_spatial_shapes), ptr(value_level_start_index),
-            ptr(sampling_locations), ptr(attention_weights), ptr(out), i32(B), i32(S), i32(M),
-            i32(D), i32(L), i32(Lq), i32(P), i32(int(im2col_step)), stream_ptr(value.device))
-    _lib.check(rc, "ms_deform_attn_forward")
+    _launch(_lib.lib().occ_ms_deform_attn_forward_f32, value.device, "ms_deform_attn_forward", value, value_spatial_shapes,
+            value_level_start_index, sampling_locations, attention_weights, out, B, S, M, D, L, Lq, P, int(im2col_step))
     return out
 
 
@@ -134,16 +148,11 @@ def ms_deform_attn_backward(value, value_spatial_shapes, value_level_start_index
     lib = _lib.lib()
     # scratch of the atomic-free grad_value path from torch's caching allocator (not hipMallocAsync behind its back);
     # freed back to the pool when this call returns — stream-ordered, the kernels are already enqueued
-    need = int(lib.occ_ms_deform_attn_backward_workspace_bytes(i32(B), i32(S), i32(M), i32(D), i32(L), i32(Lq),
-                                                               i32(P)))
+    need = lib.occ_ms_deform_attn_backward_workspace_bytes(B, S, M, D, L, Lq, P)
     ws = torch.empty(need, dtype=torch.uint8, device=value.device) if need > 0 else None
-    with torch.cuda.device(value.device):
-        rc = lib.occ_ms_deform_attn_backward_ws_f32(
-            ptr(value), ptr(value_spatial_shapes), ptr(value_level_start_index),
-            ptr(sampling_locations), ptr(attention_weights), ptr(grad_output), ptr(grad_value),
-            ptr(grad_sampling_loc), ptr(grad_attn_weight), i32(B), i32(S), i32(M), i32(D), i32(L),
-            i32(Lq), i32(P), i32(int(im2col_step)), ptr(ws), i64(need), stream_ptr(value.device))
-    _lib.check(rc, "ms_deform_attn_backward")
+    _launch(lib.occ_ms_deform_attn_backward_ws_f32, value.device, "ms_deform_attn_backward", value, value_spatial_shapes,
+            value_level_start_index, sampling_locations, attention_weights, grad_output, grad_value, grad_sampling_loc,
+            grad_attn_weight, B, S, M, D, L, Lq, P, int(im2col_step), ws, need)
 
 
 def point_sampling(ref_3d, lidar2img, ego2lidar, pc_range, img_h, img_w):
@@ -160,11 +169,8 @@ def point_sampling(ref_3d, lidar2img, ego2lidar, pc_range, img_h, img_w):
     mask = torch.empty((NC, B, Nq, Z), dtype=torch.uint8, device=dev)
     vis = torch.empty((B, Nq), dtype=torch.int32, device=dev)
     pcr = (f32 * 6)(*[float(v) for v in pc_range])
-    with torch.cuda.device(dev):
-        rc = _lib.lib().occ_point_sampling_f32(
-            ptr(ref_3d), ptr(lidar2img), ptr(ego2lidar), pcr, f32(float(img_h)), f32(float(img_w)),
-            ptr(ref_cam), ptr(mask), ptr(vis), i32(B), i32(NC), i32(Nq), i32(Z), stream_ptr(dev))
-    _lib.check(rc, "point_sampling")
+    _launch(_lib.lib().occ_point_sampling_f32, dev, "point_sampling", ref_3d, lidar2img, ego2lidar, pcr, float(img_h),
+            float(img_w), ref_cam, mask, vis, B, NC, Nq, Z)
     return ref_cam, mask.view(torch.bool), vis
 
 
@@ -316,20 +322,15 @@ def sca_fused_forward(value, spatial_shapes, level_start_index, offs, logits, re
     slots = torch.empty((B, Nq, M * D), dtype=torch.float32, device=value.device)
     fn = (_lib.lib().occ_sca_fused_forward_q16v if q16 else _lib.lib().occ_sca_fused_forward_f16v if half
           else _lib.lib().occ_sca_fused_forward_f32)
-    tail = (ptr(value_scale), stream_ptr(value.device)) if half else (stream_ptr(value.device),)
-    with torch.cuda.device(value.device), _timed(_timing):
-        rc = fn(ptr(value), ptr(spatial_shapes), ptr(level_start_index), ptr(offs), i64(offs.stride(1)), ptr(logits),
-                i64(logits.stride(1)), ptr(ref_cam), ptr(vis_bits), ptr(order), ptr(slots), ptr(stats), i32(B),
-                i32(NC), i32(S), i32(M), i32(D), i32(L), i32(P), i32(Z), i32(Nq), *tail)
-    _lib.check(rc, "sca_fused_forward")
+    _launch(fn, value.device, "sca_fused_forward", value, spatial_shapes, level_start_index, offs, offs.stride(1), logits,
+            logits.stride(1), ref_cam, vis_bits, order, slots, stats, B, NC, S, M, D, L, P, Z, Nq,
+            *((value_scale,) if half else ()), timing=_timing)
     return slots
 
 
 def sca_fused_backward_workspace_bytes(B, NC, S, M, D, L, P, Nq):
     """Bytes of scratch sca_fused_backward takes for these shapes (0: no backward kernel for them)."""
-    lib = _lib.lib()
-    return int(lib.occ_sca_fused_backward_workspace_bytes(i32(B), i32(NC), i32(S), i32(M), i32(D), i32(L), i32(P),
-                                                          i32(Nq)))
+    return _lib.lib().occ_sca_fused_backward_workspace_bytes(B, NC, S, M, D, L, P, Nq)
 
 
 def sca_fused_backward(value, spatial_shapes, level_start_index, offs, logits, ref_cam, vis_bits, grad_slots,
@@ -370,13 +371,10 @@ def sca_fused_backward(value, spatial_shapes, level_start_index, offs, logits, r
     grad_value = torch.zeros_like(value)
     grad_offs = torch.empty((B, Nq, M * L * P * 2), dtype=torch.float32, device=value.device)
     grad_logits = torch.empty((B, Nq, M * L * P), dtype=torch.float32, device=value.device)
-    with torch.cuda.device(value.device), _timed('sca_fused_backward'):
-        rc = _lib.lib().occ_sca_fused_backward_f32(
-            ptr(value), ptr(spatial_shapes), ptr(level_start_index), ptr(offs), i64(offs.stride(1)), ptr(logits),
-            i64(logits.stride(1)), ptr(ref_cam), ptr(vis_bits), ptr(grad_slots), ptr(grad_value), ptr(grad_offs),
-            i64(grad_offs.stride(1)), ptr(grad_logits), i64(grad_logits.stride(1)), i32(B), i32(NC), i32(S), i32(M),
-            i32(D), i32(L), i32(P), i32(Z), i32(Nq), ptr(ws), i64(need), stream_ptr(value.device))
-    _lib.check(rc, "sca_fused_backward")
+    _launch(_lib.lib().occ_sca_fused_backward_f32, value.device, "sca_fused_backward", value, spatial_shapes,
+            level_start_index, offs, offs.stride(1), logits, logits.stride(1), ref_cam, vis_bits, grad_slots, grad_value,
+            grad_offs, grad_offs.stride(1), grad_logits, grad_logits.stride(1), B, NC, S, M, D, L, P, Z, Nq, ws, need,
+            timing='sca_fused_backward')
     return grad_value, grad_offs, grad_logits
 
 
@@ -493,25 +491,19 @@ def _tsa_fused_forward(value, offs, logits, ref_2d, bev_h, bev_w, num_heads, num
                                   and order.device == value.device and order.is_contiguous()):
         raise OccAmdError("tsa_fused_forward: order must be a contiguous int32 (Nq) tensor on value's device")
     out = torch.empty((B, Nq, M * D), dtype=torch.float32, device=value.device)
-    with torch.cuda.device(value.device), _timed(timing):
-        if q16:
-            rc = _lib.lib().occ_tsa_fused_forward_q16v(
-                ptr(value), i64(stride), i32(Nr), ptr(offs), i64(offs.stride(1)), ptr(logits),
-                i64(logits.stride(1)), ptr(ref_2d), ptr(order), ptr(out), i32(B), i32(Nq), i32(bev_h),
-                i32(bev_w), i32(M), i32(D), i32(P), ptr(value_scale), stream_ptr(value.device))
-        else:
-            rc = _lib.lib().occ_tsa_fused_forward_f32(
-                ptr(value), i64(stride), ptr(offs), i64(offs.stride(1)), ptr(logits),
-                i64(logits.stride(1)), ptr(ref_2d), ptr(order), ptr(out), i32(B), i32(Nq), i32(bev_h),
-                i32(bev_w), i32(M), i32(D), i32(P), stream_ptr(value.device))
-    _lib.check(rc, "tsa_fused_forward")
+    if q16:
+        _launch(_lib.lib().occ_tsa_fused_forward_q16v, value.device, "tsa_fused_forward", value, stride, Nr, offs,
+                offs.stride(1), logits, logits.stride(1), ref_2d, order, out, B, Nq, bev_h, bev_w, M, D, P, value_scale,
+                timing=timing)
+    else:
+        _launch(_lib.lib().occ_tsa_fused_forward_f32, value.device, "tsa_fused_forward", value, stride, offs, offs.stride(1),
+                logits, logits.stride(1), ref_2d, order, out, B, Nq, bev_h, bev_w, M, D, P, timing=timing)
     return out
 
 
 def tsa_fused_backward_workspace_bytes(B, Nq, bev_h, bev_w, M, D, P):
     """Bytes of scratch tsa_fused_backward takes for these shapes (0: no backward kernel for them)."""
-    return int(_lib.lib().occ_tsa_fused_backward_workspace_bytes(i32(B), i32(Nq), i32(bev_h), i32(bev_w), i32(M), i32(D),
-                                                                 i32(P)))
+    return _lib.lib().occ_tsa_fused_backward_workspace_bytes(B, Nq, bev_h, bev_w, M, D, P)
 
 
 _TSA_LEVEL_TENSORS = {}
@@ -581,13 +573,9 @@ def tsa_fused_backward(value, offs, logits, ref_2d, grad_out, bev_h, bev_w, num_
     gv2 = torch.zeros((B * 2, Nq, M, D), dtype=torch.float32, device=dev) if want_value else None
     grad_offs = torch.empty((B, Nq, M * 2 * P * 2), dtype=torch.float32, device=dev) if want_query else None
     grad_logits = torch.empty((B, Nq, M * 2 * P), dtype=torch.float32, device=dev) if want_query else None
-    with torch.cuda.device(dev), _timed('tsa_fused_backward'):
-        rc = _lib.lib().occ_tsa_fused_backward_f32(
-            ptr(src), i64(stride), ptr(offs), i64(offs.stride(1)), ptr(logits), i64(logits.stride(1)), ptr(ref_2d),
-            ptr(grad_out), ptr(shapes), ptr(lstart), ptr(gv2), ptr(grad_offs), i64(M * 2 * P * 2), ptr(grad_logits),
-            i64(M * 2 * P), i32(B), i32(Nq), i32(bev_h), i32(bev_w), i32(M), i32(D), i32(P), ptr(ws), i64(need),
-            stream_ptr(dev))
-    _lib.check(rc, "tsa_fused_backward")
+    _launch(_lib.lib().occ_tsa_fused_backward_f32, dev, "tsa_fused_backward", src, stride, offs, offs.stride(1), logits,
+            logits.stride(1), ref_2d, grad_out, shapes, lstart, gv2, grad_offs, M * 2 * P * 2, grad_logits, M * 2 * P, B, Nq,
+            bev_h, bev_w, M, D, P, ws, need, timing='tsa_fused_backward')
     grad_value = None
     if want_value:
         grad_value = (gv2.view(B, 2, Nq, M, D).sum(1) if shared_queue else gv2).view(value.shape)
@@ -634,7 +622,7 @@ class TSAFusedFunction(torch.autograd.Function):
 
 def conv3d_channel_block(cin):
     """Input channels contracted per LDS phase by the MFMA Conv3d kernel (0 = unsupported)."""
-    return int(_lib.lib().occ_conv3d_channel_block(i32(int(cin))))
+    return int(_lib.lib().occ_conv3d_channel_block(int(cin)))
 
 
 CONV3D_PRECISION = os.environ.get("OCC_CONV3D_PRECISION", "bf16x3")   # 'bf16x3' (default) or 'f32'
@@ -654,16 +642,10 @@ def conv3d_pack_weight(weight, precision=None):
     if precision == 'bf16x3' and (cin % 16 == 0 or (cin == 8 and cout == 32)):
         n16 = CONV3D_C8_PACKED_INT16 if cin == 8 else weight.numel() * 2
         packed = torch.empty(n16, dtype=torch.int16, device=weight.device)
-        with torch.cuda.device(weight.device):
-            rc = _lib.lib().occ_conv3d_pack_weight_bf16x3(ptr(weight), ptr(packed), i32(cin), i32(cout),
-                                                          stream_ptr(weight.device))
-        _lib.check(rc, "conv3d_pack_weight")
+        _launch(_lib.lib().occ_conv3d_pack_weight_bf16x3, weight.device, "conv3d_pack_weight", weight, packed, cin, cout)
         return packed
     packed = torch.empty(weight.numel(), dtype=torch.float32, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = _lib.lib().occ_conv3d_pack_weight_f32(ptr(weight), ptr(packed), i32(cin), i32(cout),
-                                                   stream_ptr(weight.device))
-    _lib.check(rc, "conv3d_pack_weight")
+    _launch(_lib.lib().occ_conv3d_pack_weight_f32, weight.device, "conv3d_pack_weight", weight, packed, cin, cout)
     return packed
 
 
@@ -692,11 +674,8 @@ def conv3d_bn_relu(x, w_packed, scale, shift, Z, Y, X, cin, cout, in_layout, out
         out = torch.empty((B, Y, X, Z, cout), dtype=torch.float32, device=x.device)
         sy, sx = X * Z * cout, Z * cout
     fn = _lib.lib().occ_conv3d_bn_relu_bf16x3_f32 if x3 else _lib.lib().occ_conv3d_bn_relu_f32
-    with torch.cuda.device(x.device), _timed('conv3d_bn_relu'):
-        rc = fn(ptr(x), ptr(w_packed), ptr(scale), ptr(shift), ptr(out), i32(B), i32(Z), i32(Y), i32(X),
-                i32(cin), i32(cout), i32(int(in_layout)), i64(Y * X * Z * cout), i64(sy), i64(sx),
-                i32(1 if relu else 0), stream_ptr(x.device))
-    _lib.check(rc, "conv3d_bn_relu")
+    _launch(fn, x.device, "conv3d_bn_relu", x, w_packed, scale, shift, out, B, Z, Y, X, cin, cout, int(in_layout),
+            Y * X * Z * cout, sy, sx, 1 if relu else 0, timing='conv3d_bn_relu')
     return out
 
 
@@ -713,10 +692,7 @@ def conv3d_heads_pack(w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow,
         raise OccAmdError("conv3d_heads_pack: inconsistent weight shapes")
     lib = _lib.lib()
     packed = torch.empty(int(lib.occ_conv3d_heads_pack_bytes()), dtype=torch.uint8, device=w1_occ.device)
-    with torch.cuda.device(w1_occ.device):
-        rc = lib.occ_conv3d_heads_pack(*[ptr(t) for t in ts], ptr(packed), i32(C), i32(hidden), i32(ncls),
-                                       stream_ptr(w1_occ.device))
-    _lib.check(rc, "conv3d_heads_pack")
+    _launch(lib.occ_conv3d_heads_pack, w1_occ.device, "conv3d_heads_pack", *ts, packed, C, hidden, ncls)
     packed._occ_heads_meta = (int(C), int(hidden), int(ncls))     # the fragment layout bakes these in: checked at use
     return packed
 
@@ -740,11 +716,8 @@ def conv3d_heads_decode(x, w_packed, scale, shift, heads_packed, Z, Y, X, num_cl
     occ = torch.empty((B, X, Y, Z, num_classes), dtype=torch.float32, device=x.device)
     flow = torch.empty((B, X, Y, Z, 2), dtype=torch.float32, device=x.device)
     cls = torch.empty((B, X, Y, Z), dtype=torch.int64, device=x.device)
-    with torch.cuda.device(x.device), _timed('conv3d_heads'):
-        rc = _lib.lib().occ_conv3d_heads_decode_bf16x3_f32(
-            ptr(x), ptr(w_packed), ptr(scale), ptr(shift), ptr(heads_packed), ptr(occ), ptr(flow), ptr(cls), i32(B),
-            i32(Z), i32(Y), i32(X), i32(cin), i32(num_classes), stream_ptr(x.device))
-    _lib.check(rc, "conv3d_heads_decode")
+    _launch(_lib.lib().occ_conv3d_heads_decode_bf16x3_f32, x.device, "conv3d_heads_decode", x, w_packed, scale, shift,
+            heads_packed, occ, flow, cls, B, Z, Y, X, cin, num_classes, timing='conv3d_heads')
     return occ, flow, cls
 
 
@@ -770,12 +743,9 @@ def occ_heads(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, b
     occ = torch.empty(feat.shape[:-1] + (ncls,), dtype=torch.float32, device=feat.device)
     flow = torch.empty(feat.shape[:-1] + (2,), dtype=torch.float32, device=feat.device)
     cls = torch.empty(feat.shape[:-1], dtype=torch.int64, device=feat.device) if decode else None
-    with torch.cuda.device(feat.device), _timed('occ_heads'):
-        rc = _lib.lib().occ_occ_heads_decode_f32(
-            ptr(feat), ptr(w1_occ), ptr(b1_occ), ptr(w2_occ), ptr(b2_occ), ptr(w1_flow), ptr(b1_flow),
-            ptr(w2_flow), ptr(b2_flow), ptr(occ), ptr(flow), ptr(cls), i64(n_rows), i32(C), i32(hidden),
-            i32(ncls), i32(1 if (precision or HEADS_PRECISION) == "f32" else 0), stream_ptr(feat.device))
-    _lib.check(rc, "occ_heads")
+    _launch(_lib.lib().occ_occ_heads_decode_f32, feat.device, "occ_heads", feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow,
+            b1_flow, w2_flow, b2_flow, occ, flow, cls, n_rows, C, hidden, ncls,
+            1 if (precision or HEADS_PRECISION) == "f32" else 0, timing='occ_heads')
     return (occ, flow, cls) if decode else (occ, flow)
 
 
@@ -814,10 +784,7 @@ def linear_pack_weight_bf16x3(weight):
         _need_cuda_f32("weight", weight)
         N, K = weight.shape
         packed = torch.empty((N + 31) // 32 * 32 * K * 2, dtype=torch.int16, device=weight.device)
-        with torch.cuda.device(weight.device):
-            rc = _lib.lib().occ_linear_pack_weight_bf16x3(ptr(weight), ptr(packed), i32(N), i32(K),
-                                                          stream_ptr(weight.device))
-        _lib.check(rc, "linear_pack_weight_bf16x3")
+        _launch(_lib.lib().occ_linear_pack_weight_bf16x3, weight.device, "linear_pack_weight_bf16x3", weight, packed, N, K)
         return packed
     return _PACKED_W.get((weight,), build)
 
@@ -867,11 +834,8 @@ def value_range_scale(a_list, row_l1, bias_max):
     out, work = buf[:2 * P + 1], buf[2 * P + 1:]
     arr64 = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])
     a_ptrs = (ctypes.c_void_p * S)(*[a.data_ptr() for a in a_list])
-    with torch.cuda.device(dev), _timed('value_range'):
-        rc = _lib.lib().occ_value_range_scale_bf16(
-            i32(S), a_ptrs, arr64([a.stride(0) for a in a_list]), arr64([a.shape[0] for a in a_list]), i32(K), i32(P),
-            ptr(r), ptr(b), ptr(out), ptr(work), stream_ptr(dev))
-    _lib.check(rc, "value_range_scale")
+    _launch(_lib.lib().occ_value_range_scale_bf16, dev, "value_range_scale", S, a_ptrs, arr64([a.stride(0) for a in a_list]),
+            arr64([a.shape[0] for a in a_list]), K, P, r, b, out, work, timing='value_range')
     return out
 
 
@@ -921,9 +885,7 @@ def _range_scale_from_amax(amax8, row_l1, bias_max, timing):
     r, b = _range_terms_dev(row_l1, bias_max, dev)
     P = r.numel()
     out = torch.empty(2 * P + 1, dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed(timing):
-        rc = _lib.lib().occ_value_range_scale_from_amax(ptr(amax8), i32(P), ptr(r), ptr(b), ptr(out), stream_ptr(dev))
-    _lib.check(rc, "value_range_scale_from_amax")
+    _launch(_lib.lib().occ_value_range_scale_from_amax, dev, "value_range_scale_from_amax", amax8, P, r, b, out, timing=timing)
     return out
 
 
@@ -949,9 +911,7 @@ def sca_rows_encode_q16(v, scale=None):
     out = torch.empty((BN, S + (S & 1), C), dtype=torch.int16, device=v.device)
     if S & 1:                                    # the pad pixel (second slot of the last pair, every head): never sampled, kept defined
         out.view(BN, (S + 1) // 2, C // 32, 2, 32)[:, -1, :, 1, :].zero_()
-    with torch.cuda.device(v.device):
-        rc = _lib.lib().occ_sca_rows_encode_q16(ptr(v), ptr(out), ptr(scale), i64(BN), i32(S), i32(C), stream_ptr(v.device))
-    _lib.check(rc, "sca_rows_encode_q16")
+    _launch(_lib.lib().occ_sca_rows_encode_q16, v.device, "sca_rows_encode_q16", v, out, scale, BN, S, C)
     return out
 
 
@@ -1054,12 +1014,8 @@ def linear_q16rows(a, weight, bias, scale, groups, act=None, residual=None, ln=N
     out = torch.empty((groups, S + (S & 1), N), dtype=torch.int16, device=a.device)
     if S & 1:                                    # the pad pixel of every map: never sampled, kept defined (sca_rows_encode_q16)
         out.view(groups, (S + 1) // 2, N // 32, 2, 32)[:, -1, :, 1, :].zero_()
-    if _TIMING is not None and (_TIMING_ONLY is None or 'linear' in _TIMING_ONLY):
-        _TIMING.setdefault('linear_flops', []).append(2.0 * M * N * K)
-    with torch.cuda.device(a.device), _timed('linear'):
-        rc = _lib.lib().occ_linear_bf16x3_q16rows(ptr(a_), i64(lda), i32(K), ptr(wp), ptr(bias), ptr(scale), ptr(out),
-                                                  i32(M), i32(N), i32(groups), stream_ptr(a.device))
-    _lib.check(rc, "linear_q16rows")
+    _launch(_lib.lib().occ_linear_bf16x3_q16rows, a.device, "linear_q16rows", a_, lda, K, wp, bias, scale, out, M, N, groups,
+            timing='linear', flops=2.0 * M * N * K)
     return out
 
 
@@ -1111,13 +1067,9 @@ def value_proj_bf16(a_list, weight, group_bias, out, rows_per_group, out_group_r
     a_ptrs = (ctypes.c_void_p * S)(*[a.data_ptr() for a in a_list])
     fn = (_lib.lib().occ_value_proj_bf16_q16pairs if out_q16 else _lib.lib().occ_value_proj_bf16_f16pairs if out_half
           else _lib.lib().occ_value_proj_bf16_f32)
-    tail = (ptr(out_scale), stream_ptr(out.device)) if out_half else (stream_ptr(out.device),)
-    with torch.cuda.device(out.device), _timed('value_proj'):
-        rc = fn(
-            i32(S), a_ptrs, arr64([a.stride(0) for a in a_list]), arr64([a.shape[0] for a in a_list]),
-            arr64(rows_per_group), arr64(out_row0), gb_ptrs, i32(G), ptr(packed), ptr(out), i64(out.stride(0)),
-            i32(K), i32(N), i64(out_group_rows), *tail)
-    _lib.check(rc, "value_proj_bf16")
+    _launch(fn, out.device, "value_proj_bf16", S, a_ptrs, arr64([a.stride(0) for a in a_list]),
+            arr64([a.shape[0] for a in a_list]), arr64(rows_per_group), arr64(out_row0), gb_ptrs, G, packed, out,
+            out.stride(0), K, N, out_group_rows, *((out_scale,) if out_half else ()), timing='value_proj')
     return out
 
 
@@ -1169,14 +1121,10 @@ def value_proj_bf16_planes(a_list, weights, group_biases, out, rows_per_group, o
         gb_ptrs = (ctypes.c_void_p * S)(*[gb_keep[s].data_ptr() for s in range(S)])
     arr64 = lambda v: (ctypes.c_int64 * S)(*[int(x) for x in v])
     a_ptrs = (ctypes.c_void_p * S)(*[a.data_ptr() for a in a_list])
-    with torch.cuda.device(out.device), _timed('value_proj'):
-        rc = _lib.lib().occ_value_proj_bf16_planes(
-            i32(S), a_ptrs, arr64([a.stride(0) for a in a_list]), arr64([a.shape[0] for a in a_list]),
-            arr64(rows_per_group), arr64(out_row0), gb_ptrs, i32(G), ptr(hit[1]), ptr(out),
-            i32(2 if out_q16 else 1 if out_half else 0),
-            i64(N), i32(K), i32(P), i32(N), i64(out.stride(0)), i64(out_group_rows), ptr(out_scale),
-            stream_ptr(out.device))
-    _lib.check(rc, "value_proj_bf16_planes")
+    _launch(_lib.lib().occ_value_proj_bf16_planes, out.device, "value_proj_bf16_planes", S, a_ptrs,
+            arr64([a.stride(0) for a in a_list]), arr64([a.shape[0] for a in a_list]), arr64(rows_per_group), arr64(out_row0),
+            gb_ptrs, G, hit[1], out, 2 if out_q16 else 1 if out_half else 0, N, K, P, N, out.stride(0), out_group_rows,
+            out_scale, timing='value_proj')
     return out
 
 
@@ -1233,14 +1181,9 @@ def linear(a, weight, bias=None, a2=None, a2_add=None, act=None, residual=None, 
         raise OccAmdError("linear: weight must be contiguous")
     wdev = linear_pack_weight_bf16x3(weight) if precision == "bf16x3" and (K1 + K2) % 16 == 0 else weight
     out = torch.empty(a.shape[:-1] + (N,), dtype=torch.float32, device=a.device)
-    if _TIMING is not None and (_TIMING_ONLY is None or 'linear' in _TIMING_ONLY):
-        _TIMING.setdefault('linear_flops', []).append(2.0 * M * N * (K1 + K2))
     fn = _lib.lib().occ_linear_f32 if wdev is weight else _lib.lib().occ_linear_bf16x3_f32
-    with torch.cuda.device(a.device), _timed('linear'):
-        rc = fn(ptr(a_), i64(lda1), i32(K1), ptr(a2), ptr(a2_add), i64(lda2), i32(K2), ptr(wdev),
-                ptr(bias), i32(1 if act == 'relu' else 0), ptr(residual), i64(ldres), ptr(g), ptr(b),
-                f32(float(eps)), ptr(out), i64(N), i32(M), i32(N), stream_ptr(a.device))
-    _lib.check(rc, "linear")
+    _launch(fn, a.device, "linear", a_, lda1, K1, a2, a2_add, lda2, K2, wdev, bias, 1 if act == 'relu' else 0, residual, ldres,
+            g, b, float(eps), out, N, M, N, timing='linear', flops=2.0 * M * N * (K1 + K2))
     if g is not None:
         _attach_ln_bound(out, g, b)
     return out
@@ -1264,15 +1207,13 @@ def linear_chain_pack(weights):
             _need_cuda_f32("weight", w)
             if w.dim() != 2 or w.shape[1] % 16:
                 raise OccAmdUnsupported("linear_chain_pack: weights must be (N, K) with K % 16 == 0")
-            sizes.append(int(lib.occ_linear_chain_packed_bytes(i32(w.shape[0]), i32(w.shape[1]))) // 2)
+            sizes.append(int(lib.occ_linear_chain_packed_bytes(w.shape[0], w.shape[1])) // 2)
         packed = torch.empty(sum(sizes), dtype=torch.int16, device=weights[0].device)
         off = 0
-        with torch.cuda.device(packed.device):
-            for w, n in zip(weights, sizes):
-                rc = lib.occ_linear_chain_pack_bf16x3(ptr(w), ctypes.c_void_p(packed.data_ptr() + off * 2), i32(w.shape[0]),
-                                                      i32(w.shape[1]), stream_ptr(packed.device))
-                _lib.check(rc, "linear_chain_pack_bf16x3")
-                off += n
+        for w, n in zip(weights, sizes):
+            _launch(lib.occ_linear_chain_pack_bf16x3, packed.device, "linear_chain_pack_bf16x3", w, packed[off:], w.shape[0],
+                    w.shape[1])
+            off += n
         return packed
     return _CHAIN_PACKS.get(weights, build, ("w",))
 
@@ -1312,11 +1253,6 @@ def _chain_rows(name, t):
     return t_, M, ld
 
 
-def _chain_time(flops):
-    if _TIMING is not None and (_TIMING_ONLY is None or 'linear' in _TIMING_ONLY):
-        _TIMING.setdefault('linear_flops', []).append(float(flops))
-
-
 def linear_ln_chain(a, residual, w1, b1, ln, w2, b2, act2=None):
     """Program A of csrc/linear_chain_x3.hip in ONE launch:  y = LayerNorm(a @ w1^T + b1 + residual),
     z = act2(y @ w2^T + b2).  a, residual (…, 256) float32 device tensors; w1 (256, 256); w2 (n2, 256) with
@@ -1338,12 +1274,8 @@ def linear_ln_chain(a, residual, w1, b1, ln, w2, b2, act2=None):
     bias = _chain_bias([(b1, 256), (b2, (n2 + 255) // 256 * 256)], a.device)
     y = torch.empty(a.shape[:-1] + (256,), dtype=torch.float32, device=a.device)
     z = torch.empty(a.shape[:-1] + (n2,), dtype=torch.float32, device=a.device)
-    _chain_time(2.0 * M * 256 * (256 + n2))
-    with torch.cuda.device(a.device), _timed('linear'):
-        rc = _lib.lib().occ_linear_ln_chain_bf16x3_f32(
-            ptr(a_), i64(lda), ptr(r_), i64(ldres), ptr(wp), ptr(bias), ptr(g), ptr(b), f32(eps), ptr(y), i64(256),
-            ptr(z), i64(n2), i32(n2), i32(1 if act2 == 'relu' else 0), i32(M), stream_ptr(a.device))
-    _lib.check(rc, "linear_ln_chain")
+    _launch(_lib.lib().occ_linear_ln_chain_bf16x3_f32, a.device, "linear_ln_chain", a_, lda, r_, ldres, wp, bias, g, b, eps, y,
+            256, z, n2, n2, 1 if act2 == 'relu' else 0, M, timing='linear', flops=2.0 * M * 256 * (256 + n2))
     _attach_ln_bound(y, g, b)
     return y, z
 
@@ -1402,13 +1334,9 @@ def encoder_ffn_chain(a, residual, wo, bo, ln1, w1, b1, w2, b2, ln2, tail=None, 
         if tail is not None:
             zq, zv = out[1], out[2]
             ldzq, ldzv = _chain_out("out zq", zq, M, nq), _chain_out("out zv", zv, M, 256)
-    _chain_time(2.0 * M * 256 * (256 + 512 + 512 + (nq + 256 if tail is not None else 0)))
-    with torch.cuda.device(a.device), _timed('linear'):
-        rc = _lib.lib().occ_encoder_ffn_chain_bf16x3_f32(
-            ptr(a_), i64(lda), ptr(r_), i64(ldres), ptr(wp), ptr(bias), ptr(g1), ptr(be1), f32(eps1), ptr(g2),
-            ptr(be2), f32(eps2), ptr(y), i64(ldy), ptr(q_term), i64(ldq), ptr(zq), i64(ldzq), i32(nq), ptr(zv),
-            i64(ldzv), i32(M), stream_ptr(a.device))
-    _lib.check(rc, "encoder_ffn_chain")
+    _launch(_lib.lib().occ_encoder_ffn_chain_bf16x3_f32, a.device, "encoder_ffn_chain", a_, lda, r_, ldres, wp, bias, g1, be1,
+            eps1, g2, be2, eps2, y, ldy, q_term, ldq, zq, ldzq, nq, zv, ldzv, M, timing='linear',
+            flops=2.0 * M * 256 * (256 + 512 + 512 + (nq + 256 if tail is not None else 0)))
     _attach_ln_bound(y, g2, be2)
     return y, zq, zv
 
@@ -1431,12 +1359,8 @@ def linear_pair_chain(a, wq, q_term, wv, bv):
     bias = _chain_bias([(None, 256), (bv, 256)], a.device)
     zq = torch.empty(a.shape[:-1] + (nq,), dtype=torch.float32, device=a.device)
     zv = torch.empty(a.shape[:-1] + (256,), dtype=torch.float32, device=a.device)
-    _chain_time(2.0 * M * 256 * (nq + 256))
-    with torch.cuda.device(a.device), _timed('linear'):
-        rc = _lib.lib().occ_linear_pair_chain_bf16x3_f32(
-            ptr(a_), i64(lda), ptr(wp), ptr(bias), ptr(q_term), i64(ldq), ptr(zq), i64(nq), i32(nq), ptr(zv), i64(256),
-            i32(M), stream_ptr(a.device))
-    _lib.check(rc, "linear_pair_chain")
+    _launch(_lib.lib().occ_linear_pair_chain_bf16x3_f32, a.device, "linear_pair_chain", a_, lda, wp, bias, q_term, ldq, zq, nq,
+            nq, zv, 256, M, timing='linear', flops=2.0 * M * 256 * (nq + 256))
     return zq, zv
 
 
@@ -1458,12 +1382,10 @@ def linear_wgrad(dy, x, with_bias=True):
     dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
     db = torch.empty((N,), dtype=torch.float32, device=dy.device) if with_bias else None
     lib = _lib.lib()
-    nbytes = int(lib.occ_linear_wgrad_workspace_bytes(i32(M), i32(N), i32(K)))
+    nbytes = int(lib.occ_linear_wgrad_workspace_bytes(M, N, K))
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=dy.device)
-    with torch.cuda.device(dy.device), _timed('linear_wgrad'):
-        rc = lib.occ_linear_wgrad_bf16x3_f32(ptr(dy_), i64(lddy), ptr(x_), i64(ldx), ptr(dw), ptr(db), ptr(ws),
-                                             i64(nbytes), i32(M), i32(N), i32(K), stream_ptr(dy.device))
-    _lib.check(rc, "linear_wgrad")
+    _launch(lib.occ_linear_wgrad_bf16x3_f32, dy.device, "linear_wgrad", dy_, lddy, x_, ldx, dw, db, ws, nbytes, M, N, K,
+            timing='linear_wgrad')
     return dw, db
 
 
@@ -1529,15 +1451,13 @@ def _conv3d_x3_wgrad(gp, x, weight, Z, Y, X, in_layout):
         xc = xc.view(B, Y, X, cin, Z).permute(0, 1, 2, 4, 3)                # (B, Y, X, Z, cin) view
     xp = torch.nn.functional.pad(xc, (0, 0, 1, 1, 1, 1, 1, 1)).contiguous()      # (B, Y+2, X+2, Z+2, cin)
     lib = _lib.lib()
-    nbytes = int(lib.occ_conv3d_wgrad_workspace_bytes(i32(B), i32(Z), i32(Y), i32(X), i32(cin)))
+    nbytes = int(lib.occ_conv3d_wgrad_workspace_bytes(B, Z, Y, X, cin))
     if nbytes <= 0:
         raise OccAmdUnsupported("conv3d wgrad: grid beyond the kernel's 32-bit row range")
     ws = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=x.device)
     dw = torch.empty((cout, 27, cin), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _timed('conv3d_wgrad'):
-        rc = lib.occ_conv3d_wgrad_bf16x3_f32(ptr(gp), ptr(xp), ptr(dw), ptr(ws), i64(nbytes), i32(B), i32(Z),
-                                             i32(Y), i32(X), i32(cin), stream_ptr(x.device))
-    _lib.check(rc, "conv3d_wgrad")
+    _launch(lib.occ_conv3d_wgrad_bf16x3_f32, x.device, "conv3d_wgrad", gp, xp, dw, ws, nbytes, B, Z, Y, X, cin,
+            timing='conv3d_wgrad')
     return dw.permute(0, 2, 1).reshape(cout, cin, 3, 3, 3)
 
 
@@ -1552,7 +1472,7 @@ def conv3d_autograd(x, weight, Z, Y, X, in_layout=0):
 def bn3d_relu_train_partial(rows, C, device):
     """Scratch of bn3d_relu_train_stats / bn3d_relu_train_bwd for (rows, C) rows; OccAmdUnsupported outside C = 32,
     rows >= 2, fewer than 2^31 elements."""
-    n = int(_lib.lib().occ_bn3d_relu_train_partial_floats(i64(rows), i32(C)))
+    n = int(_lib.lib().occ_bn3d_relu_train_partial_floats(rows, C))
     if n <= 0:
         raise OccAmdUnsupported(f"bn3d_relu_train: rows={rows} C={C}: needs C = 32, rows >= 2, fewer than 2^31 elements")
     return torch.empty(n, dtype=torch.float32, device=device)
@@ -1574,11 +1494,8 @@ def bn3d_relu_train_stats(y, running_mean, running_var, eaf, eps):
     rows = y.numel() // C
     partial = bn3d_relu_train_partial(rows, C, y.device)
     mean_rstd = torch.empty((2, C), dtype=torch.float32, device=y.device)
-    with torch.cuda.device(y.device), _timed('bn3d_relu_train'):
-        rc = _lib.lib().occ_bn3d_relu_train_stats_f32(ptr(y), ptr(partial), ptr(mean_rstd), ptr(running_mean),
-                                                      ptr(running_var), f32(eaf), f32(eps), i64(rows), i32(C),
-                                                      stream_ptr(y.device))
-    _lib.check(rc, "bn3d_relu_train_stats")
+    _launch(_lib.lib().occ_bn3d_relu_train_stats_f32, y.device, "bn3d_relu_train_stats", y, partial, mean_rstd, running_mean,
+            running_var, eaf, eps, rows, C, timing='bn3d_relu_train')
     if running_mean is not None:        # written through raw pointers: tell autograd (and every version-keyed cache)
         torch._C._increment_version((running_mean, running_var))
     return mean_rstd
@@ -1600,10 +1517,8 @@ def bn3d_relu_train_fwd(y, mean_rstd, gamma, beta, Z, Y, X, out_xy_major=False):
         raise OccAmdError("bn3d_relu_train_fwd: inconsistent shapes")
     out = torch.empty((B, X, Y, Z, C) if out_xy_major else (B, Y, X, Z, C), dtype=torch.float32, device=y.device)
     sb, sy, sx = _bn3d_strides(Z, Y, X, C, out_xy_major)
-    with torch.cuda.device(y.device), _timed('bn3d_relu_train'):
-        rc = _lib.lib().occ_bn3d_relu_train_fwd_f32(ptr(y), ptr(mean_rstd), ptr(gamma), ptr(beta), ptr(out), i32(B), i32(Z),
-                                                    i32(Y), i32(X), i32(C), i64(sb), i64(sy), i64(sx), stream_ptr(y.device))
-    _lib.check(rc, "bn3d_relu_train_fwd")
+    _launch(_lib.lib().occ_bn3d_relu_train_fwd_f32, y.device, "bn3d_relu_train_fwd", y, mean_rstd, gamma, beta, out, B, Z, Y,
+            X, C, sb, sy, sx, timing='bn3d_relu_train')
     return out
 
 
@@ -1624,11 +1539,8 @@ def bn3d_relu_train_bwd(grad_out, y, mean_rstd, gamma, beta, Z, Y, X, grad_xy_ma
     gy = torch.empty((B, Y, X, Z, C), dtype=torch.float32, device=y.device) if want_grad_y else None
     gp = torch.empty((B, Y + 2, X + 2, Z + 2, C), dtype=torch.float32, device=y.device) if want_grad_y_pad else None
     sb, sy, sx = _bn3d_strides(Z, Y, X, C, grad_xy_major)
-    with torch.cuda.device(y.device), _timed('bn3d_relu_train'):
-        rc = _lib.lib().occ_bn3d_relu_train_bwd_f32(ptr(grad_out), i64(sb), i64(sy), i64(sx), ptr(y), ptr(mean_rstd), ptr(gamma),
-                                                    ptr(beta), ptr(partial), ptr(ggb), ptr(gy), ptr(gp), i32(B), i32(Z), i32(Y),
-                                                    i32(X), i32(C), stream_ptr(y.device))
-    _lib.check(rc, "bn3d_relu_train_bwd")
+    _launch(_lib.lib().occ_bn3d_relu_train_bwd_f32, y.device, "bn3d_relu_train_bwd", grad_out, sb, sy, sx, y, mean_rstd, gamma,
+            beta, partial, ggb, gy, gp, B, Z, Y, X, C, timing='bn3d_relu_train')
     return gy, gp, ggb[0], ggb[1]
 
 
@@ -1724,10 +1636,8 @@ def rows_gather_sum(x, index):
     B, rows_in, F = x.shape
     rows_out, K = index.shape
     out = torch.empty((B, rows_out, F), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device), _timed('rows_gather_sum'):
-        rc = _lib.lib().occ_rows_gather_sum_f32(ptr(x), i64(rows_in * F), ptr(index), i32(K), ptr(out), i32(B),
-                                                i64(rows_out), i64(rows_in), i32(F), stream_ptr(x.device))
-    _lib.check(rc, "rows_gather_sum")
+    _launch(_lib.lib().occ_rows_gather_sum_f32, x.device, "rows_gather_sum", x, rows_in * F, index, K, out, B, rows_out,
+            rows_in, F, timing='rows_gather_sum')
     return out
 
 
@@ -1777,11 +1687,8 @@ class SCAPrepFunction(torch.autograd.Function):
         Z = ref_rb.shape[2]
         loc = torch.empty((B, R, M, L, P, 2), dtype=torch.float32, device=proj.device)
         attn = torch.empty((B, R, M, L, P), dtype=torch.float32, device=proj.device)
-        with torch.cuda.device(proj.device), _timed('sca_prep'):
-            rc = _lib.lib().occ_sca_prep_forward_f32(ptr(proj), i64(Q * ld), i32(ld), ptr(row_to_query), ptr(ref_rb),
-                                                     ptr(spatial_shapes), ptr(loc), ptr(attn), i32(B), i64(R),
-                                                     i32(M), i32(L), i32(P), i32(Z), stream_ptr(proj.device))
-        _lib.check(rc, "sca_prep_forward")
+        _launch(_lib.lib().occ_sca_prep_forward_f32, proj.device, "sca_prep_forward", proj, Q * ld, ld, row_to_query, ref_rb,
+                spatial_shapes, loc, attn, B, R, M, L, P, Z, timing='sca_prep')
         ctx.save_for_backward(attn, query_to_rows, spatial_shapes)
         ctx.dims = (B, Q, ld, R, M, L, P)
         return loc, attn
@@ -1796,12 +1703,8 @@ class SCAPrepFunction(torch.autograd.Function):
         dproj = torch.empty((B, Q, ld), dtype=torch.float32, device=attn.device)
         if ld > 3 * M * L * P:
             dproj.zero_()
-        with torch.cuda.device(attn.device), _timed('sca_prep_bwd'):
-            rc = _lib.lib().occ_sca_prep_backward_f32(ptr(g_loc), ptr(g_attn), ptr(attn), ptr(query_to_rows),
-                                                      i32(query_to_rows.shape[1]), ptr(spatial_shapes), ptr(dproj),
-                                                      i32(ld), i32(B), i64(R), i64(Q), i32(M), i32(L), i32(P),
-                                                      stream_ptr(attn.device))
-        _lib.check(rc, "sca_prep_backward")
+        _launch(_lib.lib().occ_sca_prep_backward_f32, attn.device, "sca_prep_backward", g_loc, g_attn, attn, query_to_rows,
+                query_to_rows.shape[1], spatial_shapes, dproj, ld, B, R, Q, M, L, P, timing='sca_prep_bwd')
         return dproj, None, None, None, None, None, None, None
 
 
@@ -1851,11 +1754,8 @@ class DropoutAddLayerNormFunction(torch.autograd.Function):
         z, y = torch.empty_like(x2), torch.empty_like(x2)
         stats = torch.empty((rows, 2), dtype=torch.float32, device=x.device)
         seed = int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item()) if p > 0 else 0
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().occ_dropout_add_ln_fwd_f32(ptr(x2), ptr(r2), ptr(weight), ptr(bias), f32(eps), f32(p),
-                                                       ctypes.c_uint64(seed), ptr(z), ptr(y), ptr(stats), i64(rows), i32(C),
-                                                       stream_ptr(x.device))
-        _lib.check(rc, "dropout_add_ln_fwd")
+        _launch(_lib.lib().occ_dropout_add_ln_fwd_f32, x.device, "dropout_add_ln_fwd", x2, r2, weight, bias, eps, p, seed, z,
+                y, stats, rows, C)
         ctx.save_for_backward(z, stats, weight)
         ctx.cfg = (float(p), seed, tuple(shape), tuple(residual.shape))
         return y.view(shape)
@@ -1868,16 +1768,13 @@ class DropoutAddLayerNormFunction(torch.autograd.Function):
         rows, C = z.shape
         gy2 = gy.reshape(rows, C).contiguous()
         lib = _lib.lib()
-        partial = torch.empty(int(lib.occ_dropout_add_ln_bwd_partial_floats(i64(rows), i32(C))), dtype=torch.float32,
+        partial = torch.empty(int(lib.occ_dropout_add_ln_bwd_partial_floats(rows, C)), dtype=torch.float32,
                               device=z.device)
         gres = torch.empty_like(z)
         gx = torch.empty_like(z) if p > 0 else gres
         ggb = torch.empty(2 * C, dtype=torch.float32, device=z.device)
-        with torch.cuda.device(z.device):
-            rc = lib.occ_dropout_add_ln_bwd_f32(ptr(gy2), ptr(z), ptr(stats), ptr(weight), f32(p), ctypes.c_uint64(seed),
-                                                ptr(gx) if p > 0 else ptr(None), ptr(gres), ptr(partial), ptr(ggb), i64(rows),
-                                                i32(C), stream_ptr(z.device))
-        _lib.check(rc, "dropout_add_ln_bwd")
+        _launch(lib.occ_dropout_add_ln_bwd_f32, z.device, "dropout_add_ln_bwd", gy2, z, stats, weight, p, seed,
+                gx if p > 0 else None, gres, partial, ggb, rows, C)
         return gx.view(shape), gres.view(rshape), ggb[:C], ggb[C:], None, None
 
 
@@ -1950,12 +1847,8 @@ def dvr_render_forward(sigma, origin, points, tindex, grid=None, phase_name="tes
     pred = torch.empty((N, M), dtype=torch.float32, device=dev)
     gt = torch.empty((N, M), dtype=torch.float32, device=dev)
     coord = torch.empty((N, M, 3), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed('dvr_render_forward'):
-        rc = _lib.lib().occ_dvr_render_forward_f32(
-            ptr(sigma), ptr(origin), ptr(points), ptr(tindex), ptr(pred), ptr(gt), ptr(coord), i32(N),
-            i32(T), i32(Z), i32(Y), i32(X), i32(M), i32(points.shape[2]),
-            i32(1 if phase_name == "train" else 0), stream_ptr(dev))
-    _lib.check(rc, "dvr_render_forward")
+    _launch(_lib.lib().occ_dvr_render_forward_f32, dev, "dvr_render_forward", sigma, origin, points, tindex, pred, gt, coord,
+            N, T, Z, Y, X, M, points.shape[2], 1 if phase_name == "train" else 0, timing='dvr_render_forward')
     return pred, gt, coord
 
 
@@ -1995,14 +1888,14 @@ def _eval_workspace(what, workspace, need, dev):
 
 def ray_metrics_state_words(free_id=16):
     """int64 words of the RayIoU / mAVE state for classes 0..free_id (14 per class; layout: include/occnet_amd.h)."""
-    n = int(_lib.lib().occ_ray_metrics_state_words(i32(free_id)))
+    n = int(_lib.lib().occ_ray_metrics_state_words(free_id))
     if n <= 0:
         raise OccAmdError(f"ray_metrics_state_words: free_id must be 1..31, got {free_id}")
     return n
 
 
 def ray_metrics_workspace_bytes(B, X, Y, Z):
-    return int(_lib.lib().occ_ray_metrics_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z)))
+    return int(_lib.lib().occ_ray_metrics_workspace_bytes(B, X, Y, Z))
 
 
 def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins, rays, pc_min, voxel_size, free_id=16,
@@ -2035,14 +1928,10 @@ def ray_metrics_accumulate(state, sem_pred, flow_pred, sem_gt, flow_gt, origins,
     if return_rays:
         rows_pred = torch.zeros((B, Tmax, R, 4), dtype=torch.float32, device=dev)
         rows_gt = torch.zeros((B, Tmax, R, 4), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev), _timed('ray_metrics_accumulate'):
-        rc = _lib.lib().occ_ray_metrics_accumulate(
-            ptr(sem_pred), i32(_SEM_DTYPE_CODES[sem_pred.dtype]), ptr(flow_pred), ptr(sem_gt),
-            i32(_SEM_DTYPE_CODES[sem_gt.dtype]), ptr(flow_gt), ptr(origins), ptr(origin_counts), ptr(rays),
-            f32(pc_min[0]), f32(pc_min[1]), f32(pc_min[2]), f32(voxel_size), i32(free_id), ptr(state), ptr(rows_pred),
-            ptr(rows_gt), ptr(workspace), i64(workspace.numel()), i32(B), i32(Tmax), i32(X), i32(Y), i32(Z), i32(R),
-            stream_ptr(dev))
-    _lib.check(rc, what)
+    _launch(_lib.lib().occ_ray_metrics_accumulate, dev, what, sem_pred, _SEM_DTYPE_CODES[sem_pred.dtype], flow_pred, sem_gt,
+            _SEM_DTYPE_CODES[sem_gt.dtype], flow_gt, origins, origin_counts, rays, pc_min[0], pc_min[1], pc_min[2], voxel_size,
+            free_id, state, rows_pred, rows_gt, workspace, workspace.numel(), B, Tmax, X, Y, Z, R,
+            timing='ray_metrics_accumulate')
     return (rows_pred, rows_gt) if return_rays else None
 
 
@@ -2060,11 +1949,11 @@ def submission_rays_layout(B, Tmax, R):
 
 
 def submission_rays_bytes(B, Tmax, R):
-    return int(_lib.lib().occ_submission_rays_bytes(i32(B), i32(Tmax), i32(R)))
+    return int(_lib.lib().occ_submission_rays_bytes(B, Tmax, R))
 
 
 def submission_rays_workspace_bytes(B, X, Y, Z):
-    return int(_lib.lib().occ_submission_rays_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z)))
+    return int(_lib.lib().occ_submission_rays_workspace_bytes(B, X, Y, Z))
 
 
 def submission_rays_views(packed, B, Tmax, R):
@@ -2111,19 +2000,15 @@ def submission_rays(sem_pred, flow_pred, origins, rays, pc_min, voxel_size, free
         out = torch.zeros(need_out, dtype=torch.uint8, device=dev)
     elif not (out.is_cuda and out.dtype == torch.uint8 and out.is_contiguous() and out.numel() >= need_out):
         raise OccAmdError(f"submission_rays: out must be a contiguous uint8 device tensor of >= {need_out} bytes")
-    with torch.cuda.device(dev), _timed('submission_rays'):
-        rc = _lib.lib().occ_submission_rays(
-            ptr(sem_pred), i32(_SEM_DTYPE_CODES[sem_pred.dtype]), ptr(flow_pred), ptr(origins),
-            i32(_ORIGIN_DTYPE_CODES[origins.dtype]), ptr(origin_counts), ptr(rays), f32(pc_min[0]), f32(pc_min[1]),
-            f32(pc_min[2]), f32(voxel_size), i32(free_id), ptr(out), i64(out.numel()), ptr(workspace),
-            i64(workspace.numel()), i32(B), i32(Tmax), i32(X), i32(Y), i32(Z), i32(R), stream_ptr(dev))
-    _lib.check(rc, what)
+    _launch(_lib.lib().occ_submission_rays, dev, what, sem_pred, _SEM_DTYPE_CODES[sem_pred.dtype], flow_pred, origins,
+            _ORIGIN_DTYPE_CODES[origins.dtype], origin_counts, rays, pc_min[0], pc_min[1], pc_min[2], voxel_size, free_id, out,
+            out.numel(), workspace, workspace.numel(), B, Tmax, X, Y, Z, R, timing='submission_rays')
     return submission_rays_views(out, B, Tmax, R)
 
 
 def render_workspace_bytes(B, X, Y, Z, diff=False):
     """Bytes of the pillar-mask workspace of render_views / render_bev (both grids with diff); 0 for Z > 32."""
-    return int(_lib.lib().occ_render_workspace_bytes(i32(B), i32(X), i32(Y), i32(Z), i32(1 if diff else 0)))
+    return int(_lib.lib().occ_render_workspace_bytes(B, X, Y, Z, 1 if diff else 0))
 
 
 def _render_u8(what, name, t, shape):
@@ -2188,14 +2073,10 @@ def render_views(sem, cams, pc_min, voxel_size, size, free_id=16, sem_gt=None, f
     depth = _render_out(what, 'depth', out.get('depth'), 'depth' in want, (B, V, h, w), torch.float32, dev)
     rgb = _render_out(what, 'rgb', out.get('rgb'), 'rgb' in want, (B, V, h, w, 3), torch.uint8, dev)
     workspace = _eval_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
-    with torch.cuda.device(dev), _timed('render_views'):
-        rc = _lib.lib().occ_render_views(
-            ptr(sem), i32(_SEM_DTYPE_CODES[sem.dtype]), ptr(sem_gt),
-            i32(0 if sem_gt is None else _SEM_DTYPE_CODES[sem_gt.dtype]), ptr(cams), ptr(frames), i32(Hs), i32(Ws),
-            ptr(palette), ptr(cat_palette), f32(pc_min[0]), f32(pc_min[1]), f32(pc_min[2]), f32(voxel_size), i32(free_id),
-            f32(far), f32(tol), i32(alpha), i32(bg_rgb), ptr(label), ptr(depth), ptr(rgb), ptr(workspace),
-            i64(workspace.numel()), i32(B), i32(V), i32(X), i32(Y), i32(Z), i32(h), i32(w), stream_ptr(dev))
-    _lib.check(rc, what)
+    _launch(_lib.lib().occ_render_views, dev, what, sem, _SEM_DTYPE_CODES[sem.dtype], sem_gt,
+            0 if sem_gt is None else _SEM_DTYPE_CODES[sem_gt.dtype], cams, frames, Hs, Ws, palette, cat_palette, pc_min[0],
+            pc_min[1], pc_min[2], voxel_size, free_id, far, tol, alpha, bg_rgb, label, depth, rgb, workspace,
+            workspace.numel(), B, V, X, Y, Z, h, w, timing='render_views')
     return {k: v for k, v in (('label', label), ('depth', depth), ('rgb', rgb)) if v is not None}
 
 
@@ -2221,26 +2102,22 @@ def render_bev(sem, free_id=16, sem_gt=None, palette=None, cat_palette=None, bg_
     label = _render_out(what, 'label', out.get('label'), 'label' in want, (B, X, Y), torch.uint8, dev)
     rgb = _render_out(what, 'rgb', out.get('rgb'), 'rgb' in want, (B, X, Y, 3), torch.uint8, dev)
     workspace = _eval_workspace(what, workspace, render_workspace_bytes(B, X, Y, Z, sem_gt is not None), dev)
-    with torch.cuda.device(dev), _timed('render_bev'):
-        rc = _lib.lib().occ_render_bev(
-            ptr(sem), i32(_SEM_DTYPE_CODES[sem.dtype]), ptr(sem_gt),
-            i32(0 if sem_gt is None else _SEM_DTYPE_CODES[sem_gt.dtype]), ptr(palette), ptr(cat_palette), i32(free_id),
-            i32(bg_rgb), ptr(label), ptr(rgb), ptr(workspace), i64(workspace.numel()), i32(B), i32(X), i32(Y), i32(Z),
-            stream_ptr(dev))
-    _lib.check(rc, what)
+    _launch(_lib.lib().occ_render_bev, dev, what, sem, _SEM_DTYPE_CODES[sem.dtype], sem_gt,
+            0 if sem_gt is None else _SEM_DTYPE_CODES[sem_gt.dtype], palette, cat_palette, free_id, bg_rgb, label, rgb,
+            workspace, workspace.numel(), B, X, Y, Z, timing='render_bev')
     return {k: v for k, v in (('label', label), ('rgb', rgb)) if v is not None}
 
 
 def submission_score_state_words(free_id=16):
     """int64 words of the submission score's state for classes 0..free_id (17 per class; layout: include/occnet_amd.h)."""
-    n = int(_lib.lib().occ_submission_score_state_words(i32(free_id)))
+    n = int(_lib.lib().occ_submission_score_state_words(free_id))
     if n <= 0:
         raise OccAmdError(f"submission_score_state_words: free_id must be 1..31, got {free_id}")
     return n
 
 
 def submission_score_workspace_bytes(B):
-    return int(_lib.lib().occ_submission_score_workspace_bytes(i32(B)))
+    return int(_lib.lib().occ_submission_score_workspace_bytes(B))
 
 
 def _score_side(name, side, B, stride):
@@ -2282,11 +2159,8 @@ def submission_score_accumulate(state, pred, gt, counts, stride, free_id=16, wor
     gf, gc, gd, gfl = _score_side("gt", gt, B, stride)
     dev = state.device
     workspace = _eval_workspace("submission_score_accumulate", workspace, submission_score_workspace_bytes(B), dev)
-    with torch.cuda.device(dev), _timed('submission_score_accumulate'):
-        rc = _lib.lib().occ_submission_score_accumulate(
-            i32(pf), ptr(pc), ptr(pd), ptr(pfl), i32(gf), ptr(gc), ptr(gd), ptr(gfl), ptr(counts), i32(free_id), ptr(state),
-            ptr(workspace), i64(workspace.numel()), i32(B), i64(stride), i32(max_chunks), stream_ptr(dev))
-    _lib.check(rc, "submission_score_accumulate")
+    _launch(_lib.lib().occ_submission_score_accumulate, dev, "submission_score_accumulate", pf, pc, pd, pfl, gf, gc, gd, gfl,
+            counts, free_id, state, workspace, workspace.numel(), B, stride, max_chunks, timing='submission_score_accumulate')
 
 
 _HEADS_LOSS_PARAMS = ("w1_occ", "b1_occ", "w2_occ", "b2_occ", "w1_flow", "b1_flow", "w2_flow", "b2_flow")
@@ -2330,7 +2204,7 @@ def _heads_loss_check(what, feat, params, labels, flow_gt, mask, class_weight, r
 
 
 def _heads_loss_workspace(n_rows, ncls, max_blocks, device):
-    nbytes = int(_lib.lib().occ_heads_loss_workspace_bytes(i64(n_rows), i32(ncls), i32(max_blocks)))
+    nbytes = int(_lib.lib().occ_heads_loss_workspace_bytes(n_rows, ncls, max_blocks))
     if nbytes <= 0:
         raise OccAmdUnsupported(f"heads_loss: no kernel for num_classes={ncls}, max_blocks={max_blocks}")
     return torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=device), nbytes
@@ -2345,12 +2219,9 @@ def heads_loss_forward(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w
     n_rows, ncls = _heads_loss_check("heads_loss_forward", feat, params, labels, flow_gt, mask, class_weight, reduction)
     ws, nbytes = _heads_loss_workspace(n_rows, ncls, max_blocks, feat.device)
     losses = torch.empty(3, dtype=torch.float32, device=feat.device)
-    with torch.cuda.device(feat.device), _timed('heads_loss_fwd'):
-        rc = _lib.lib().occ_heads_loss_fwd_f32(
-            ptr(feat), *[ptr(t) for t in params], ptr(labels), i32(_SEM_DTYPE_CODES[labels.dtype]), ptr(flow_gt), ptr(mask),
-            ptr(class_weight), i64(int(ignore_index)), i32(1 if reduction == 'mean' else 0), ptr(losses), ptr(ws),
-            i64(nbytes), i64(n_rows), i32(32), i32(64), i32(ncls), i32(max_blocks), stream_ptr(feat.device))
-    _lib.check(rc, "heads_loss_forward")
+    _launch(_lib.lib().occ_heads_loss_fwd_f32, feat.device, "heads_loss_forward", feat, *params, labels,
+            _SEM_DTYPE_CODES[labels.dtype], flow_gt, mask, class_weight, int(ignore_index), 1 if reduction == 'mean' else 0,
+            losses, ws, nbytes, n_rows, 32, 64, ncls, max_blocks, timing='heads_loss_fwd')
     return losses
 
 
@@ -2367,13 +2238,10 @@ def heads_loss_backward(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, 
     ws, nbytes = _heads_loss_workspace(n_rows, ncls, max_blocks, feat.device)
     dfeat = torch.empty_like(feat) if need_feat else None
     grads = [torch.empty_like(p) if need else None for p, need in zip(params, need_params)]
-    with torch.cuda.device(feat.device), _timed('heads_loss_bwd'):
-        rc = _lib.lib().occ_heads_loss_bwd_f32(
-            ptr(feat), *[ptr(t) for t in params], ptr(labels), i32(_SEM_DTYPE_CODES[labels.dtype]), ptr(flow_gt), ptr(mask),
-            ptr(class_weight), i64(int(ignore_index)), i32(1 if reduction == 'mean' else 0), ptr(grad_losses),
-            ptr(occ_denom), ptr(dfeat), *[ptr(g) for g in grads], ptr(ws), i64(nbytes), i64(n_rows), i32(32), i32(64),
-            i32(ncls), i32(max_blocks), stream_ptr(feat.device))
-    _lib.check(rc, "heads_loss_backward")
+    _launch(_lib.lib().occ_heads_loss_bwd_f32, feat.device, "heads_loss_backward", feat, *params, labels,
+            _SEM_DTYPE_CODES[labels.dtype], flow_gt, mask, class_weight, int(ignore_index), 1 if reduction == 'mean' else 0,
+            grad_losses, occ_denom, dfeat, *grads, ws, nbytes, n_rows, 32, 64, ncls, max_blocks,
+            timing='heads_loss_bwd')
     return dfeat, grads
 
 
@@ -2414,9 +2282,14 @@ def heads_loss(feat, w1_occ, b1_occ, w2_occ, b2_occ, w1_flow, b1_flow, w2_flow, 
                                       flow_gt, mask, class_weight, ignore_index, reduction, max_blocks)
 
 
+def _is_cl_bf16(t):
+    """True for a channels_last bfloat16 (N, C, H, W) device tensor."""
+    return (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
+            and t.is_contiguous(memory_format=torch.channels_last))
+
+
 def _need_cl_bf16(what, name, t):
-    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
-            and t.is_contiguous(memory_format=torch.channels_last)):
+    if not _is_cl_bf16(t):
         raise OccAmdUnsupported(f"{what}: {name} must be a channels_last bfloat16 device tensor")
 
 
@@ -2428,37 +2301,27 @@ def bias_act_nhwc_(x, bias, residual=None, relu=True):
     N, C, H, W = x.shape
     if bias.numel() != C:
         raise OccAmdError("bias_act_nhwc_: bias must have C entries")
-    if residual is not None and not (residual.dtype == torch.bfloat16 and residual.shape == x.shape and
-                                     residual.is_contiguous(memory_format=torch.channels_last)):
+    if residual is not None and not (_is_cl_bf16(residual) and residual.shape == x.shape):
         raise OccAmdUnsupported("bias_act_nhwc_: residual must match x (channels_last bfloat16)")
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().occ_bias_act_nhwc_bf16(ptr(x), ptr(bias), ptr(residual), i64(N * H * W), i32(C),
-                                               i32(1 if relu else 0), stream_ptr(x.device))
-    _lib.check(rc, "bias_act_nhwc_")
+    _launch(_lib.lib().occ_bias_act_nhwc_bf16, x.device, "bias_act_nhwc_", x, bias, residual, N * H * W, C, 1 if relu else 0)
     return x
 
 
 def bias_act_bwd_nhwc(grad_y, y=None, relu=True):
     """Backward of bias_act_nhwc_ in one pass: -> (g, bias_grad) with g = grad_y * (y > 0) (grad_y itself when not relu) and
     bias_grad (C) float32 = sum of g over N, H, W.  grad_y / y: channels_last bfloat16 (N, C, H, W) device tensors."""
-    ok = lambda t: (t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 4
-                    and t.is_contiguous(memory_format=torch.channels_last))
-    if not ok(grad_y) or (relu and not (y is not None and ok(y) and y.shape == grad_y.shape)):
+    if not _is_cl_bf16(grad_y) or (relu and not (_is_cl_bf16(y) and y.shape == grad_y.shape)):
         raise OccAmdUnsupported("bias_act_bwd_nhwc: grad_y / y must be matching channels_last bfloat16 device tensors")
     N, C, H, W = grad_y.shape
     rows = N * H * W
-    lib = _lib.lib()
-    nfl = int(lib.occ_bias_act_bwd_partial_floats(i64(rows), i32(C)))
+    nfl = _lib.lib().occ_bias_act_bwd_partial_floats(rows, C)
     if nfl <= 0:
         raise OccAmdUnsupported(f"bias_act_bwd_nhwc: no kernel for C={C}")
     partial = torch.empty(nfl, dtype=torch.float32, device=grad_y.device)
     bias_grad = torch.empty(C, dtype=torch.float32, device=grad_y.device)
     g = torch.empty_like(grad_y) if relu else grad_y
-    with torch.cuda.device(grad_y.device):
-        rc = _lib.lib().occ_bias_act_bwd_nhwc_bf16(ptr(grad_y), ptr(y) if relu else ptr(None), ptr(g) if relu else ptr(None),
-                                                   ptr(partial), ptr(bias_grad), i64(rows), i32(C), i32(1 if relu else 0),
-                                                   stream_ptr(grad_y.device))
-    _lib.check(rc, "bias_act_bwd_nhwc")
+    _launch(_lib.lib().occ_bias_act_bwd_nhwc_bf16, grad_y.device, "bias_act_bwd_nhwc", grad_y, y if relu else None,
+            g if relu else None, partial, bias_grad, rows, C, 1 if relu else 0)
     return g, bias_grad
 
 
@@ -2471,10 +2334,8 @@ def conv_bn_fold_fwd(weight, gamma, beta, rstd, mean_rstd):
     wf = torch.empty_like(weight, memory_format=torch.contiguous_format)
     w16 = torch.empty((O, I, KH, KW), dtype=torch.bfloat16, device=weight.device, memory_format=torch.channels_last)
     b = torch.empty(O, dtype=torch.float32, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = _lib.lib().occ_conv_bn_fold_fwd_f32(ptr(weight), ptr(gamma), ptr(beta), ptr(rstd), ptr(mean_rstd), ptr(wf), ptr(w16),
-                                                 ptr(b), i32(O), i32(I), i32(KH), i32(KW), stream_ptr(weight.device))
-    _lib.check(rc, "conv_bn_fold_fwd")
+    _launch(_lib.lib().occ_conv_bn_fold_fwd_f32, weight.device, "conv_bn_fold_fwd", weight, gamma, beta, rstd, mean_rstd, wf,
+            w16, b, O, I, KH, KW)
     return wf, w16, b
 
 
@@ -2489,11 +2350,8 @@ def conv_bn_fold_bwd(grad_w16, weight, gamma, rstd, mean_rstd, grad_bias):
     dW = torch.empty_like(weight, memory_format=torch.contiguous_format)
     dgamma = torch.empty(O, dtype=torch.float32, device=weight.device)
     so, si, sh, sw = grad_w16.stride()
-    with torch.cuda.device(weight.device):
-        rc = _lib.lib().occ_conv_bn_fold_bwd_f32(ptr(grad_w16), i64(so), i64(si), i64(sh), i64(sw), ptr(weight), ptr(gamma),
-                                                 ptr(rstd), ptr(mean_rstd), ptr(grad_bias), ptr(dW), ptr(dgamma), i32(O), i32(I),
-                                                 i32(KH), i32(KW), stream_ptr(weight.device))
-    _lib.check(rc, "conv_bn_fold_bwd")
+    _launch(_lib.lib().occ_conv_bn_fold_bwd_f32, weight.device, "conv_bn_fold_bwd", grad_w16, so, si, sh, sw, weight, gamma,
+            rstd, mean_rstd, grad_bias, dW, dgamma, O, I, KH, KW)
     return dW, dgamma
 
 
@@ -2521,11 +2379,8 @@ def stem_conv7x7_pool(x, weight_frag, bias):
     Hc, Wc = (H - 1) // 2 + 1, (W - 1) // 2 + 1
     Hp, Wp = (Hc - 1) // 2 + 1, (Wc - 1) // 2 + 1
     out = torch.empty((N, 64, Hp, Wp), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    with torch.cuda.device(x.device), _timed('bb_stem7x7_pool'):
-        rc = _lib.lib().occ_stem_conv7x7_pool_f32_bf16(ptr(x), ptr(weight_frag), ptr(bias), ptr(out), i32(N),
-                                                       i32(H), i32(W), stream_ptr(x.device))
-    _note_flops('bb_stem7x7_pool', 2.0 * N * Hc * Wc * 64 * 147)
-    _lib.check(rc, "stem_conv7x7_pool")
+    _launch(_lib.lib().occ_stem_conv7x7_pool_f32_bf16, x.device, "stem_conv7x7_pool", x, weight_frag, bias, out, N, H, W,
+            timing='bb_stem7x7_pool', flops=2.0 * N * Hc * Wc * 64 * 147)
     return out
 
 
@@ -2548,11 +2403,8 @@ def stem_conv7x7_pool_u8(x_u8, weight_frag, bias, mean, std, to_rgb=False, size_
     out = torch.empty((N, 64, Hp, Wp), dtype=torch.bfloat16, device=x_u8.device, memory_format=torch.channels_last)
     mean_c = (f32 * 3)(*[float(v) for v in mean])
     std_c = (f32 * 3)(*[float(v) for v in std])
-    with torch.cuda.device(x_u8.device):
-        rc = _lib.lib().occ_stem_conv7x7_pool_u8_bf16(ptr(x_u8), ptr(weight_frag), ptr(bias), ptr(out), i32(N),
-                                                      i32(Hs), i32(Ws), i32(H), i32(W), mean_c, std_c,
-                                                      i32(1 if to_rgb else 0), stream_ptr(x_u8.device))
-    _lib.check(rc, "stem_conv7x7_pool_u8")
+    _launch(_lib.lib().occ_stem_conv7x7_pool_u8_bf16, x_u8.device, "stem_conv7x7_pool_u8", x_u8, weight_frag, bias, out, N, Hs,
+            Ws, H, W, mean_c, std_c, 1 if to_rgb else 0)
     return out, (H, W)
 
 
@@ -2592,11 +2444,8 @@ def train_input_u8(frames_u8, records, mean, std, to_rgb, size_divisor=32, grid_
         if len(grid_mask) != 7:
             raise OccAmdError("train_input_u8: grid_mask must be (d, l, st_h, st_w, use_h, use_w, mode)")
         gm_c = (i32 * 8)(1, *[int(v) for v in grid_mask])
-    with torch.cuda.device(frames_u8.device), _timed('train_input_u8'):
-        rc = _lib.lib().occ_train_input_u8_f32(ptr(frames_u8), ptr(records), ptr(out), i32(NI), i32(Hs), i32(Ws), i32(H),
-                                               i32(W), mean_c, std_c, i32(1 if to_rgb else 0), gm_c,
-                                               stream_ptr(frames_u8.device))
-    _lib.check(rc, "train_input_u8")
+    _launch(_lib.lib().occ_train_input_u8_f32, frames_u8.device, "train_input_u8", frames_u8, records, out, NI, Hs, Ws, H, W,
+            mean_c, std_c, 1 if to_rgb else 0, gm_c, timing='train_input_u8')
     return out
 
 
@@ -2610,10 +2459,7 @@ def bias_relu_maxpool_nhwc(y, bias):
         raise OccAmdError("bias_relu_maxpool_nhwc: bias must have C entries")
     out = torch.empty((N, C, (H - 1) // 2 + 1, (W - 1) // 2 + 1), dtype=torch.bfloat16, device=y.device,
                       memory_format=torch.channels_last)
-    with torch.cuda.device(y.device):
-        rc = _lib.lib().occ_bias_relu_maxpool_nhwc_bf16(ptr(y), ptr(bias), ptr(out), i32(N), i32(H), i32(W),
-                                                        i32(C), stream_ptr(y.device))
-    _lib.check(rc, "bias_relu_maxpool_nhwc")
+    _launch(_lib.lib().occ_bias_relu_maxpool_nhwc_bf16, y.device, "bias_relu_maxpool_nhwc", y, bias, out, N, H, W, C)
     return out
 
 
@@ -2649,17 +2495,44 @@ def conv1x1_nhwc(x, weight_frag, bias, residual=None, relu=False, stride=1, resi
     want = (N, Cout, Ho // 2, Wo // 2) if residual_upsample2 else tuple(out.shape)
     if residual_upsample2 and (residual is None or Ho % 2 or Wo % 2):
         raise OccAmdUnsupported("conv1x1_nhwc: an upsampled residual needs even output sizes")
-    if residual is not None and not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == want and
-                                     residual.is_contiguous(memory_format=torch.channels_last)):
+    if residual is not None and not (_is_cl_bf16(residual) and tuple(residual.shape) == want):
         raise OccAmdUnsupported("conv1x1_nhwc: residual must match the output (channels_last bfloat16)")
-    with torch.cuda.device(x.device), _timed(_timing):
-        rc = _lib.lib().occ_conv1x1_nhwc_bf16_variant(ptr(x), ptr(weight_frag), ptr(bias), ptr(residual), ptr(out),
-                                                      i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s),
-                                                      i32(1 if relu else 0), i32(1 if residual_upsample2 else 0),
-                                                      i32(0 if variant is None else int(variant)), stream_ptr(x.device))
-    _note_flops(_timing, 2.0 * N * Ho * Wo * Cin * Cout)
-    _lib.check(rc, "conv1x1_nhwc")
+    _launch(_lib.lib().occ_conv1x1_nhwc_bf16_variant, x.device, "conv1x1_nhwc", x, weight_frag, bias, residual, out, N, H, W,
+            Cin, Cout, s, 1 if relu else 0, 1 if residual_upsample2 else 0, 0 if variant is None else int(variant),
+            timing=_timing, flops=2.0 * N * Ho * Wo * Cin * Cout)
     return out
+
+
+def _conv_wgrad_nhwc(k, g, x, stride, out_dtype, splits):
+    """The body of conv1x1_wgrad_nhwc (k = 1) and conv3x3_wgrad_nhwc (k = 3): they differ in their name, their two entry
+    points, the shape and memory format of dw, the kernel_timing name and the k * k taps in the FLOPs."""
+    what = f"conv{k}x{k}_wgrad_nhwc"
+    _need_cl_bf16(what, "g", g)
+    _need_cl_bf16(what, "x", x)
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise OccAmdUnsupported(f"{what}: out_dtype must be float32 or bfloat16")
+    N, Cin, H, W = x.shape
+    s = int(stride)
+    Cout = g.shape[1]
+    if s not in (1, 2) or tuple(g.shape) != (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1) or g.device != x.device:
+        raise OccAmdUnsupported(f"{what}: g must be (N, Cout, (H-1)//stride+1, (W-1)//stride+1) on x's device, "
+                                "stride 1 or 2")
+    sp = 0 if splits is None else int(splits)
+    if sp < 0 or (splits is not None and sp == 0):
+        raise OccAmdError(f"{what}: splits must be None or a positive int")
+    lib = _lib.lib()
+    query, fn = ((lib.occ_conv1x1_wgrad_workspace_bytes, lib.occ_conv1x1_wgrad_nhwc_bf16) if k == 1 else
+                 (lib.occ_conv3x3_wgrad_workspace_bytes, lib.occ_conv3x3_wgrad_nhwc_bf16))
+    nbytes = query(N, H, W, Cin, Cout, s, sp)
+    if nbytes <= 0:
+        raise OccAmdUnsupported(f"{what}: needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048 "
+                                f"(Cin={Cin}, Cout={Cout})")
+    dw = torch.empty((Cout, Cin, k, k), dtype=out_dtype, device=x.device,
+                     memory_format=torch.channels_last if k == 3 else torch.contiguous_format)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)     # torch's caching allocator
+    _launch(fn, x.device, what, g, x, dw, 1 if out_dtype == torch.bfloat16 else 0, ws, N, H, W, Cin, Cout, s, sp,
+            timing=f"bb_conv{k}x{k}_wgrad", flops=2.0 * N * g.shape[2] * g.shape[3] * k * k * Cin * Cout)
+    return dw
 
 
 def conv1x1_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
@@ -2668,33 +2541,7 @@ def conv1x1_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
     g (N, Cout, Ho, Wo) and x (N, Cin, H, W) channels_last bf16 with Ho = (H - 1) // stride + 1 -> (Cout, Cin, 1, 1) in
     out_dtype (float32 or bfloat16).  Cin % 32 == 0, Cout % 32 == 0, both <= 2048, stride 1 or 2: OccAmdUnsupported
     otherwise.  splits: None = the launcher's choice of pixel ranges; an int forces it (tests, probes)."""
-    _need_cl_bf16("conv1x1_wgrad_nhwc", "g", g)
-    _need_cl_bf16("conv1x1_wgrad_nhwc", "x", x)
-    if out_dtype not in (torch.float32, torch.bfloat16):
-        raise OccAmdUnsupported("conv1x1_wgrad_nhwc: out_dtype must be float32 or bfloat16")
-    N, Cin, H, W = x.shape
-    s = int(stride)
-    Cout = g.shape[1]
-    if s not in (1, 2) or tuple(g.shape) != (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1) or g.device != x.device:
-        raise OccAmdUnsupported("conv1x1_wgrad_nhwc: g must be (N, Cout, (H-1)//stride+1, (W-1)//stride+1) on x's device, "
-                                "stride 1 or 2")
-    sp = 0 if splits is None else int(splits)
-    if sp < 0 or (splits is not None and sp == 0):
-        raise OccAmdError("conv1x1_wgrad_nhwc: splits must be None or a positive int")
-    lib = _lib.lib()
-    nbytes = int(lib.occ_conv1x1_wgrad_workspace_bytes(i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp)))
-    if nbytes <= 0:
-        raise OccAmdUnsupported("conv1x1_wgrad_nhwc: needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048 "
-                                f"(Cin={Cin}, Cout={Cout})")
-    dw = torch.empty((Cout, Cin, 1, 1), dtype=out_dtype, device=x.device)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)     # torch's caching allocator
-    with torch.cuda.device(x.device), _timed('bb_conv1x1_wgrad'):
-        rc = lib.occ_conv1x1_wgrad_nhwc_bf16(ptr(g), ptr(x), ptr(dw), i32(1 if out_dtype == torch.bfloat16 else 0), ptr(ws),
-                                             i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp),
-                                             stream_ptr(x.device))
-    _note_flops('bb_conv1x1_wgrad', 2.0 * N * g.shape[2] * g.shape[3] * Cin * Cout)
-    _lib.check(rc, "conv1x1_wgrad_nhwc")
-    return dw
+    return _conv_wgrad_nhwc(1, g, x, stride, out_dtype, splits)
 
 
 def conv1x1_dgrad_nhwc(g, w16):
@@ -2725,10 +2572,7 @@ def mfma_pack_b_frag(weight2d):
     weight2d = weight2d.contiguous()
     n, k = weight2d.shape
     packed = torch.empty(n * k, dtype=torch.int16, device=weight2d.device)
-    with torch.cuda.device(weight2d.device):
-        rc = _lib.lib().occ_mfma_pack_b_frag_bf16(ptr(weight2d), ptr(packed), i32(n), i32(k),
-                                                  stream_ptr(weight2d.device))
-    _lib.check(rc, "mfma_pack_b_frag")
+    _launch(_lib.lib().occ_mfma_pack_b_frag_bf16, weight2d.device, "mfma_pack_b_frag", weight2d, packed, n, k)
     return packed
 
 
@@ -2769,13 +2613,10 @@ def bottleneck64_nhwc(x, pack, variant=0, out=None):
         _need_cl_bf16("bottleneck64_nhwc", "out", out)
         if tuple(out.shape) != (N, 256, H, W) or out.device != x.device or out.data_ptr() == x.data_ptr():
             raise OccAmdError("bottleneck64_nhwc: out must be a (N, 256, H, W) tensor on x's device, not x itself")
-    with torch.cuda.device(x.device), _timed('bb_bottleneck64'):
-        rc = _lib.lib().occ_bottleneck64_nhwc_bf16_variant(ptr(x), ptr(pack['w1']), ptr(pack['b1']), ptr(pack['w2']),
-                                                           ptr(pack['b2']), ptr(pack['w3']), ptr(pack['b3']), ptr(out),
-                                                           i32(N), i32(H), i32(W), i32(Cin), i32(1 if pack['ds'] else 0),
-                                                           i32(int(variant)), stream_ptr(x.device))
-    _note_flops('bb_bottleneck64', 2.0 * N * H * W * (Cin * 64 + 9 * 64 * 64 + 64 * 256 + (Cin * 256 if pack['ds'] else 0)))
-    _lib.check(rc, "bottleneck64_nhwc")
+    _launch(_lib.lib().occ_bottleneck64_nhwc_bf16_variant, x.device, "bottleneck64_nhwc", x, pack['w1'], pack['b1'],
+            pack['w2'], pack['b2'], pack['w3'], pack['b3'], out, N, H, W, Cin, 1 if pack['ds'] else 0, int(variant),
+            timing='bb_bottleneck64',
+            flops=2.0 * N * H * W * (Cin * 64 + 9 * 64 * 64 + 64 * 256 + (Cin * 256 if pack['ds'] else 0)))
     return out
 
 
@@ -2783,7 +2624,7 @@ def bottleneck64_next_pick(batch, H, W, cmid_next):
     """True where bottleneck64_next_nhwc replaces bottleneck64_nhwc + the two conv1x1_nhwc launches behind it for a
     (batch, 256, H, W) map (occ_bottleneck64_next_pick: a kernel for cmid_next, and both 1x1 launches on the resident
     kernel by the launcher's default rule; a pure function of the shape, needs no GPU)."""
-    return bool(_lib.lib().occ_bottleneck64_next_pick(i32(batch), i32(H), i32(W), i32(int(cmid_next))))
+    return bool(_lib.lib().occ_bottleneck64_next_pick(batch, H, W, int(cmid_next)))
 
 
 def bottleneck64_next_nhwc(x, pack, w1_frag, b1, wds_frag, bds, out=None):
@@ -2822,14 +2663,10 @@ def bottleneck64_next_nhwc(x, pack, w1_frag, b1, wds_frag, bds, out=None):
                 raise OccAmdError(f"bottleneck64_next_nhwc: {name} must be a {s} tensor on x's device")
         if len({y.data_ptr(), sc.data_ptr(), x.data_ptr()}) != 3:
             raise OccAmdError("bottleneck64_next_nhwc: x and the two outputs must be distinct tensors")
-    with torch.cuda.device(x.device), _timed('bb_bottleneck64'):
-        rc = _lib.lib().occ_bottleneck64_next_nhwc_bf16(ptr(x), ptr(pack['w1']), ptr(pack['b1']), ptr(pack['w2']),
-                                                        ptr(pack['b2']), ptr(pack['w3']), ptr(pack['b3']), ptr(w1_frag),
-                                                        ptr(b1), ptr(wds_frag), ptr(bds), ptr(y), ptr(sc), i32(N), i32(H),
-                                                        i32(W), i32(cmid), stream_ptr(x.device))
-    _note_flops('bb_bottleneck64', 2.0 * N * H * W * (256 * 64 + 9 * 64 * 64 + 64 * 256 + 256 * cmid)
-                + 2.0 * N * shapes[1][2] * shapes[1][3] * 256 * 4 * cmid)
-    _lib.check(rc, "bottleneck64_next_nhwc")
+    _launch(_lib.lib().occ_bottleneck64_next_nhwc_bf16, x.device, "bottleneck64_next_nhwc", x, pack['w1'], pack['b1'],
+            pack['w2'], pack['b2'], pack['w3'], pack['b3'], w1_frag, b1, wds_frag, bds, y, sc, N, H, W, cmid,
+            timing='bb_bottleneck64', flops=2.0 * N * H * W * (256 * 64 + 9 * 64 * 64 + 64 * 256 + 256 * cmid)
+            + 2.0 * N * shapes[1][2] * shapes[1][3] * 256 * 4 * cmid)
     return y, sc
 
 
@@ -2840,10 +2677,7 @@ def conv3x3_pack_weight(weight):
         raise OccAmdError("conv3x3_pack_weight: expected a (Cout, Cin, 3, 3) weight")
     cout, cin = weight.shape[:2]
     packed = torch.empty(weight.numel(), dtype=torch.int16, device=weight.device)
-    with torch.cuda.device(weight.device):
-        rc = _lib.lib().occ_conv3x3_pack_weight_bf16(ptr(weight), ptr(packed), i32(cout), i32(cin),
-                                                     stream_ptr(weight.device))
-    _lib.check(rc, "conv3x3_pack_weight")
+    _launch(_lib.lib().occ_conv3x3_pack_weight_bf16, weight.device, "conv3x3_pack_weight", weight, packed, cout, cin)
     return packed
 
 
@@ -2874,13 +2708,9 @@ def _conv3x3_nhwc(x, w_packed, bias, cout, relu, stride, amax, variant, timing):
         raise OccAmdError("conv3x3_nhwc: amax must be 8 contiguous int32 device words")
     out = torch.empty((N, cout, (H - 1) // st + 1, (W - 1) // st + 1), dtype=torch.bfloat16, device=x.device,
                       memory_format=torch.channels_last)
-    with torch.cuda.device(x.device), _timed(timing):
-        rc = _lib.lib().occ_conv3x3_nhwc_bf16_variant(ptr(x), ptr(w_packed), ptr(bias), ptr(out), i32(N), i32(H),
-                                                      i32(W), i32(Cin), i32(cout), i32(st), i32(1 if relu else 0),
-                                                      ptr(amax), i32(0 if variant is None else int(variant)),
-                                                      stream_ptr(x.device))
-    _note_flops(timing, 2.0 * N * out.shape[2] * out.shape[3] * 9 * Cin * cout)
-    _lib.check(rc, "conv3x3_nhwc")
+    _launch(_lib.lib().occ_conv3x3_nhwc_bf16_variant, x.device, "conv3x3_nhwc", x, w_packed, bias, out, N, H, W, Cin, cout, st,
+            1 if relu else 0, amax, 0 if variant is None else int(variant), timing=timing,
+            flops=2.0 * N * out.shape[2] * out.shape[3] * 9 * Cin * cout)
     return out
 
 
@@ -2892,33 +2722,7 @@ def conv3x3_wgrad_nhwc(g, x, stride=1, out_dtype=torch.float32, splits=None):
     out_dtype (float32 or bfloat16), channels_last strides (memory order [Cout][3][3][Cin]).  Cin % 32 == 0, Cout % 32 == 0,
     both <= 2048, stride 1 or 2: OccAmdUnsupported otherwise.  splits: None = the launcher's choice of row ranges; an int
     forces it (tests, probes)."""
-    _need_cl_bf16("conv3x3_wgrad_nhwc", "g", g)
-    _need_cl_bf16("conv3x3_wgrad_nhwc", "x", x)
-    if out_dtype not in (torch.float32, torch.bfloat16):
-        raise OccAmdUnsupported("conv3x3_wgrad_nhwc: out_dtype must be float32 or bfloat16")
-    N, Cin, H, W = x.shape
-    s = int(stride)
-    Cout = g.shape[1]
-    if s not in (1, 2) or tuple(g.shape) != (N, Cout, (H - 1) // s + 1, (W - 1) // s + 1) or g.device != x.device:
-        raise OccAmdUnsupported("conv3x3_wgrad_nhwc: g must be (N, Cout, (H-1)//stride+1, (W-1)//stride+1) on x's device, "
-                                "stride 1 or 2")
-    sp = 0 if splits is None else int(splits)
-    if sp < 0 or (splits is not None and sp == 0):
-        raise OccAmdError("conv3x3_wgrad_nhwc: splits must be None or a positive int")
-    lib = _lib.lib()
-    nbytes = int(lib.occ_conv3x3_wgrad_workspace_bytes(i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp)))
-    if nbytes <= 0:
-        raise OccAmdUnsupported("conv3x3_wgrad_nhwc: needs Cin % 32 == 0, Cout % 32 == 0, both <= 2048 "
-                                f"(Cin={Cin}, Cout={Cout})")
-    dw = torch.empty((Cout, Cin, 3, 3), dtype=out_dtype, device=x.device, memory_format=torch.channels_last)
-    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=x.device)     # torch's caching allocator
-    with torch.cuda.device(x.device), _timed('bb_conv3x3_wgrad'):
-        rc = lib.occ_conv3x3_wgrad_nhwc_bf16(ptr(g), ptr(x), ptr(dw), i32(1 if out_dtype == torch.bfloat16 else 0), ptr(ws),
-                                             i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(s), i32(sp),
-                                             stream_ptr(x.device))
-    _note_flops('bb_conv3x3_wgrad', 2.0 * N * g.shape[2] * g.shape[3] * 9 * Cin * Cout)
-    _lib.check(rc, "conv3x3_wgrad_nhwc")
-    return dw
+    return _conv_wgrad_nhwc(3, g, x, stride, out_dtype, splits)
 
 
 def conv3x3_dgrad_weight(weight):
@@ -2954,7 +2758,7 @@ def conv3x3_dgrad_nhwc(g, w16):
 def conv3x3_conv1x1_pick(batch, H, W, cmid, cout, stride=1):
     """Tile id (10 * NT + RT) conv3x3_conv1x1_nhwc uses for an input of (batch, cmid, H, W), or 0 when the shape stays on
     conv3x3_nhwc + conv1x1_nhwc (occ_conv3x3_conv1x1_pick: a pure function of the shape, needs no GPU)."""
-    return int(_lib.lib().occ_conv3x3_conv1x1_pick(i32(batch), i32(H), i32(W), i32(cmid), i32(cout), i32(int(stride))))
+    return int(_lib.lib().occ_conv3x3_conv1x1_pick(batch, H, W, cmid, cout, int(stride)))
 
 
 def conv3x3_conv1x1_nhwc(x, w3_packed, b2, cmid, w1_frag, b3, residual, stride=1, variant=None):
@@ -2980,14 +2784,10 @@ def conv3x3_conv1x1_nhwc(x, w3_packed, b2, cmid, w1_frag, b3, residual, stride=1
         raise OccAmdUnsupported("conv3x3_conv1x1_nhwc: stride must be 1 or 2")
     Ho, Wo = (H - 1) // st + 1, (W - 1) // st + 1
     out = torch.empty((N, Cout, Ho, Wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-    if residual is None or not (residual.dtype == torch.bfloat16 and tuple(residual.shape) == tuple(out.shape) and
-                                residual.is_cuda and residual.is_contiguous(memory_format=torch.channels_last)):
+    if not (_is_cl_bf16(residual) and tuple(residual.shape) == tuple(out.shape)):
         raise OccAmdUnsupported("conv3x3_conv1x1_nhwc: residual must match the output (channels_last bfloat16)")
     # timed under the 3x3 family (bench.py --full sums four fixed family names), with the FLOPs of both convolutions
-    with torch.cuda.device(x.device), _timed('bb_conv3x3'):
-        rc = _lib.lib().occ_conv3x3_conv1x1_nhwc_bf16(ptr(x), ptr(w3_packed), ptr(b2), ptr(w1_frag), ptr(b3), ptr(residual),
-                                                      ptr(out), i32(N), i32(H), i32(W), i32(cmid), i32(Cout), i32(st),
-                                                      i32(0 if variant is None else int(variant)), stream_ptr(x.device))
-    _note_flops('bb_conv3x3', 2.0 * N * Ho * Wo * (9 * Cin * cmid + cmid * Cout))
-    _lib.check(rc, "conv3x3_conv1x1_nhwc")
+    _launch(_lib.lib().occ_conv3x3_conv1x1_nhwc_bf16, x.device, "conv3x3_conv1x1_nhwc", x, w3_packed, b2, w1_frag, b3,
+            residual, out, N, H, W, cmid, Cout, st, 0 if variant is None else int(variant), timing='bb_conv3x3',
+            flops=2.0 * N * Ho * Wo * (9 * Cin * cmid + cmid * Cout))
     return out

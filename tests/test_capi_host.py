@@ -17,6 +17,77 @@ def test_library_exports_declared_symbols():
     assert lib.occ_abi_version() == _lib.ABI == 3
 
 
+def test_every_prototype_is_bound_from_the_header():
+    """_lib.lib() sets restype and argtypes on every function of the header, from the header's own text."""
+    import re
+    protos = _lib.prototypes()
+    assert sorted(protos) == _lib.declared_symbols() and len(protos) == 102
+    lib = _lib.lib()
+    for name, (restype, params) in protos.items():
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == len(params), name
+        assert fn.restype is restype and restype is not None, name
+    with open(_lib.HEADER_PATH) as f:
+        wide = set(re.findall(r"\bint64_t\s+(occ_[a-z0-9_]+)\s*\(", f.read()))
+    assert len(wide) == 20
+    for name in wide:
+        assert getattr(lib, name).restype is ctypes.c_int64, name
+    # spot checks of the three kinds of parameter: scalar widths as declared, every pointer the tensor-accepting type
+    kinds = [t for t, _ in protos["occ_ms_deform_attn_backward_ws_f32"][1]]
+    assert kinds[:9] == [_lib.DevicePtr] * 9 and kinds[9:17] == [ctypes.c_int] * 8
+    assert kinds[17:] == [_lib.DevicePtr, ctypes.c_int64, _lib.DevicePtr]
+    assert [n for _, n in protos["occ_sca_rows_encode_q16"][1]] == ["v", "out", "scale", "groups", "S", "C", "stream"]
+    assert protos["occ_last_error"] == (ctypes.c_char_p, []) and protos["occ_ln_dropout_hash"][0] is ctypes.c_uint
+
+
+def test_int64_answers_arrive_whole():
+    lib = _lib.lib()
+    assert lib.occ_linear_chain_packed_bytes(1 << 20, 1 << 11) == 1 << 33
+    assert lib.occ_submission_rays_bytes(64, 8, 1 << 22) == 7 * (1 << 31)
+
+
+def test_binding_mistakes_stop_on_the_host():
+    """A wrong argument count or kind raises before the library is entered: its last error stays what it was."""
+    lib = _lib.lib()
+    null = ctypes.c_void_p(0)
+    assert lib.occ_ms_deform_attn_forward_f32(null, null, null, null, null, null, 1, 1, 1, 1, 1, 1, 1, 64, null) == -1
+    before = lib.occ_last_error()
+    assert b'null' in before
+    buf = (ctypes.c_float * 4)()
+    p = ctypes.cast(buf, ctypes.c_void_p)
+    with pytest.raises(TypeError):                                 # one argument short
+        lib.occ_ms_deform_attn_forward_f32(p, p, p, p, p, p, 1, 1, 1, 1, 1, 1, 1, 64)
+    with pytest.raises(ctypes.ArgumentError):                      # a float where int B is expected
+        lib.occ_ms_deform_attn_forward_f32(p, p, p, p, p, p, 1.0, 1, 1, 1, 1, 1, 1, 64, null)
+    with pytest.raises(ctypes.ArgumentError):                      # a c_int in the int64_t workspace_bytes slot
+        lib.occ_ms_deform_attn_backward_ws_f32(p, p, p, p, p, p, p, p, p, 1, 1, 1, 1, 1, 1, 1, 64, p, ctypes.c_int(1), null)
+    assert lib.occ_last_error() == before
+
+
+def test_pointer_parameters_take_what_the_callers_pass():
+    """None, an int, a c_void_p, a ctypes array, byref(...) and a torch.Tensor all cross a foreign call as the address they
+    stand for (the callee here is a ctypes callback with the binding's pointer type as its argtype)."""
+    echo = ctypes.CFUNCTYPE(ctypes.c_size_t, _lib.DevicePtr)(lambda p: p.value or 0)
+    buf = (ctypes.c_float * 4)()
+    addr = ctypes.addressof(buf)
+    t = torch.zeros(4)
+    assert echo(None) == 0
+    for a in (addr, ctypes.c_void_p(addr), buf, ctypes.byref(buf), ctypes.cast(buf, ctypes.c_void_p)):
+        assert echo(a) == addr
+    assert echo(t) == t.data_ptr() != 0 and echo(t[1:]) == t.data_ptr() + 4
+    with pytest.raises(ctypes.ArgumentError):
+        echo(1.5)
+
+
+def test_parser_refuses_a_type_it_does_not_know():
+    assert list(_lib.prototypes("/* c */\n#define X 1\nint occ_y(const void* const* a, int64_t n);")["occ_y"][1]) == \
+        [(_lib.DevicePtr, "a"), (ctypes.c_int64, "n")]
+    with pytest.raises(_lib.OccAmdError, match="occ_x"):
+        _lib.prototypes("int occ_x(double v);")
+    with pytest.raises(_lib.OccAmdError, match="occ_z"):
+        _lib.prototypes("double occ_z(int v);")
+
+
 def test_argument_validation_without_gpu():
     lib = _lib.lib()
     null = ctypes.c_void_p(0)
@@ -88,7 +159,6 @@ def test_backbone_and_projection_entry_points_validate_without_gpu():
     assert lib.occ_conv3x3_nhwc_bf16_amax(p, p, p, p, 1, 4, 4, 32, 128, 1, 1, null, null) == -1     # null amax8
     assert lib.occ_value_range_scale_bf16(1, ptrs, one, one, 64, 4, f4, f4, null, p, null) == -1  # no output
     # fused second convolution + heads + decode (round 3)
-    lib.occ_conv3d_heads_pack_bytes.restype = ctypes.c_int64
     assert lib.occ_conv3d_heads_pack_bytes() == 16 * 1024 + 16 * 1024 + 128 * 4 + 32 * 4
     hargs = lambda Z, Cin, ncls, occ=p: (p, p, p, p, p, occ, p, null, 1, Z, 4, 4, Cin, ncls, null)
     assert lib.occ_conv3d_heads_decode_bf16x3_f32(*hargs(16, 32, 17, null)) == -1                 # null output
@@ -96,7 +166,6 @@ def test_backbone_and_projection_entry_points_validate_without_gpu():
     assert lib.occ_conv3d_heads_decode_bf16x3_f32(*hargs(16, 16, 17)) == -3                       # Cin = 16
     assert lib.occ_conv3d_heads_decode_bf16x3_f32(*hargs(16, 32, 40)) == -3                       # > 30 classes
     # row-local Linear chains (round 4): argument checks before any launch
-    lib.occ_linear_chain_packed_bytes.restype = ctypes.c_int64
     assert lib.occ_linear_chain_packed_bytes(768, 256) == 768 * 256 * 4
     assert lib.occ_linear_chain_packed_bytes(192, 256) == 256 * 256 * 4                           # padded to a 256-row group
     assert lib.occ_linear_chain_pack_bf16x3(p, p, 256, 40, null) == -3                            # K % 16
@@ -162,8 +231,6 @@ def test_training_entry_points_validate_without_gpu():
     buf = (ctypes.c_float * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
     i64 = ctypes.c_int64
-    lib.occ_linear_wgrad_workspace_bytes.restype = ctypes.c_int64
-    lib.occ_ms_deform_attn_backward_workspace_bytes.restype = ctypes.c_int64
     # one partial (N*K + N floats) per row chunk; 512 blocks when the rows allow it
     ws = lib.occ_linear_wgrad_workspace_bytes(40000, 512, 256)
     assert ws > 0 and ws % ((512 * 256 + 512) * 4) == 0 and ws // ((512 * 256 + 512) * 4) == 63    # 640-row chunks
@@ -205,9 +272,6 @@ def test_round6_training_nodes_validate_without_gpu():
     buf = (ctypes.c_float * 64)()
     p = ctypes.cast(buf, ctypes.c_void_p)
     i64, f32 = ctypes.c_int64, ctypes.c_float
-    lib.occ_bias_act_bwd_partial_floats.restype = ctypes.c_int64
-    lib.occ_dropout_add_ln_bwd_partial_floats.restype = ctypes.c_int64
-    lib.occ_ln_dropout_hash.restype = ctypes.c_uint32
     # bias_act backward: <= 512 blocks of 256 / (C / 8) rows each, one row of C partial sums per block; C % 8 == 0, C <= 2048
     assert lib.occ_bias_act_bwd_partial_floats(i64(6 * 116 * 200), 512) == 512 * 512
     assert lib.occ_bias_act_bwd_partial_floats(i64(7), 64) == 1 * 64

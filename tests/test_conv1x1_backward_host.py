@@ -15,7 +15,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_wgrad_workspace_and_argument_checks_without_gpu():
     lib = _lib.lib()
-    lib.occ_conv1x1_wgrad_workspace_bytes.restype = ctypes.c_int64
     ws = lib.occ_conv1x1_wgrad_workspace_bytes
     n = ws(2, 12, 20, 256, 128, 1, 0)
     assert n > 0 and n % (128 * 256 * 4) == 0                     # whole f32 partials of the (Cout, Cin) output

@@ -16,7 +16,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_wgrad_workspace_and_argument_checks_without_gpu():
     lib = _lib.lib()
-    lib.occ_conv3x3_wgrad_workspace_bytes.restype = ctypes.c_int64
     ws = lib.occ_conv3x3_wgrad_workspace_bytes
     one = 9 * 128 * 256 * 4                                       # one f32 partial of the (Cout, 3, 3, Cin) output
     n = ws(2, 12, 20, 256, 128, 1, 0)

@@ -55,13 +55,11 @@ def test_wgrad_matches_float64(N, Cin, Cout, H, W, stride, splits):
     """|got - want| <= B = P * 2^-23 * (|g| (*) |x|) for the fp32 output (the worst-case bound of an fp32 sum of exact
     products in any order, doubled; P = output pixels), 2^-8 |want| + 2 B for the bf16 output (one round-to-nearest on top).
     dw and the workspace hold NaN before the call and dw is finite after it; the C ABI and ext give the same bits, twice."""
-    import ctypes
     from occnet_amd import _lib, ext
     from occnet_amd._lib import i32, ptr, stream_ptr
     g, x, want, mag, P = _wgrad_problem(N, Cin, Cout, H, W, stride)
     B = P * 2.0 ** -23 * mag
     lib = _lib.lib()
-    lib.occ_conv3x3_wgrad_workspace_bytes.restype = ctypes.c_int64
     sp = 0 if splits is None else splits
     nbytes = int(lib.occ_conv3x3_wgrad_workspace_bytes(i32(N), i32(H), i32(W), i32(Cin), i32(Cout), i32(stride), i32(sp)))
     assert nbytes > 0 and nbytes % (9 * Cout * Cin * 4) == 0

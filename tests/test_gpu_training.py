@@ -426,7 +426,6 @@ def test_dropout_add_layernorm_node_matches_torch(rows, p, monkeypatch):
         assert len(seeds) == 1
         keep = _keep_mask(n, seeds[0], p)
         lib = _lib.lib()
-        lib.occ_ln_dropout_hash.restype = ctypes.c_uint32
         thr = int(p * 4294967296.0)
         for i in (0, 1, 255, 256, n - 1):
             assert (lib.occ_ln_dropout_hash(ctypes.c_uint32(i), ctypes.c_uint32(seeds[0] & 0xffffffff),

@@ -32,8 +32,6 @@ def test_symbols_declared_and_exported():
     for name in ('occ_ray_metrics_accumulate', 'occ_ray_metrics_state_words', 'occ_ray_metrics_workspace_bytes'):
         assert name in declared and hasattr(lib, name), name
     assert lib.occ_abi_version() == _lib.ABI == 3
-    lib.occ_ray_metrics_state_words.restype = ctypes.c_int64
-    lib.occ_ray_metrics_workspace_bytes.restype = ctypes.c_int64
     assert lib.occ_ray_metrics_state_words(16) == ROWS * 17
     assert lib.occ_ray_metrics_state_words(0) == 0 and lib.occ_ray_metrics_state_words(32) == 0
     assert lib.occ_ray_metrics_workspace_bytes(1, 200, 200, 16) == 2 * 200 * 200 * 2          # uint16 masks, both grids

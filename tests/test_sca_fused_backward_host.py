@@ -40,7 +40,6 @@ def _ws_bytes(B, NC, S, M, L, P, Nq):
 
 def _lib_ws():
     lib = _lib.lib()
-    lib.occ_sca_fused_backward_workspace_bytes.restype = ctypes.c_int64
     return lib
 
 

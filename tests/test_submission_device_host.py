@@ -16,8 +16,6 @@ from tests import submission_ref as sref
 
 def _lib64():
     lib = _lib.lib()
-    lib.occ_submission_rays_bytes.restype = ctypes.c_int64
-    lib.occ_submission_rays_workspace_bytes.restype = ctypes.c_int64
     return lib
 
 
@@ -60,7 +58,6 @@ def test_byte_queries():
     assert ext.submission_rays_workspace_bytes(1, 200, 200, 33) == 0
     assert lib.occ_submission_rays_workspace_bytes(0, 200, 200, 16) == 0
     # one grid's masks: two samples here take what the evaluator needs for the two grids of one
-    lib.occ_ray_metrics_workspace_bytes.restype = ctypes.c_int64
     assert lib.occ_submission_rays_workspace_bytes(2, 200, 200, 16) == lib.occ_ray_metrics_workspace_bytes(1, 200, 200, 16)
 
 
@@ -70,8 +67,6 @@ def test_workspace_queries_agree(B, X, Y, Z):
     """One formula behind the three queries: `grids` grids of B * X * Y mask words (2 bytes up to Z = 16, 4 up to 32), rounded up
     to 256 bytes; 0 where there are no masks.  The evaluator holds two grids, the writer one, the renderer one or two."""
     lib = _lib64()
-    lib.occ_ray_metrics_workspace_bytes.restype = ctypes.c_int64
-    lib.occ_render_workspace_bytes.restype = ctypes.c_int64
 
     def want(batch, grids):
         if batch <= 0 or Z > 32:

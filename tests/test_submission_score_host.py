@@ -65,8 +65,6 @@ def test_rounding_path_is_live(gold):
 
 def _lib64():
     lib = _lib.lib()
-    lib.occ_submission_score_state_words.restype = ctypes.c_int64
-    lib.occ_submission_score_workspace_bytes.restype = ctypes.c_int64
     return lib
 
 
