@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/occnet_amd.h.
+"""ctypes binding of the C ABI in include/occnet_amd.h (and the headers of EXTRA_HEADERS).
 
 The product path has no CPU fallback: if libocc_amd.so is missing or an entry point is absent this
 module raises at import/use time.  torch is imported first so the HIP runtime already loaded by
@@ -13,6 +13,8 @@ import torch  # noqa: F401  (loads libamdhip64 before our library)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "libocc_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "occnet_amd.h")
+# headers whose prototypes lib() binds besides the main one's: extensions of the C ABI that leave occnet_amd.h as it is
+EXTRA_HEADERS = (os.path.join(os.path.dirname(_HERE), "include", "occnet_amd_visibility.h"),)
 
 
 class OccAmdError(RuntimeError):
@@ -89,7 +91,11 @@ def lib():
                 f"{LIB_PATH} not found: build it with `python -m occnet_amd.build` "
                 "(the MI355X path has no CPU fallback)")
         _lib = ctypes.CDLL(LIB_PATH)
-        for name, (restype, args) in prototypes().items():
+        protos = prototypes()
+        for header in EXTRA_HEADERS:
+            with open(header) as f:
+                protos.update(prototypes(f.read()))
+        for name, (restype, args) in protos.items():
             fn = getattr(_lib, name)
             fn.restype, fn.argtypes = restype, [t for t, _ in args]
         if _lib.occ_abi_version() != ABI:

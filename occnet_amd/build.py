@@ -27,7 +27,9 @@ def sources():
 
 
 def _headers():
-    return [HEADER] + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
+    inc = os.path.dirname(HEADER)      # the main header first, then its extensions (occnet_amd_visibility.h)
+    public = [HEADER] + sorted(p for p in (os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")) if p != HEADER)
+    return public + sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h"))
 
 
 def _file_digest(paths):

@@ -1,8 +1,9 @@
-// The ray caster shared by the device-resident evaluation (ray_metrics_fused.hip), the submission writer (submission_rays.hip)
-// and the renderer (occ_render.hip): class read, occupancy bit masks per pillar, the origin / end-point conversion of
-// process_one_sample, the traversal set-up of csrc/dvr_render.hip and its "test"-phase walk over the masks.  One copy of the
-// text: the files report the same voxel and the same distance for the same ray, bit for bit.  Below the kernels, the host side
-// their entry points share: the workspace size, the grid-argument checks, the mask launch and the mask-type dispatch.
+// The ray caster shared by the device-resident evaluation (ray_metrics_fused.hip), the submission writer (submission_rays.hip),
+// the renderer (occ_render.hip) and the camera visibility masks (visibility.hip, which walks with rm_visit): class read,
+// occupancy bit masks per pillar, the origin / end-point conversion of process_one_sample, the traversal set-up of
+// csrc/dvr_render.hip and its "test"-phase walk over the masks.  One copy of the text: the files report the same voxel and the
+// same distance for the same ray, bit for bit.  Below the kernels, the host side their entry points share: the workspace size,
+// the grid-argument checks, the mask launch and the mask-type dispatch.
 //
 // Lane predicates that select a load address are kept as 0 / 1 integers (common.h: lane_flag) and every load inside the
 // traversal is issued with a clamped, always-legal index; the traversal of a lane that is not cast runs zero steps.
@@ -18,7 +19,14 @@ __device__ __forceinline__ int rm_class_at(const void* __restrict__ sem, int is_
   return (v < -2147483647ll || v > 2147483647ll) ? -1 : (int)v;      // beyond int: occupied, counted in no class
 }
 
-// One thread per pillar of one grid: bit z set iff class(x, y, z) != free_id.  grid 0 = prediction, 1 = ground truth
+// The occupancy bits of pillar p (cells p * Z .. p * Z + Z - 1): bit z set iff class(x, y, z) != free_id.
+__device__ __forceinline__ unsigned rm_pillar_bits(const void* __restrict__ sem, int is_i64, long p, int Z, int free_id) {
+  unsigned m = 0;
+  for (int z = 0; z < Z; ++z) m |= (rm_class_at(sem, is_i64, p * Z + z) != free_id ? 1u : 0u) << z;
+  return m;
+}
+
+// One thread per pillar of one grid: its occupancy bits.  grid 0 = prediction, 1 = ground truth
 // (a launch with gridDim.y == 1 builds the prediction's masks only and never reads sem_gt).
 template <typename MaskT>
 __global__ __launch_bounds__(256) void ray_metrics_occupancy_kernel(
@@ -29,9 +37,7 @@ __global__ __launch_bounds__(256) void ray_metrics_occupancy_kernel(
   const int g = blockIdx.y;
   const void* sem = g ? sem_gt : sem_pred;
   const int is_i64 = g ? gt_i64 : pred_i64;
-  unsigned m = 0;
-  for (int z = 0; z < Z; ++z) m |= (rm_class_at(sem, is_i64, p * Z + z) != free_id ? 1u : 0u) << z;
-  masks[(long)g * pillars + p] = (MaskT)m;
+  masks[(long)g * pillars + p] = (MaskT)rm_pillar_bits(sem, is_i64, p, Z, free_id);
 }
 
 struct RmHit {
@@ -120,6 +126,77 @@ __device__ __forceinline__ RmHit rm_cast(const RmRay& r, const MaskT* __restrict
   h.dist = was_inside ? (float)last_d : -1.f;
   h.x = lx; h.y = ly; h.z = lz;
   return h;
+}
+
+// The visiting walk (visibility.hip): rm_cast's loop statement for statement — the same tMax comparison order, steps 0..1000, the
+// same "left the grid" break — which MARKS every voxel the loop body runs for with `inside` true, the first occupied voxel (where
+// the loop ends) included.  `vis` holds one uint32 word per pillar of this grid, bit z = voxel (x, y, z) visited.  A ray ORs the z
+// bits it collects while it stays in one pillar into that word with one atomicOr when it leaves the pillar (rm_mark), and at the
+// end of the walk.  OR is order-independent: the words do not depend on the order of the rays.  live == 0: zero steps, no store.
+//
+// rm_mark — the lanes of a wave that leave a pillar in the same step mostly leave the SAME pillar with the same bits (an 8 x 8
+// pixel tile is a narrow bundle), so they are served in rounds: the first lane still waiting is the round's leader, it alone
+// touches memory, and every lane of its pillar whose bits its own cover is done with it (the leader always retires itself, so the
+// loop ends).  The leader skips the atomic when the word already shows its bits; that read may be served from the vector L1
+// (wavefront scope).  `seen` may be stale only towards FEWER bits, which costs an atomic and never a mark: within the kernel bits
+// are only ever set, and the acquire at the kernel's start keeps words of an earlier launch — set bits of a reused workspace, from
+// before visibility_prepare_kernel cleared them — out of the L1.
+// KEEP WAVE-UNIFORM: the `while` condition and the readlane index.  `todo` is a ballot and every marking lane stays in the loop to
+// its end; a loop that lanes leave one by one (readfirstlane inside a divergent `while`) was compiled to a single pass and marked
+// wrong voxels (EXPERIMENTS.md 8zc).
+__device__ __forceinline__ void rm_mark(unsigned* vis, int held, unsigned bits) {
+  if (!bits) return;
+  const int lane = threadIdx.x & 63;
+  unsigned long long todo = __builtin_amdgcn_ballot_w64(true);              // the lanes that mark now
+  while (todo) {
+    const int leader = __ffsll((long long)todo) - 1;
+    const int lead = __builtin_amdgcn_readlane(held, leader);
+    const unsigned lead_bits = (unsigned)__builtin_amdgcn_readlane((int)bits, leader);
+    if (lane == leader) {
+      const unsigned seen = __hip_atomic_load(vis + lead, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      if ((seen & lead_bits) != lead_bits) atomicOr(vis + lead, lead_bits);
+    }
+    const int done = lane_flag(held == lead) & lane_flag((bits & ~lead_bits) == 0u);
+    todo &= ~__builtin_amdgcn_ballot_w64(done != 0);
+  }
+}
+
+template <typename MaskT>
+__device__ __forceinline__ void rm_visit(const RmRay& r, const MaskT* __restrict__ masks, unsigned* vis, int X, int Y, int Z,
+                                         int live) {
+#pragma clang fp contract(off)
+  int vx = r.vx, vy = r.vy, vz = r.vz;
+  double tMaxX = r.tMaxX, tMaxY = r.tMaxY, tMaxZ = r.tMaxZ;
+  int was_inside = 0;
+  int held = 0;                               // the pillar whose bits are in `bits` (any legal word while bits == 0)
+  unsigned bits = 0u;
+  const int last_step = live ? 1000 : -1;
+  for (int step = 0; step <= last_step; ++step) {
+    const int inside = lane_flag(0 <= vx) & lane_flag(vx < X) & lane_flag(0 <= vy) & lane_flag(vy < Y) &
+                       lane_flag(0 <= vz) & lane_flag(vz < Z);
+    if (!inside && was_inside) break;
+    const int cx = vx, cy = vy, cz = vz;
+    if (tMaxX < tMaxY) {
+      if (tMaxX < tMaxZ) { vx += r.stepX; tMaxX += r.tDeltaX; }
+      else { vz += r.stepZ; tMaxZ += r.tDeltaZ; }
+    } else {
+      if (tMaxY < tMaxZ) { vy += r.stepY; tMaxY += r.tDeltaY; }
+      else { vz += r.stepZ; tMaxZ += r.tDeltaZ; }
+    }
+    const int pillar = inside ? cx * Y + cy : 0;                 // always a legal word
+    const unsigned m = (unsigned)masks[pillar];
+    if (inside) {
+      was_inside = 1;
+      if (pillar != held) {
+        rm_mark(vis, held, bits);
+        held = pillar;
+        bits = 0u;
+      }
+      bits |= 1u << cz;
+      if ((m >> cz) & 1u) break;
+    }
+  }
+  rm_mark(vis, held, bits);
 }
 
 // ---- host side: what every entry point over the pillar masks asks, checks and launches -----------------------------------------

@@ -2108,6 +2108,75 @@ def render_bev(sem, free_id=16, sem_gt=None, palette=None, cat_palette=None, bg_
     return {k: v for k, v in (('label', label), ('rgb', rgb)) if v is not None}
 
 
+def visibility_workspace_bytes(B, X, Y, Z):
+    """Bytes of the workspace of visibility_views (pillar masks + one visibility word per pillar); 0 for Z > 32."""
+    return int(_lib.lib().occ_visibility_workspace_bytes(B, X, Y, Z))
+
+
+def visibility_views(sem, cams, pc_min, voxel_size, size, free_id=16, far=100.0, out=None, workspace=None):
+    """The voxels seen by the cameras, in three launches on the current stream: no synchronisation, no copy
+    (csrc/visibility.hip; the definition is written out in include/occnet_amd_visibility.h).  A voxel is marked when a pixel ray
+    of render_views — same cams, same size = (h, w), same far — passes through it before it is stopped, the first occupied
+    voxel included.
+    sem (B, X, Y, Z) uint8 or int64; cams (B, V, 12) float32 (vis.view_rays); out: None, or a contiguous uint8 device tensor
+    of at least B * X * Y * Z elements (every byte of the mask is written); workspace: None, or a uint8 device tensor of at
+    least visibility_workspace_bytes(B, X, Y, Z) bytes, reusable from call to call as it is.
+    -> mask (B, X, Y, Z) uint8: 1 seen, 0 not."""
+    what = "visibility_views"
+    _eval_grid(what, "sem", sem)
+    _need_cuda_f32("cams", cams)
+    B, X, Y, Z = sem.shape
+    if cams.dim() != 3 or cams.shape[0] != B or cams.shape[2] != 12 or not cams.is_contiguous():
+        raise OccAmdError(f"{what}: cams must be a contiguous (B, V, 12) tensor, got {tuple(cams.shape)}")
+    V = cams.shape[1]
+    h, w = int(size[0]), int(size[1])
+    dev = sem.device
+    mask = _render_out(what, 'mask', out, True, (B, X, Y, Z), torch.uint8, dev)
+    workspace = _eval_workspace(what, workspace, visibility_workspace_bytes(B, X, Y, Z), dev)
+    for name, t in (("cams", cams), ("out", mask), ("workspace", workspace)):
+        if t.device != dev:
+            raise OccAmdError(f"{what}: {name} must be on the device of sem ({dev}), got {t.device}")
+    _launch(_lib.lib().occ_visibility_views, dev, what, sem, _SEM_DTYPE_CODES[sem.dtype], cams, pc_min[0], pc_min[1],
+            pc_min[2], voxel_size, free_id, far, mask, workspace, workspace.numel(), B, V, X, Y, Z, h, w,
+            timing='visibility_views')
+    return mask
+
+
+def confusion_state_words(free_id=16):
+    """int64 words of the confusion state for classes 0..free_id: (ncls + 1) * ncls, ncls = free_id + 1 (layout:
+    include/occnet_amd_visibility.h)."""
+    n = int(_lib.lib().occ_confusion_state_words(free_id))
+    if n <= 0:
+        raise OccAmdError(f"confusion_state_words: free_id must be 1..31, got {free_id}")
+    return n
+
+
+def confusion_accumulate(state, sem_pred, sem_gt, mask=None, free_id=16):
+    """Add the confusion counts of two class grids over the voxels `mask` admits (None: all) to `state` (int64 device tensor of
+    confusion_state_words(free_id) words), in one launch on the current stream (csrc/visibility.hip).
+    sem_pred / sem_gt: contiguous uint8 or int64 device tensors of the same shape; mask: None, or a contiguous bool / uint8
+    device tensor of as many elements."""
+    what = "confusion_accumulate"
+    for name, t in (("sem_pred", sem_pred), ("sem_gt", sem_gt)):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda:
+            raise OccAmdError(f"{what}: {name} must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+        if t.dtype not in _SEM_DTYPE_CODES or not t.is_contiguous():
+            raise OccAmdError(f"{what}: {name} must be a contiguous uint8 or int64 tensor, got {t.dtype}")
+    if sem_gt.shape != sem_pred.shape:
+        raise OccAmdError(f"{what}: sem_gt {tuple(sem_gt.shape)} does not match sem_pred {tuple(sem_pred.shape)}")
+    if mask is not None and not (isinstance(mask, torch.Tensor) and mask.is_cuda and mask.dtype in (torch.bool, torch.uint8)
+                                 and mask.is_contiguous() and mask.numel() == sem_pred.numel()):
+        raise OccAmdError(f"{what}: mask must be a contiguous bool or uint8 device tensor of {sem_pred.numel()} elements")
+    if not isinstance(state, torch.Tensor):
+        raise TypeError(f"{what}: state must be a torch.Tensor")
+    dev = sem_pred.device
+    if sem_gt.device != dev or state.device != dev or (mask is not None and mask.device != dev):
+        raise OccAmdError(f"{what}: sem_pred, sem_gt, mask and state must be on one device")
+    _eval_state(what, state, confusion_state_words(free_id))
+    _launch(_lib.lib().occ_confusion_accumulate, dev, what, sem_pred, _SEM_DTYPE_CODES[sem_pred.dtype], sem_gt,
+            _SEM_DTYPE_CODES[sem_gt.dtype], mask, free_id, state, sem_pred.numel(), timing='confusion_accumulate')
+
+
 def submission_score_state_words(free_id=16):
     """int64 words of the submission score's state for classes 0..free_id (17 per class; layout: include/occnet_amd.h)."""
     n = int(_lib.lib().occ_submission_score_state_words(free_id))

@@ -4,3 +4,4 @@ from .ray_metrics import (calc_metrics, generate_lidar_rays, main, occ_class_nam
 from .ray_metrics_device import RayMetrics, main_device  # noqa: F401
 from .submission_device import SubmissionWriter  # noqa: F401
 from .submission_score import SubmissionScore  # noqa: F401
+from .voxel_miou import VoxelMIoU  # noqa: F401

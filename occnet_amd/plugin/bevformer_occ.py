@@ -52,6 +52,7 @@ class BEVFormerOcc(BaseModule):
         self.pretrained = pretrained
         self.video_test_mode = video_test_mode
         self.prev_frame_info = {'prev_bev': None, 'scene_token': None, 'prev_pos': 0, 'prev_angle': 0}
+        self._camera_visibility = None      # visibility.CameraVisibility of a use_mask head, made at the first need (camera_visibility)
 
     def train(self, mode=True):
         """Mode switch + cache safety net.  Every derived-weight cache (packed Linear / chain weights, folded backbone
@@ -304,6 +305,24 @@ class BEVFormerOcc(BaseModule):
             self.train()
         return prev_bev
 
+    def camera_visibility(self, voxel_semantics):
+        """The CameraVisibility that makes `mask_camera` for a use_mask head from the ground truth and img_metas alone, made at
+        the first call and again when the grid or the device changes: the head's pc_range, the device the model's parameters
+        are on, and the grid's voxel size — pc_range's x extent over the grid's X; the grid must have cubic voxels
+        (ValueError otherwise: the ray caster has one voxel size)."""
+        head = self.pts_bbox_head
+        pc_range = [float(v) for v in head.pc_range]
+        shape = tuple(voxel_semantics.shape[-3:])
+        sizes = [(pc_range[3 + k] - pc_range[k]) / shape[k] for k in range(3)]
+        if max(sizes) - min(sizes) > 1e-6 * max(sizes):
+            raise ValueError(f'camera_visibility: pc_range {pc_range} over a {shape} grid has no single voxel size ({sizes})')
+        device = next(self.parameters()).device
+        cv = self._camera_visibility
+        if cv is None or cv.device != device or tuple(cv.occ_size) != shape:
+            from ..visibility import CameraVisibility
+            cv = self._camera_visibility = CameraVisibility(pc_range, sizes[0], free_id=head.num_classes - 1, device=device)
+        return cv
+
     def forward_train(self, points=None, img_metas=None, gt_bboxes_3d=None, gt_labels_3d=None,
                       voxel_semantics=None, voxel_flow=None, mask_lidar=None, mask_camera=None,
                       gt_labels=None, gt_bboxes=None, img=None, proposals=None,
@@ -320,6 +339,8 @@ class BEVFormerOcc(BaseModule):
             img_feats, _ = self.extract_feat_u8(img_u8, img_norm_cfg, aug=img_aug)
         else:
             img_feats = self.extract_feat(img=img, img_metas=img_metas)
+        if mask_camera is None and getattr(self.pts_bbox_head, 'use_mask', False):
+            mask_camera = self.camera_visibility(voxel_semantics)(voxel_semantics, img_metas)
         losses = dict()
         losses.update(self.forward_pts_train(img_feats, gt_bboxes_3d, gt_labels_3d, voxel_semantics,
                                              voxel_flow, mask_camera, img_metas, gt_bboxes_ignore,
