@@ -1,4 +1,4 @@
-"""ctypes binding of the C ABI in include/occnet_amd.h (and the headers of EXTRA_HEADERS).
+"""ctypes binding of the C ABI in include/occnet_amd.h (and the headers of EXTENSION_HEADERS).
 
 The product path has no CPU fallback: if libocc_amd.so is missing or an entry point is absent this
 module raises at import/use time.  torch is imported first so the HIP runtime already loaded by
@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libocc_amd.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "occnet_amd.h")
 # headers whose prototypes lib() binds besides the main one's: extensions of the C ABI that leave occnet_amd.h as it is
 EXTRA_HEADERS = (os.path.join(os.path.dirname(_HERE), "include", "occnet_amd_visibility.h"),)
+INPUT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "occnet_amd_input.h")
+EXTENSION_HEADERS = EXTRA_HEADERS + (INPUT_HEADER,)      # all of them; EXTRA_HEADERS stays the visibility header alone
 
 
 class OccAmdError(RuntimeError):
@@ -92,7 +94,7 @@ def lib():
                 "(the MI355X path has no CPU fallback)")
         _lib = ctypes.CDLL(LIB_PATH)
         protos = prototypes()
-        for header in EXTRA_HEADERS:
+        for header in EXTENSION_HEADERS:
             with open(header) as f:
                 protos.update(prototypes(f.read()))
         for name, (restype, args) in protos.items():

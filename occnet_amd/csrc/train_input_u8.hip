@@ -20,68 +20,9 @@
 // address; the loads of a wave cover 768 contiguous bytes), one float4 store per plane.  blockIdx.y = image, so the
 // image's record arrives through uniform loads.  Source coordinates are clamped into the frame (the pad area reads
 // the frame's last row / column and discards it): nothing outside the NI * Hs * Ws * 3 bytes is read.
-#include "common.h"
-#include <float.h>
+#include "train_input.h"
 
 namespace occ {
-
-struct TrainInputArgs {
-  float mean[3], stdinv[3];
-  int Hs, Ws, H, W, to_rgb;
-  // GridMask (rotate = 1, offset = False): d, l, st_h, st_w as drawn; oy / ox = offset of the crop in the
-  // (1.5 H, 1.5 W) plane; nh / nw = number of bands (hh / d, ww / d); use_h / use_w / inv as 0 / 1
-  int gm, d, l, st_h, st_w, oy, ox, nh, nw, use_h, use_w, inv;
-};
-
-// band test of grid_mask.py:96-110 on coordinate t = Y - st + d (> 0 because st < d): quotient q = t / d - 1 is the band
-// number, r = t % d the position inside the period; in a band iff 0 <= q < n and r < l
-__device__ __forceinline__ int in_band(int q, int r, int n, int l) {
-  return lane_flag(q >= 0) & lane_flag(q < n) & lane_flag(r < l);
-}
-
-__device__ __forceinline__ void photometric_pixel(float& b, float& g, float& r, float delta, float alpha_pre, float sat,
-                                                  float hue, float alpha_post) {
-#pragma clang fp contract(off)        // the reference rounds every operation: no fused multiply-add
-  b = (b + delta) * alpha_pre;
-  g = (g + delta) * alpha_pre;
-  r = (r + delta) * alpha_pre;
-  // BGR -> HSV
-  const float v = fmaxf(fmaxf(b, g), r), vmin = fminf(fminf(b, g), r);
-  const float diff = v - vmin;
-  float s = fdiv(diff, fabsf(v) + FLT_EPSILON);
-  const float k = fdiv(60.f, diff + FLT_EPSILON);
-  const int is_r = lane_flag(v == r), is_g = lane_flag(v == g);
-  const float hr = (g - b) * k, hg = (b - r) * k + 120.f, hb = (r - g) * k + 240.f;
-  float h = hb;                                   // flat select chains: all three candidates are computed, no branch
-  h = is_g ? hg : h;
-  h = is_r ? hr : h;
-  h = lane_flag(h < 0.f) ? h + 360.f : h;
-  // saturation, hue
-  s *= sat;
-  h += hue;
-  h = lane_flag(h > 360.f) ? h - 360.f : h;
-  h = lane_flag(h < 0.f) ? h + 360.f : h;
-  // HSV -> BGR.  h is in [0, 360] here, so one step of -6 brings h / 60 into [0, 6)
-  const int grey = lane_flag(s == 0.f);
-  h *= (float)(1.0 / 60.0);
-  h = lane_flag(h < 0.f) ? h + 6.f : h;
-  h = lane_flag(h >= 6.f) ? h - 6.f : h;
-  const float fl = floorf(h);
-  const int over = lane_flag(fl >= 6.f);          // (unsigned)sector >= 6: sector = 0, f = 0
-  const float sec = over ? 0.f : fl;
-  const float f = over ? 0.f : h - fl;
-  const float p = v * (1.f - s), q = v * (1.f - s * f), t = v * (1.f - s * (1.f - f));
-  const int e0 = lane_flag(sec == 0.f), e1 = lane_flag(sec == 1.f), e2 = lane_flag(sec == 2.f), e3 = lane_flag(sec == 3.f),
-            e4 = lane_flag(sec == 4.f);
-  // tab = {v, p, q, t}; (b, g, r) = tab[{{1,3,0},{1,0,2},{3,0,1},{0,2,1},{0,1,3},{2,1,0}}[sector]]
-  float nb = q, ng = p, nr = v;                   // sector 5
-  nb = (e3 | e4) ? v : nb; nb = e2 ? t : nb; nb = (e0 | e1) ? p : nb;
-  ng = e3 ? q : ng; ng = (e1 | e2) ? v : ng; ng = e0 ? t : ng;
-  nr = e4 ? t : nr; nr = (e2 | e3) ? p : nr; nr = e1 ? q : nr;
-  b = (grey ? v : nb) * alpha_post;
-  g = (grey ? v : ng) * alpha_post;
-  r = (grey ? v : nr) * alpha_post;
-}
 
 __global__ __launch_bounds__(256) void train_input_u8_kernel(const unsigned char* __restrict__ x,
                                                              const float* __restrict__ records, float* __restrict__ out,
@@ -93,8 +34,6 @@ __global__ __launch_bounds__(256) void train_input_u8_kernel(const unsigned char
   const int img = blockIdx.y;
   const int y = item / W4, x0 = (item - y * W4) * 4;
   const float* rec = records + (long)img * 8;
-  const float delta = rec[0], alpha_pre = rec[1], sat = rec[2], hue = rec[3], alpha_post = rec[4];
-  const float pm0 = rec[5], pm1 = rec[6], pm2 = rec[7];
 
   // 12 clamped byte loads first, then the arithmetic
   const int sy = min(y, a.Hs - 1);
@@ -108,38 +47,17 @@ __global__ __launch_bounds__(256) void train_input_u8_kernel(const unsigned char
   }
 
   const int row_in = lane_flag(y < a.Hs);
-  int row_band = 0, cq = 0, cr = 0;
-  if (a.gm) {
-    const unsigned ty = (unsigned)(y + a.oy - a.st_h + a.d);
-    row_band = a.use_h & in_band((int)(ty / (unsigned)a.d) - 1, (int)(ty % (unsigned)a.d), a.nh, a.l);
-    const unsigned tx = (unsigned)(x0 + a.ox - a.st_w + a.d);
-    cq = (int)(tx / (unsigned)a.d) - 1;
-    cr = (int)(tx % (unsigned)a.d);
-  }
+  GridCursor gc = grid_cursor(a, y, x0);
 
   float o[3][4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    float b = (float)raw[j][0], g = (float)raw[j][1], r = (float)raw[j][2];
-    photometric_pixel(b, g, r, delta, alpha_pre, sat, hue, alpha_post);
-    // x = x[perm] (uniform per image), then the channel reversal of to_rgb
-    float c0 = r, c1 = r, c2 = r;
-    c0 = pm0 == 1.f ? g : c0; c0 = pm0 == 0.f ? b : c0;
-    c1 = pm1 == 1.f ? g : c1; c1 = pm1 == 0.f ? b : c1;
-    c2 = pm2 == 1.f ? g : c2; c2 = pm2 == 0.f ? b : c2;
-    const float n0 = a.to_rgb ? c2 : c0, n2 = a.to_rgb ? c0 : c2;
-    float m = 1.f;
-    if (a.gm) {
-      const int band = row_band | (a.use_w & in_band(cq, cr, a.nw, a.l));
-      m = (band ^ a.inv) ? 0.f : 1.f;
-      const int wrap = lane_flag(cr + 1 == a.d);         // next column
-      cr = wrap ? 0 : cr + 1;
-      cq += wrap;
-    }
+    float n[3];
+    normalised_pixel((float)raw[j][0], (float)raw[j][1], (float)raw[j][2], rec, a, n);
+    const float m = grid_next(a, gc);
     const int in = row_in & lane_flag(x0 + j < a.Ws);
-    o[0][j] = in ? (n0 - a.mean[0]) * a.stdinv[0] * m : 0.f;
-    o[1][j] = in ? (c1 - a.mean[1]) * a.stdinv[1] * m : 0.f;
-    o[2][j] = in ? (n2 - a.mean[2]) * a.stdinv[2] * m : 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) o[c][j] = in ? n[c] * m : 0.f;
   }
   const long plane = (long)a.H * a.W;
   float* dst = out + (long)img * 3 * plane + (long)y * a.W + x0;
@@ -154,30 +72,13 @@ extern "C" int occ_train_input_u8_f32(const uint8_t* x, const void* records, flo
                                       int H, int W, const float* mean, const float* std, int to_rgb,
                                       const int32_t* grid_mask, void* stream) {
   using namespace occ;
-  OCC_CHECK_ARG(x && records && out && mean && std, "train_input_u8: null pointer argument");
-  OCC_CHECK_ARG((reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(records) & 3) == 0,
-                "train_input_u8: out must be 16-byte aligned, records 4-byte aligned");
-  OCC_CHECK_ARG(n_images > 0 && n_images <= 65535 && Hs > 0 && Ws > 0, "train_input_u8: bad dimension");
+  if (int rc = check_input_buffers("train_input_u8", x, records, out, mean, std, n_images, Hs, Ws)) return rc;
   OCC_CHECK_ARG(H >= Hs && W >= Ws, "train_input_u8: padded size (%d, %d) smaller than the frames (%d, %d)", H, W, Hs, Ws);
-  OCC_CHECK_ARG((long)H * W < (1L << 30), "train_input_u8: image too large");
-  OCC_CHECK_ARG(std[0] != 0.f && std[1] != 0.f && std[2] != 0.f, "train_input_u8: zero std");
-  if (W % 4 != 0) {
-    set_error("train_input_u8: W = %d is not a multiple of 4 (one thread stores four pixels)", W);
-    return OCC_E_UNSUPPORTED;
-  }
+  if (int rc = check_input_output("train_input_u8", std, H, W)) return rc;
   TrainInputArgs a = {};
-  for (int c = 0; c < 3; ++c) { a.mean[c] = mean[c]; a.stdinv[c] = (float)(1.0 / (double)std[c]); }   // stdinv in f64 (mmcv), used in f32
-  a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W; a.to_rgb = to_rgb ? 1 : 0;
-  if (grid_mask && grid_mask[0]) {
-    const int d = grid_mask[1], l = grid_mask[2], st_h = grid_mask[3], st_w = grid_mask[4];
-    OCC_CHECK_ARG(d >= 2, "train_input_u8: grid mask period d = %d < 2", d);
-    OCC_CHECK_ARG(l >= 1 && l <= d - 1, "train_input_u8: grid mask band l = %d outside [1, d - 1]", l);
-    OCC_CHECK_ARG(st_h >= 0 && st_h < d && st_w >= 0 && st_w < d, "train_input_u8: grid mask start outside [0, d)");
-    const int hh = (int)(3L * H / 2), ww = (int)(3L * W / 2);           // int(1.5 * H)
-    a.gm = 1; a.d = d; a.l = l; a.st_h = st_h; a.st_w = st_w;
-    a.oy = (hh - H) / 2; a.ox = (ww - W) / 2; a.nh = hh / d; a.nw = ww / d;
-    a.use_h = grid_mask[5] ? 1 : 0; a.use_w = grid_mask[6] ? 1 : 0; a.inv = grid_mask[7] == 1 ? 1 : 0;
-  }
+  set_norm(a, mean, std, to_rgb);
+  a.Hs = Hs; a.Ws = Ws; a.H = H; a.W = W;
+  if (int rc = set_grid_mask(a, grid_mask, H, W, "train_input_u8")) return rc;
   const int items = H * (W / 4);
   hipLaunchKernelGGL(train_input_u8_kernel, dim3((unsigned)((items + 255) / 256), (unsigned)n_images), dim3(256), 0,
                      reinterpret_cast<hipStream_t>(stream), x, reinterpret_cast<const float*>(records), out, a);

@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .derived import DerivedCache
+from .io import check_scale, scaled_size
 from ._lib import OccAmdError, OccAmdUnsupported, f32, i32
 from ._lib import i64, ptr, stream_ptr  # noqa: F401  (not used here any more; callers import them from this module)
 
@@ -2486,36 +2487,66 @@ def train_input_u8(frames_u8, records, mean, std, to_rgb, size_divisor=32, grid_
     grid_mask.py:84-124).  grid_mask: None (not applied) or (d, l, st_h, st_w, use_h, use_w, mode) — the draws of
     GridMask.sample_params and the module's use_h / use_w / mode; rotate == 1 and offset == False only.
     out: optional (NI, 3, H, W) float32 contiguous device tensor to write into."""
+    return _u8_input("train_input_u8", frames_u8, records, mean, std, to_rgb, None, size_divisor, grid_mask, out)[0]
+
+
+def input_u8_scaled(frames_u8, records, mean, std, to_rgb, scale, size_divisor=32, grid_mask=None, out=None):
+    """train_input_u8 with RandomScaleImageMultiViewImage(scales=[scale]) between normalise and pad, in one launch:
+    frames_u8 (NI, Hs, Ws, 3) uint8 -> photometric distortion (records) -> normalise -> bilinear rescale to
+    (Hd, Wd) = (int(Hs * scale), int(Ws * scale)) -> pad to the next multiples of `size_divisor` -> GridMask of the padded
+    size.  The resize is the project's float32 definition (include/occnet_amd_input.h; io.random_scale_multiview is its host
+    twin); scale == 1.0 gives train_input_u8's tensor.  Arguments as train_input_u8's.
+    -> ((NI, 3, H, W) float32, (Hd, Wd))."""
+    _as_occ_error(check_scale, scale)         # a bad scale is refused before anything else is looked at
+    return _u8_input("input_u8_scaled", frames_u8, records, mean, std, to_rgb, scale, size_divisor, grid_mask, out)
+
+
+def _as_occ_error(fn, *args):
+    """fn(*args) of io's scale helpers, their ValueError as this module's error type."""
+    try:
+        return fn(*args)
+    except ValueError as e:
+        raise OccAmdError(f"input_u8_scaled: {e}") from None
+
+
+def _u8_input(what, frames_u8, records, mean, std, to_rgb, scale, size_divisor, grid_mask, out):
+    """The checks and the launch of train_input_u8 (scale None) and input_u8_scaled -> (out, (Hd, Wd))."""
     if not (isinstance(frames_u8, torch.Tensor) and frames_u8.is_cuda):
-        raise OccAmdError("train_input_u8: frames must be a device (HIP) tensor: the MI355X path has no CPU fallback")
+        raise OccAmdError(f"{what}: frames must be a device (HIP) tensor: the MI355X path has no CPU fallback")
     if not (frames_u8.dtype == torch.uint8 and frames_u8.dim() == 4 and frames_u8.shape[-1] == 3
             and frames_u8.is_contiguous()):
-        raise OccAmdUnsupported("train_input_u8: frames must be a contiguous (NI, Hs, Ws, 3) uint8 device tensor")
+        raise OccAmdUnsupported(f"{what}: frames must be a contiguous (NI, Hs, Ws, 3) uint8 device tensor")
     NI, Hs, Ws, _ = frames_u8.shape
+    Hd, Wd = (Hs, Ws) if scale is None else _as_occ_error(scaled_size, Hs, Ws, scale)
     if not isinstance(records, torch.Tensor):
         import numpy as np
         records = torch.from_numpy(np.ascontiguousarray(records, dtype=np.float32)).to(frames_u8.device)
     _need_cuda_f32("records", records)
     if tuple(records.shape) != (NI, 8):
-        raise OccAmdError(f"train_input_u8: records must be ({NI}, 8), got {tuple(records.shape)}")
+        raise OccAmdError(f"{what}: records must be ({NI}, 8), got {tuple(records.shape)}")
     d = int(size_divisor)
-    H, W = (Hs + d - 1) // d * d, (Ws + d - 1) // d * d
+    H, W = (Hd + d - 1) // d * d, (Wd + d - 1) // d * d
     if out is None:
         out = torch.empty((NI, 3, H, W), dtype=torch.float32, device=frames_u8.device)
     else:
         _need_cuda_f32("out", out)
         if tuple(out.shape) != (NI, 3, H, W):
-            raise OccAmdError(f"train_input_u8: out must be ({NI}, 3, {H}, {W}), got {tuple(out.shape)}")
+            raise OccAmdError(f"{what}: out must be ({NI}, 3, {H}, {W}), got {tuple(out.shape)}")
     mean_c = (f32 * 3)(*[float(v) for v in mean])
     std_c = (f32 * 3)(*[float(v) for v in std])
     gm_c = None
     if grid_mask is not None:
         if len(grid_mask) != 7:
-            raise OccAmdError("train_input_u8: grid_mask must be (d, l, st_h, st_w, use_h, use_w, mode)")
+            raise OccAmdError(f"{what}: grid_mask must be (d, l, st_h, st_w, use_h, use_w, mode)")
         gm_c = (i32 * 8)(1, *[int(v) for v in grid_mask])
-    _launch(_lib.lib().occ_train_input_u8_f32, frames_u8.device, "train_input_u8", frames_u8, records, out, NI, Hs, Ws, H, W,
-            mean_c, std_c, 1 if to_rgb else 0, gm_c, timing='train_input_u8')
-    return out
+    tail = (H, W, mean_c, std_c, 1 if to_rgb else 0, gm_c)
+    if scale is None:
+        _launch(_lib.lib().occ_train_input_u8_f32, frames_u8.device, what, frames_u8, records, out, NI, Hs, Ws, *tail,
+                timing=what)
+    else:
+        _launch(_lib.lib().occ_input_u8_scaled_f32, frames_u8.device, what, frames_u8, records, out, NI, Hs, Ws, Hd, Wd, *tail,
+                timing=what)
+    return out, (Hd, Wd)
 
 
 def bias_relu_maxpool_nhwc(y, bias):

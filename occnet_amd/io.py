@@ -4,6 +4,10 @@ or the nuScenes devkit.  Host-side formatting only (no model compute lives here)
 
   pad_multiview / normalize_multiview / to_batch   P/datasets/pipelines/transform_3d.py:12-101
                                                    (PadMultiViewImage size_divisor=32, NormalizeMultiviewImage)
+  random_scale_multiview / scale_img_metas         P/datasets/pipelines/transform_3d.py:292-331
+                                                   (RandomScaleImageMultiViewImage: the resize as this project defines it,
+                                                   DESIGN.md "Image scale on the device", and the meta keys it rewrites;
+                                                   the device chain is ext.input_u8_scaled)
   sample_photometric / photometric_distort         P/datasets/pipelines/transform_3d.py:102-189
                                                    (PhotoMetricDistortionMultiViewImage: the draws, and the host chain;
                                                    the device chain is ext.train_input_u8)
@@ -61,6 +65,80 @@ def normalize_multiview(imgs, mean, std, to_rgb=True):
             x = x[..., ::-1]
         out.append((x - mean) * stdinv)
     return out, dict(mean=mean.reshape(-1), std=std.reshape(-1), to_rgb=to_rgb)
+
+
+def check_scale(scale):
+    """-> float(scale); ValueError unless it is finite and positive."""
+    s = float(scale)
+    if not (np.isfinite(s) and s > 0.0):
+        raise ValueError(f"image scale must be finite and positive, got {scale!r}")
+    return s
+
+
+def scaled_size(h, w, scale):
+    """(Hd, Wd) = (int(h * scale), int(w * scale)): RandomScaleImageMultiViewImage truncates after a double multiply.
+    ValueError for a scale that is not finite and positive, or that leaves no pixel."""
+    s = check_scale(scale)
+    hd, wd = int(h * s), int(w * s)
+    if hd < 1 or wd < 1:
+        raise ValueError(f"image scale {s} leaves no pixel of a ({h}, {w}) image: ({hd}, {wd})")
+    return hd, wd
+
+
+def resize_taps(n_src, n_dst, reset_fraction):
+    """One axis of the linear resize n_src -> n_dst (DESIGN.md "Image scale on the device"): for every destination index d
+        f = float32((d + 0.5) * scale - 0.5), scale = 1.0 / (n_dst / n_src) in float64;  i = floor(f);  f = f - float32(i)
+    reset_fraction (the columns): i < 0 -> i = 0, f = 0 and i >= n_src - 1 -> i = n_src - 1, f = 0; otherwise (the rows) f
+    stays and only the indices are clipped.  -> (i0, i1 int64 (n_dst,), w0 = 1 - f, w1 = f float32 (n_dst,))."""
+    scale = 1.0 / (np.float64(n_dst) / np.float64(n_src))
+    f = ((np.arange(n_dst, dtype=np.float64) + 0.5) * scale - 0.5).astype(np.float32)
+    fl = np.floor(f)
+    i = fl.astype(np.int64)
+    f = f - fl
+    if reset_fraction:
+        f = np.where((i < 0) | (i >= n_src - 1), np.float32(0), f)
+    i0 = np.clip(i, 0, n_src - 1)
+    i1 = np.clip(i + 1, 0, n_src - 1) if not reset_fraction else np.minimum(i0 + 1, n_src - 1)
+    return i0, i1, np.float32(1) - f, f
+
+
+def random_scale_multiview(imgs, scale):
+    """RandomScaleImageMultiViewImage(scales=[scale]) on the images: list of float32 (H, W, C) arrays -> (resized list of
+    (int(H * scale), int(W * scale), C) float32 arrays, meta dict).  The bilinear resize in float32, every operation
+    rounded: columns first (h = x[r, c0] * a0 + x[r, c1] * a1 for both rows), then rows (h0 * b0 + h1 * b1), taps and
+    weights from resize_taps.  The metas' side of the transform is scale_img_metas."""
+    out = []
+    for img in imgs:
+        assert img.dtype == np.float32 and img.ndim == 3
+        hd, wd = scaled_size(img.shape[0], img.shape[1], scale)
+        r0, r1, b0, b1 = resize_taps(img.shape[0], hd, reset_fraction=False)
+        c0, c1, a0, a1 = resize_taps(img.shape[1], wd, reset_fraction=True)
+        a0, a1 = a0[None, :, None], a1[None, :, None]
+        h0 = img[r0][:, c0] * a0 + img[r0][:, c1] * a1
+        h1 = img[r1][:, c0] * a0 + img[r1][:, c1] * a1
+        out.append(h0 * b0[:, None, None] + h1 * b1[:, None, None])
+    return out, dict(scale=float(scale), img_shape=[i.shape for i in out], ori_shape=[i.shape for i in out])
+
+
+def scale_img_metas(meta, scale, src_hw, size_divisor=32):
+    """The img_meta of one sample after RandomScaleImageMultiViewImage(scales=[scale]) and PadMultiViewImage(size_divisor) on
+    (Hs, Ws) = src_hw frames -> a copy of `meta` with
+        lidar2img     diag(scale, scale, 1, 1) @ lidar2img per view (the scale itself, not the size ratio, as the reference)
+        ori_shape     (Hd, Wd, 3) per view
+        img_shape, pad_shape   (H, W, 3) per view, the padded size the model is fed
+    and every other key (cam_intrinsic among them, as in the reference) as it was."""
+    hd, wd = scaled_size(src_hw[0], src_hw[1], scale)
+    d = int(size_divisor)
+    H, W = (hd + d - 1) // d * d, (wd + d - 1) // d * d
+    factor = np.eye(4)
+    factor[0, 0] = factor[1, 1] = float(scale)
+    out = dict(meta)
+    out['lidar2img'] = [factor @ np.asarray(m) for m in meta['lidar2img']]
+    views = len(out['lidar2img'])
+    out['ori_shape'] = [(hd, wd, 3)] * views
+    out['img_shape'] = [(H, W, 3)] * views
+    out['pad_shape'] = [(H, W, 3)] * views
+    return out
 
 
 _EPS32 = np.float32(np.finfo(np.float32).eps)     # FLT_EPSILON

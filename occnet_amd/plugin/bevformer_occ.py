@@ -9,7 +9,7 @@ train_cfg / test_cfg is injected into the head's config.
 import torch
 
 from .. import cache_epoch, derived, ext
-from ..io import identity_photometric
+from ..io import identity_photometric, scaled_size
 from .bricks import BaseModule
 from .grid_mask import GridMask
 from .registry import DETECTORS, build_backbone, build_head, build_neck
@@ -187,15 +187,18 @@ class BEVFormerOcc(BaseModule):
     def extract_feat(self, img, img_metas=None, len_queue=None):
         return self.extract_img_feat(img, img_metas, len_queue=len_queue)
 
-    def _train_input_u8(self, frames_u8, img_norm_cfg, size_divisor, aug):
+    def _train_input_u8(self, frames_u8, img_norm_cfg, size_divisor, aug, img_scale=None):
         """(NI, Hs, Ws, 3) uint8 frames -> the (NI, 3, H, W) float32 backbone input in one launch
         (ext.train_input_u8): photometric distortion with the records `aug`, normalise, pad and — where
         extract_img_feat would apply the GridMask module — the module's mask from its own draws
         (GridMask.sample_params: same RNG consumption as the module's forward, which is then skipped).  A GridMask
-        with rotate > 1 or offset=True has no closed form in the kernel: the module is applied to the result."""
+        with rotate > 1 or offset=True has no closed form in the kernel: the module is applied to the result.
+        img_scale: RandomScaleImageMultiViewImage(scales=[img_scale]) between normalise and pad (ext.input_u8_scaled);
+        H x W, which the mask is drawn for, is then the padded size of the scaled image."""
         NI, Hs, Ws, _ = frames_u8.shape
         d = int(size_divisor)
-        H, W = (Hs + d - 1) // d * d, (Ws + d - 1) // d * d
+        Hd, Wd = (Hs, Ws) if img_scale is None else scaled_size(Hs, Ws, img_scale)
+        H, W = (Hd + d - 1) // d * d, (Wd + d - 1) // d * d
         gm, module_mask = None, False
         plan_serves = not self.training and not torch.is_grad_enabled() and self._current_plan() is not None
         if self.use_grid_mask and not plan_serves:
@@ -206,21 +209,32 @@ class BEVFormerOcc(BaseModule):
                     gm = tuple(drawn) + (int(bool(g.use_h)), int(bool(g.use_w)), int(g.mode))
             else:
                 module_mask = True
-        x = ext.train_input_u8(frames_u8, aug, img_norm_cfg['mean'], img_norm_cfg['std'],
-                               bool(img_norm_cfg.get('to_rgb', True)), size_divisor=d, grid_mask=gm)
+        norm = (img_norm_cfg['mean'], img_norm_cfg['std'], bool(img_norm_cfg.get('to_rgb', True)))
+        if img_scale is None:
+            x = ext.train_input_u8(frames_u8, aug, *norm, size_divisor=d, grid_mask=gm)
+        else:
+            x, _ = ext.input_u8_scaled(frames_u8, aug, *norm, img_scale, size_divisor=d, grid_mask=gm)
         return self.grid_mask(x) if module_mask else x
 
-    def extract_feat_u8(self, img_u8, img_norm_cfg, size_divisor=32, aug=None, len_queue=None):
+    def extract_feat_u8(self, img_u8, img_norm_cfg, size_divisor=32, aug=None, len_queue=None, img_scale=None,
+                        img_metas=None):
         """Device-side input path: img_u8 (B, N, Hs, Ws, 3) uint8 HWC raw camera images on
         the device.  NormalizeMultiviewImage(**img_norm_cfg) + PadMultiViewImage(size_divisor) + the layout
         change of DefaultFormatBundle3D (reference transform_3d.py:31-45,82-94) run inside the stem kernel of
         the inference plan, or as torch device ops without it.  -> (list of (B, N, C, h, w) maps, padded (H, W)).
         aug: (B * N, 8) photometric records (io.sample_photometric / io.identity_photometric) select the training
         input kernel instead: distortion + normalise + pad + GridMask in one launch (_train_input_u8), then the
-        backbone as extract_img_feat runs it."""
+        backbone as extract_img_feat runs it.
+        img_scale: the image scale of RandomScaleImageMultiViewImage; takes the same kernel route (ext.input_u8_scaled),
+        with the identity records when `aug` is None.  img_metas: with a scale, the metas of these B samples, checked before
+        any launch to be those of the scaled and padded images (_check_scaled_metas)."""
         B, N, Hs, Ws, _ = img_u8.shape
+        if img_scale is not None and img_metas is not None:
+            self._check_scaled_metas(img_metas, (Hs, Ws), img_scale, size_divisor)
+        if img_scale is not None and aug is None:
+            aug = identity_photometric(B * N)
         if aug is not None:
-            x = self._train_input_u8(img_u8.reshape(B * N, Hs, Ws, 3), img_norm_cfg, size_divisor, aug)
+            x = self._train_input_u8(img_u8.reshape(B * N, Hs, Ws, 3), img_norm_cfg, size_divisor, aug, img_scale)
             H, W = x.shape[-2:]
             return self.extract_img_feat(x.view(B, N, 3, H, W), len_queue=len_queue, grid_masked=True), (H, W)
         mean, std = img_norm_cfg['mean'], img_norm_cfg['std']
@@ -275,10 +289,11 @@ class BEVFormerOcc(BaseModule):
             return self.forward_train(**kwargs)
         return self.forward_test(**kwargs)
 
-    def obtain_history_bev(self, imgs_queue, img_metas_list, img_norm_cfg=None, img_aug=None):
+    def obtain_history_bev(self, imgs_queue, img_metas_list, img_norm_cfg=None, img_aug=None, img_scale=None):
         """BEV of the history frames, iteratively, without gradients
         (imgs_queue (bs, len_queue, N, 3, H, W), or raw uint8 frames (bs, len_queue, N, Hs, Ws, 3) with
-        img_norm_cfg and optional (bs * len_queue * N, 8) photometric records img_aug, as forward_train takes them)."""
+        img_norm_cfg, optional (bs * len_queue * N, 8) photometric records img_aug and an optional img_scale, as forward_train
+        takes them)."""
         was_training = self.training
         object.__setattr__(self, '_in_history', True)      # no content fingerprint for this eval <-> train flip
         self.eval()
@@ -290,7 +305,8 @@ class BEVFormerOcc(BaseModule):
                 if img_aug is None:
                     img_aug = identity_photometric(bs * len_queue * num_cams)
                 img_feats_list, _ = self.extract_feat_u8(imgs_queue.reshape(bs * len_queue, num_cams, Hs, Ws, 3),
-                                                         img_norm_cfg, aug=img_aug, len_queue=len_queue)
+                                                         img_norm_cfg, aug=img_aug, len_queue=len_queue, img_scale=img_scale,
+                                                         img_metas=[each[i] for each in img_metas_list for i in range(len_queue)])
             else:
                 bs, len_queue, num_cams, C, H, W = imgs_queue.shape
                 imgs_queue = imgs_queue.reshape(bs * len_queue, num_cams, C, H, W)
@@ -327,17 +343,20 @@ class BEVFormerOcc(BaseModule):
                       voxel_semantics=None, voxel_flow=None, mask_lidar=None, mask_camera=None,
                       gt_labels=None, gt_bboxes=None, img=None, proposals=None,
                       gt_bboxes_ignore=None, img_depth=None, img_mask=None, img_u8=None, img_norm_cfg=None,
-                      img_aug=None):
+                      img_aug=None, img_scale=None):
         """img_u8 (B, N, Hs, Ws, 3) uint8 device frames + img_norm_cfg (+ img_aug, (B * N, 8) records of
         io.sample_photometric; identity when None) instead of `img`: the input tensor is built on the device by
-        ext.train_input_u8, GridMask included when use_grid_mask."""
+        ext.train_input_u8, GridMask included when use_grid_mask.  img_scale: the frames are rescaled on the way
+        (ext.input_u8_scaled); img_metas must be those of the scaled images (io.scale_img_metas)."""
         if img_u8 is not None:
             if img is not None:
                 raise ValueError('forward_train: pass img or img_u8, not both')
             if img_aug is None:
                 img_aug = identity_photometric(img_u8.shape[0] * img_u8.shape[1])
-            img_feats, _ = self.extract_feat_u8(img_u8, img_norm_cfg, aug=img_aug)
+            img_feats, _ = self.extract_feat_u8(img_u8, img_norm_cfg, aug=img_aug, img_scale=img_scale, img_metas=img_metas)
         else:
+            if img_scale is not None:
+                raise ValueError('forward_train: img_scale rescales img_u8 frames; an `img` tensor is taken as it is')
             img_feats = self.extract_feat(img=img, img_metas=img_metas)
         if mask_camera is None and getattr(self.pts_bbox_head, 'use_mask', False):
             mask_camera = self.camera_visibility(voxel_semantics)(voxel_semantics, img_metas)
@@ -361,6 +380,30 @@ class BEVFormerOcc(BaseModule):
         occ, flow = self.pts_bbox_head.get_occ(outs, img_metas, rescale=rescale)
         return outs['bev_embed'], occ, flow
 
-    def simple_test(self, img_metas, img=None, prev_bev=None, rescale=False):
-        img_feats = self.extract_feat(img=img, img_metas=img_metas)
+    @staticmethod
+    def _check_scaled_metas(img_metas, frames_hw, img_scale, size_divisor):
+        """With an image scale the caller scales the metas, as the reference's pipeline does; scaled images under unscaled
+        matrices would project every reference point to the wrong pixel without any error.  Checked before any launch:
+        every img_shape must be the padded size of the (Hs, Ws) = frames_hw frames at img_scale."""
+        hd, wd = scaled_size(frames_hw[0], frames_hw[1], img_scale)
+        d = int(size_divisor)
+        hw = ((hd + d - 1) // d * d, (wd + d - 1) // d * d)
+        for b, meta in enumerate(img_metas):
+            for v, shape in enumerate(meta['img_shape']):
+                if tuple(int(n) for n in shape[:2]) != hw:
+                    raise ValueError(f"img_scale: img_metas[{b}]['img_shape'][{v}] is {tuple(shape)}, the scaled and padded "
+                                     f"images are {hw}: pass metas scaled by io.scale_img_metas")
+
+    def simple_test(self, img_metas, img=None, prev_bev=None, rescale=False, img_u8=None, img_norm_cfg=None, img_scale=None):
+        """img_u8 (B, N, Hs, Ws, 3) uint8 device frames + img_norm_cfg instead of `img`: extract_feat_u8's route, the stem
+        of the inference plan reading the frames where there is one.  img_scale: the frames are rescaled on the way
+        (ext.input_u8_scaled -> the backbone); img_metas must be those of the scaled images (io.scale_img_metas)."""
+        if img_u8 is not None:
+            if img is not None:
+                raise ValueError('simple_test: pass img or img_u8, not both')
+            img_feats, _ = self.extract_feat_u8(img_u8, img_norm_cfg, img_scale=img_scale, img_metas=img_metas)
+        else:
+            if img_scale is not None:
+                raise ValueError('simple_test: img_scale rescales img_u8 frames; an `img` tensor is taken as it is')
+            img_feats = self.extract_feat(img=img, img_metas=img_metas)
         return self.simple_test_pts(img_feats, img_metas, prev_bev, rescale=rescale)
