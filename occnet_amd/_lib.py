@@ -16,7 +16,8 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "occnet_amd.h")
 # headers whose prototypes lib() binds besides the main one's: extensions of the C ABI that leave occnet_amd.h as it is
 EXTRA_HEADERS = (os.path.join(os.path.dirname(_HERE), "include", "occnet_amd_visibility.h"),)
 INPUT_HEADER = os.path.join(os.path.dirname(_HERE), "include", "occnet_amd_input.h")
-EXTENSION_HEADERS = EXTRA_HEADERS + (INPUT_HEADER,)      # all of them; EXTRA_HEADERS stays the visibility header alone
+DVR_HEADER = os.path.join(os.path.dirname(_HERE), "include", "occnet_amd_dvr.h")
+EXTENSION_HEADERS = EXTRA_HEADERS + (INPUT_HEADER, DVR_HEADER)      # all of them; EXTRA_HEADERS stays the visibility header alone
 
 
 class OccAmdError(RuntimeError):

@@ -48,6 +48,7 @@ struct RmHit {
 struct RmRay {      // per-ray constants of the traversal (dvr_render_forward_kernel's set-up)
   int vx, vy, vz, stepX, stepY, stepZ;
   double tMaxX, tMaxY, tMaxZ, tDeltaX, tDeltaY, tDeltaZ;
+  double gt_d;      // |end - origin| (dvr_render_train.hip: the pre-entry stop, the depth target and the padded-ray rule)
 };
 
 #pragma clang fp contract(off)
@@ -68,6 +69,7 @@ __device__ __forceinline__ RmRay rm_ray_setup(float fxo, float fyo, float fzo, f
   r.tDeltaX = (dx != 0) ? r.stepX / dx : DBL_MAX;
   r.tDeltaY = (dy != 0) ? r.stepY / dy : DBL_MAX;
   r.tDeltaZ = (dz != 0) ? r.stepZ / dz : DBL_MAX;
+  r.gt_d = gt_d;
   return r;
 }
 

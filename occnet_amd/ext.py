@@ -1853,6 +1853,37 @@ def dvr_render_forward(sigma, origin, points, tindex, grid=None, phase_name="tes
     return pred, gt, coord
 
 
+_DVR_LOSS_CODES = {"l1": 0, "l2": 1, "absrel": 2, "bce": 0}     # "bce" is l1 in the reference too (dvr.cu:676-677)
+
+
+def dvr_render(sigma, origin, points, tindex, loss_name):
+    """Same call shape as the reference's `dvr.render(sigma, origin, points, tindex, loss_name)` (tools/ray_iou/lib/dvr/dvr.cu:
+    648-703): sigma (N, T, Z, Y, X) densities, origin (N, T, 3), points (N, M, >=3) in voxel units, tindex (N, M), all float32
+    device tensors; loss_name "l1", "l2", "absrel" or "bce" (= l1).
+    -> (pred_dist (N, M), gt_dist (N, M), grad_sigma (N, T, Z, Y, X)) float32: the expected depth of every ray, its clamped
+    target, and d(sum of the per-ray losses) / d sigma, accumulated with float atomics (last bits vary from run to run).
+    Rays that are not rendered (include/occnet_amd_dvr.h: padded rays) keep -1 and add nothing."""
+    if loss_name not in _DVR_LOSS_CODES:
+        raise OccAmdError(f"UNKNOWN LOSS TYPE: {loss_name}")       # the reference prints this and calls exit(1)
+    for n, t in (("sigma", sigma), ("origin", origin), ("points", points), ("tindex", tindex)):
+        _need_cuda_f32(n, t)
+    if sigma.dim() != 5 or origin.dim() != 3 or points.dim() != 3 or tindex.dim() != 2:
+        raise OccAmdError("dvr_render: expected sigma (N,T,Z,Y,X), origin (N,T,3), points (N,M,>=3), tindex (N,M)")
+    N, T, Z, Y, X = sigma.shape
+    M = points.shape[1]
+    if (points.shape[0] != N or tuple(tindex.shape) != (N, M) or tuple(origin.shape) != (N, T, 3) or points.shape[2] < 3):
+        raise OccAmdError("dvr_render: inconsistent shapes")
+    dev = sigma.device
+    if any(t.device != dev for t in (origin, points, tindex)):
+        raise OccAmdError("dvr_render: all tensors must be on one device")
+    pred = torch.empty((N, M), dtype=torch.float32, device=dev)
+    gt = torch.empty((N, M), dtype=torch.float32, device=dev)
+    grad = torch.empty_like(sigma)
+    _launch(_lib.lib().occ_dvr_render_f32, dev, "dvr_render", sigma, origin, points, tindex, pred, gt, grad,
+            N, T, Z, Y, X, M, points.shape[2], _DVR_LOSS_CODES[loss_name], timing='dvr_render')
+    return pred, gt, grad
+
+
 _SEM_DTYPE_CODES = {torch.uint8: 0, torch.int64: 1}
 _ORIGIN_DTYPE_CODES = {torch.float32: 0, torch.float64: 1}
 

@@ -14,6 +14,7 @@ from .detection_names import (CustomMSDeformableAttention, DetectionTransformerD
 from .encoder import BEVFormerEncoder, BEVFormerLayer, MyCustomBaseTransformerLayer  # noqa: F401
 from .functions import (MultiScaleDeformableAttnFunction_fp16,  # noqa: F401
                         MultiScaleDeformableAttnFunction_fp32)
+from .ray_depth_loss import DvrRenderLoss, RayDepthLoss  # noqa: F401
 from .registry import *  # noqa: F401,F403
 from .registry import (BBOX_ASSIGNERS, DATASETS, MATCH_COST, OPTIMIZERS, PIPELINES, RUNNERS,
                        SAMPLER, register_parse_only)

@@ -277,12 +277,14 @@ class BEVFormerOcc(BaseModule):
         return list(res.missing_keys), list(res.unexpected_keys)
 
     def forward_pts_train(self, pts_feats, gt_bboxes_3d, gt_labels_3d, voxel_semantics, voxel_flow,
-                          mask_camera, img_metas, gt_bboxes_ignore=None, prev_bev=None):
+                          mask_camera, img_metas, gt_bboxes_ignore=None, prev_bev=None, lidar_origins=None):
+        depth = {} if lidar_origins is None else dict(lidar_origins=lidar_origins)      # a head's configured loss_depth
         if getattr(self.pts_bbox_head, 'fused_loss', False):     # heads + losses as one node (OCC_TRAIN_FUSED_LOSS)
-            return self.pts_bbox_head.forward_loss(pts_feats, img_metas, prev_bev, voxel_semantics, voxel_flow, mask_camera)
+            return self.pts_bbox_head.forward_loss(pts_feats, img_metas, prev_bev, voxel_semantics, voxel_flow, mask_camera,
+                                                   **depth)
         outs = self.pts_bbox_head(pts_feats, img_metas, prev_bev)
         return self.pts_bbox_head.loss(voxel_semantics, voxel_flow, mask_camera, outs,
-                                       img_metas=img_metas)
+                                       img_metas=img_metas, **depth)
 
     def forward(self, return_loss=True, **kwargs):
         if return_loss:
@@ -343,8 +345,9 @@ class BEVFormerOcc(BaseModule):
                       voxel_semantics=None, voxel_flow=None, mask_lidar=None, mask_camera=None,
                       gt_labels=None, gt_bboxes=None, img=None, proposals=None,
                       gt_bboxes_ignore=None, img_depth=None, img_mask=None, img_u8=None, img_norm_cfg=None,
-                      img_aug=None, img_scale=None):
-        """img_u8 (B, N, Hs, Ws, 3) uint8 device frames + img_norm_cfg (+ img_aug, (B * N, 8) records of
+                      img_aug=None, img_scale=None, lidar_origins=None):
+        """lidar_origins (B, T, 3), ego metres (io.lidar_origins): the ray origins of the head's `loss_depth`, when configured.
+        img_u8 (B, N, Hs, Ws, 3) uint8 device frames + img_norm_cfg (+ img_aug, (B * N, 8) records of
         io.sample_photometric; identity when None) instead of `img`: the input tensor is built on the device by
         ext.train_input_u8, GridMask included when use_grid_mask.  img_scale: the frames are rescaled on the way
         (ext.input_u8_scaled); img_metas must be those of the scaled images (io.scale_img_metas)."""
@@ -363,7 +366,8 @@ class BEVFormerOcc(BaseModule):
         losses = dict()
         losses.update(self.forward_pts_train(img_feats, gt_bboxes_3d, gt_labels_3d, voxel_semantics,
                                              voxel_flow, mask_camera, img_metas, gt_bboxes_ignore,
-                                             prev_bev=None))
+                                             prev_bev=None,
+                                             **({} if lidar_origins is None else dict(lidar_origins=lidar_origins))))
         return losses
 
     def forward_test(self, img_metas, img=None, voxel_semantics=None, mask_lidar=None,

@@ -26,7 +26,7 @@ class BEVFormerOccHead(BaseModule):
     def __init__(self, *args, with_box_refine=False, as_two_stage=False, transformer=None,
                  bbox_coder=None, num_cls_fcs=2, code_weights=None,
                  pc_range=[-40, -40, -1.0, 40, 40, 5.4], bev_h=30, bev_w=30, loss_occ=None,
-                 loss_flow=None, use_mask=False, positional_encoding=None, **kwargs):
+                 loss_flow=None, use_mask=False, positional_encoding=None, loss_depth=None, **kwargs):
         super().__init__()
         self.bev_h = bev_h
         self.bev_w = bev_w
@@ -43,6 +43,15 @@ class BEVFormerOccHead(BaseModule):
         self.num_cls_fcs = num_cls_fcs - 1
         self.loss_occ = build_loss(loss_occ)
         self.loss_flow = build_loss(loss_flow)
+        # opt-in ray-depth supervision (ray_depth_loss.RayDepthLoss); None: no module, no code path and no number changes.
+        # The geometry the config leaves out is the head's own: its pc_range, cubic voxels of real_w / bev_w, last class free.
+        self.loss_depth = None
+        if loss_depth is not None:
+            cfg = dict(loss_depth)
+            cfg.setdefault('pc_range', pc_range)
+            cfg.setdefault('voxel_size', self.real_w / self.bev_w)
+            cfg.setdefault('free_id', self.num_classes - 1)
+            self.loss_depth = build_loss(cfg)
         self.positional_encoding = build_positional_encoding(positional_encoding)
         self.transformer = build_transformer(transformer)
         self.embed_dims = self.transformer.embed_dims
@@ -93,29 +102,38 @@ class BEVFormerOccHead(BaseModule):
         return preds
 
     def loss(self, voxel_semantics, voxel_flow, mask_camera, preds_dicts, gt_bboxes_ignore=None,
-             img_metas=None):
+             img_metas=None, lidar_origins=None):
+        """lidar_origins (B, T, 3), ego metres: the origins of the rays of a configured `loss_depth` (required then)."""
         loss_occ, loss_flow = self.loss_single(voxel_semantics, voxel_flow, mask_camera,
                                                preds_dicts['occ'].float(),
                                                preds_dicts['flow'].float())
-        return dict(loss_occ=loss_occ, loss_flow=loss_flow)
+        losses = dict(loss_occ=loss_occ, loss_flow=loss_flow)
+        if self.loss_depth is not None:
+            if lidar_origins is None:
+                raise ValueError('BEVFormerOccHead.loss: loss_depth is configured and needs lidar_origins (B, T, 3)')
+            targets = self.loss_depth.targets_from_occupancy(voxel_semantics, lidar_origins)
+            losses['loss_depth'] = self.loss_depth(preds_dicts['occ'].float(), *targets)
+        return losses
 
     def _fused_loss_ok(self, mlvl_feats):
         """Everything the fused heads + loss node needs that is known BEFORE the decoder runs (its BatchNorms update their
         statistics: no second pass after that): autograd on, device fp32 features, the heads and the two losses in the forms
-        the kernels compute, num_classes <= 30."""
+        the kernels compute, num_classes <= 30 — and no `loss_depth`: the fused node never materialises the logits that
+        the ray-depth loss renders."""
         t, lo, lf = self.transformer, self.loss_occ, self.loss_flow
-        return (self.fused_loss and torch.is_grad_enabled() and mlvl_feats[0].is_cuda
+        return (self.fused_loss and self.loss_depth is None and torch.is_grad_enabled() and mlvl_feats[0].is_cuda
                 and mlvl_feats[0].dtype != torch.float64 and t._heads_fusable()
                 and t.out_dim == 32 and t.predicter[0].weight.dtype == torch.float32
                 and type(lo) is CrossEntropyLoss and type(lf) is L1Loss and lo.reduction in ('mean', 'sum')
                 and lf.reduction == lo.reduction and self.num_classes <= 30)
 
-    def forward_loss(self, mlvl_feats, img_metas, prev_bev, voxel_semantics, voxel_flow, mask_camera):
+    def forward_loss(self, mlvl_feats, img_metas, prev_bev, voxel_semantics, voxel_flow, mask_camera, lidar_origins=None):
         """loss(forward(...)) -> {'loss_occ', 'loss_flow'}; with `fused_loss` (and its conditions, _fused_loss_ok) the heads
         and both losses run as one node on the decoder features, and the logits are never materialised.  Otherwise, or when
         the node refuses its inputs, today's modules run and give today's numbers."""
         if not self._fused_loss_ok(mlvl_feats):
-            return self.loss(voxel_semantics, voxel_flow, mask_camera, self(mlvl_feats, img_metas, prev_bev))
+            return self.loss(voxel_semantics, voxel_flow, mask_camera, self(mlvl_feats, img_metas, prev_bev),
+                             lidar_origins=lidar_origins)
         from .. import ext
         bev_queries, bev_pos, grid_length = self._bev_inputs(mlvl_feats)
         t = self.transformer

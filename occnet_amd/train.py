@@ -58,10 +58,11 @@ def synthetic_targets(bev_h, bev_w, pillar_h, num_classes=18, batch=1, seed=0, d
 
 
 def train_step(model, optimizer, img, img_metas, voxel_semantics, voxel_flow, mask_camera,
-               max_norm=35.0, autocast_backbone=False, img_u8=None, img_norm_cfg=None, img_aug=None):
+               max_norm=35.0, autocast_backbone=False, img_u8=None, img_norm_cfg=None, img_aug=None, lidar_origins=None):
     """One optimisation step; returns the rank-local loss dict (python floats are NOT synchronised:
     call .item() on the values only when logging).  img_u8 / img_norm_cfg / img_aug (with img=None): raw uint8
-    frames and photometric records, handed to BEVFormerOcc.forward_train."""
+    frames and photometric records, handed to BEVFormerOcc.forward_train.  lidar_origins (B, T, 3): the ray origins of a head
+    configured with `loss_depth` (the config key is the switch; without it the argument is not passed on)."""
     net = model.module if hasattr(model, 'module') else model
     optimizer.zero_grad(set_to_none=True)
     # the stock MIOpen backbone may run in bf16 (the hand-written hot path stays fp32): a detector attribute,
@@ -69,6 +70,8 @@ def train_step(model, optimizer, img, img_metas, voxel_semantics, voxel_flow, ma
     # forward that bypasses the wrapper leaves the gradients un-reduced (each rank would diverge silently)
     net.backbone_autocast_dtype = torch.bfloat16 if autocast_backbone else None
     u8 = {} if img_u8 is None else dict(img_u8=img_u8, img_norm_cfg=img_norm_cfg, img_aug=img_aug)
+    if lidar_origins is not None:
+        u8['lidar_origins'] = lidar_origins
     losses = model(return_loss=True, img_metas=img_metas, img=img, voxel_semantics=voxel_semantics,
                    voxel_flow=voxel_flow, mask_camera=mask_camera, **u8)
     loss = sum(losses.values())
