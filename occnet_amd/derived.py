@@ -61,6 +61,19 @@ class DerivedCache:
         self.entries.clear()
 
 
+def snapshot():
+    """What every registered cache holds now, for restore(): a test that runs the wrappers on tensors of its own puts the
+    caches back afterwards, so that they do not go on pinning those tensors."""
+    return [(cache, dict(cache.entries)) for cache in _REGISTERED]
+
+
+def restore(snap):
+    """Put the caches of a snapshot() back to what they held then (a cache registered since is left alone)."""
+    for cache, entries in snap:
+        cache.entries.clear()
+        cache.entries.update(entries)
+
+
 def owned(owner, attr):
     """The single-entry cache that hangs on `owner` (a module) as `attr`, made at first use; nn.Module does not register it."""
     cache = owner.__dict__.get(attr)

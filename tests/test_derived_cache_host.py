@@ -147,3 +147,23 @@ def test_registered_caches_are_emptied_by_invalidate_caches():
     assert w2 is not w and torch.equal(w2, w)
     owned = DerivedCache("owned", 1)                            # module-owned caches do not register
     assert owned not in derived._REGISTERED
+
+
+def test_snapshot_and_restore_put_the_registered_caches_back():
+    """An entry made after the snapshot leaves with restore() (and with it the pin on its sources); one made before stays."""
+    cache, calls = DerivedCache("snap", 4, register=True), []
+    try:
+        old, new = torch.ones(3), torch.ones(5)
+        v = _doubling(cache, old, calls)
+        snap = derived.snapshot()
+        _doubling(cache, new, calls)
+        ref = weakref.ref(new)
+        assert len(cache) == 2
+        derived.restore(snap)
+        assert len(cache) == 1 and _doubling(cache, old, calls) is v and len(calls) == 2
+        del new
+        gc.collect()
+        assert ref() is None                                    # the cache no longer pins the later source
+    finally:
+        derived._REGISTERED.remove(cache)
+
